@@ -14,7 +14,13 @@ layers' fwd+bwd are captured once into a hipGraph and replayed (gspn_amd/graph.p
 all-reduce and the Adam update stay eager.  --no-overlap runs the geometry inline on the main stream, --no-graph
 enqueues kernel by kernel (same kernels, same results either way).
 
+A plain run does only what the headline needs: set up, warm up, time --steps steps, print the line (`value`, `ms_per_step`).  --full also
+brackets the FPS / ball-query launches of the timed steps with HIP events (`roofline`), times the CPU baseline, measures the collective at
+N > 1 and writes bench_detail.json; --detail (implies --full) adds the post-run legs.  --dump-outputs DIR writes what the last timed step
+computed (dump_outputs) for comparing two builds.
+
   python bench.py --gpus 1 --steps 100 --warmup 10      (the defaults)
+  python bench.py --full                                 (everything the benchmark measures and checks besides the headline)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
 import argparse
@@ -89,17 +95,27 @@ def main():
     ap.add_argument("--no-graph", action="store_true", help="enqueue the layers kernel by kernel instead of replaying a captured hipGraph")
     ap.add_argument("--sync-bn", action="store_true", help="optional SyncBN (global-batch statistics, SURVEY 8e): unfused layers + two small "
                     "all-reduces per layer, no hipGraph; NOT the headline configuration")
-    ap.add_argument("--detail", action="store_true", help="after the headline run, also run the post-run legs (ball-query / layer / per-op rooflines, "
+    ap.add_argument("--detail", action="store_true", help="(implies --full) after the headline run, also run the post-run legs (ball-query / layer / per-op rooflines, "
                     "the S and D cloud kinds, the other BASELINE configs, the reference's own harness shapes: several child processes, a few minutes) "
                     "and put them into bench_detail.json.  The stdout line is the same compact object either way.")
     ap.add_argument("--no-extra", action="store_true", help="(accepted for the tools/ scripts of earlier rounds: the default run has no post-run legs any more)")
     ap.add_argument("--legs-only", action="store_true", help="(internal) run the post-run legs alone and print their JSON: roofline_mlp, other_configs, "
                     "roofline_ops, reference_harness -- bench.py runs itself with this flag in a child process")
     ap.add_argument("--force-collective", action="store_true", help="issue the gradient all-reduce through RCCL even at world size 1 (one-rank "
-                    "communicator, identity result): the collective path of the N>1 runs, executed on a single GPU; the line then carries `collective`")
+                    "communicator, identity result): the collective path of the N>1 runs, executed on a single GPU; with --full the line then carries `collective`")
     ap.add_argument("--collective-in-graph", action="store_true", help="capture the all-reduce as the last node of the captured step instead of "
                     "issuing it after the replay (diagnostic: the default placement is after the graph)")
+    ap.add_argument("--full", action="store_true", help="besides the headline, measure what it does not need: HIP events around the FPS / "
+                    "ball-query launches of the timed steps (`roofline`), the CPU baseline, the collective's cost at N > 1 (or with "
+                    "--force-collective), and bench_detail.json.  Off by default: a plain run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed as "
+                    "DIR/<name>.npy (float32): a fixed sample of the features, the loss, the gradients, the updated parameters and the "
+                    "batch-norm moving statistics")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if args.detail:
+        args.full = True                  # the post-run legs are part of the full run
 
     global DATA_KIND, SCENES_PER_GPU, NPOINTS
     DATA_KIND = args.data
@@ -223,6 +239,9 @@ def main():
         out = pn2_fea_extractor(xyz, col, 'fea', True, 0.5, geometry=g)
         loss = _DotLoss.apply(out, gout_scaled)       # <out, gout> / numel: one reduction kernel; its gradient IS gout_scaled (no kernel)
         loss.backward(gradient=one)                   # (a given gradient: autograd would otherwise fill a one-element tensor, a 5 us kernel)
+        if args.dump_outputs:
+            # --dump-outputs: keep what this call returns to a caller of the step (in graph mode: the captured tensors, which every replay of slot k rewrites)
+            state.setdefault("outputs", {})[k] = (out.detach(), loss.detach())
         if state["bucket"] is None:
             params = store.parameters()
             state["bucket"] = parallel.FlatGradBucket(params)
@@ -437,7 +456,8 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    if os.environ.get("GSPN_BENCH_NOPROFILE") != "1":      # (diagnostic switch: no per-launch events)
+    # per-launch events for `roofline` (and roofline_ball_query): --full and the internal legs only (diagnostic switch GSPN_BENCH_NOPROFILE=1: none)
+    if (args.full or args.kind_leg) and os.environ.get("GSPN_BENCH_NOPROFILE") != "1":
         tf_sampling.PROFILE_MIN_N = NPOINTS   # (the roofline kernel only: SA level 1)
         PSTEPS = int(os.environ.get("GSPN_BENCH_PROFILE_STEPS", "24"))     # steps of the timed region whose FPS / ball-query launches are bracketed
         tf_sampling.PROFILE_BUDGET[0] = PSTEPS
@@ -517,8 +537,11 @@ def main():
         except Exception:
             traffic = None
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, state, store, (state["i"] - 1) % NB)
+
     coll = None
-    if world > 1 or FORCE_COLL:         # every rank enters (a collective is entered by all ranks or by none); after the timed region
+    if args.full and (world > 1 or FORCE_COLL):         # every rank enters (a collective is entered by all ranks or by none); after the timed region
         coll = collective_leg(state["bucket"], world, FORCE_COLL, "last node of the captured step" if (use_graph and COLL_IN_GRAPH) else
                               "after the graph replay, before the Adam kernel (same stream)")
         # what the collective costs INSIDE the step: the same steps once more without it (a difference run; the replicas' parameters drift
@@ -590,7 +613,7 @@ def main():
                 coll.update(n1_reference(res["value"], world))
             res["collective"] = coll
         _stdout_discipline(rank)                                    # whatever the C side buffered so far comes out BEFORE the line
-        if world == 1 and not args.no_cpu_baseline and not args.kind_leg:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.kind_leg:
             try:
                 res["cpu_baseline"] = cpu_baseline(xyz_np0, col_np0, full=args.detail)
             except Exception as e:                                  # the CPU leg never takes the headline down with it
@@ -613,8 +636,10 @@ def main():
         if args.kind_leg:
             print(json.dumps(res), flush=True)                      # (internal child of data_kinds_legs: the parent reads the full object)
         else:
-            if not LAYERS_ONLY:
+            if args.full and not LAYERS_ONLY:
                 write_detail(res)
+            else:
+                res["detail_file"] = None                           # (a plain run writes no detail file)
             print(json.dumps(compact_line(res)), flush=True)
         _stdout_discipline(rank, done=True)                         # ... and nothing after it
     if dist.is_initialized():
@@ -686,12 +711,35 @@ def compact_line(res):
             c = res.get("collective") if (res.get("n_gpus") or 1) > 1 else None
             out[k] = None if not c else {q: _short(_num(c.get(q)), 120) for q in COLLECTIVE_KEYS}
         elif k == "detail_file":
-            out[k] = DETAIL_FILE
+            out[k] = res.get("detail_file", DETAIL_FILE)
         else:
             out[k] = _short(_num(res.get(k)), 200)
     line = json.dumps(out, allow_nan=False)
     assert len(line) < LINE_LIMIT, "bench line grew to %d bytes" % len(line)
     return out
+
+
+DUMP_POINTS = 4096         # --dump-outputs: features of this many points per scene (a fixed, seeded choice), all 64 channels
+
+
+def dump_outputs(path, state, store, k):
+    """--dump-outputs: what the last timed step (batch slot k) handed back, as float32 .npy files under `path` -- the same arguments give the
+    same inputs (seeded clouds, weights and loss gradient), so two builds can be compared file by file.  features: the extractor's output at
+    DUMP_POINTS seeded points of every scene (8 MiB of the 64 MiB tensor); loss: <out, g> / numel; grads: the flat gradient bucket (summed over
+    ranks); params: the flat parameters after the Adam update; bn_moving_stats: every non-trainable variable (moving mean / variance) in
+    creation order.  Rank 0's view."""
+    torch.cuda.synchronize()
+    out, loss = state["outputs"][k]
+    pts = np.sort(np.random.default_rng(4242).choice(out.shape[1], size=min(DUMP_POINTS, out.shape[1]), replace=False))
+    trainable = set(store.trainable)
+    arrays = {"features": out[:, torch.from_numpy(pts).to(out.device)],
+              "loss": loss.reshape(1),
+              "grads": state["bucket"].flat,
+              "params": state["opt"].flat,
+              "bn_moving_stats": torch.cat([v.detach().reshape(-1) for n, v in store.vars.items() if n not in trainable])}
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().float().cpu().numpy())
 
 
 def write_detail(res):

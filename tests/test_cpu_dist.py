@@ -15,7 +15,14 @@ def _free_port():
     return p
 
 
+def _cpu_rank():
+    """the ranks of this suite are CPU processes (gloo, CPU tensors), also on a box with a GPU: init_from_env must not bind LOCAL_RANK to a
+    device (a one-GPU box has no device 1), so each spawned worker sees no GPU, as on a CPU-only host"""
+    torch.cuda.is_available = lambda: False
+
+
 def _worker(rank, world, port, out):
+    _cpu_rank()
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
     from gspn_amd import parallel
     r, local, w = parallel.init_from_env(backend="gloo")
@@ -56,6 +63,7 @@ def test_gloo_world2_flat_bucket_allreduce():
 def _worker4(rank, world, port, out):
     """world 4, 10 scenes -> unequal shards (3,3,2,2): a scene-weighted mean needs the SUM form with per-scene gradient sums; and the
     optional SyncBN (global-batch statistics) must reproduce a single-process batch norm over the concatenated batch."""
+    _cpu_rank()
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
     from gspn_amd import parallel
     r, local, w = parallel.init_from_env(backend="gloo")
@@ -122,6 +130,7 @@ def test_gloo_world4_unequal_shards_and_sync_bn():
 
 def _worker_forced(rank, world, port, out):
     """world 1 with force=True: the process group exists and the bucket's all-reduce really calls the backend (identity result)"""
+    _cpu_rank()
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
     from gspn_amd import parallel
     r, local, w = parallel.init_from_env(backend="gloo", force=True)
@@ -153,6 +162,7 @@ def test_forced_collective_at_world_1():
 
 
 def _worker_mv(rank, world, port, out):
+    _cpu_rank()
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
     from gspn_amd import parallel
     parallel.init_from_env(backend="gloo")

@@ -60,6 +60,7 @@ SIGNATURES = {
     "gspn_preagg_bwd_dy": [_L, _I, _c.POINTER(DyArgs), _P, _I, _I, _P, _P, _P, _c.POINTER(_I), _P],
     "gspn_threenn": [_I, _I, _I, _P, _P, _P, _P, _P],
     "gspn_threenn_ordered": [_I, _I, _I, _P, _P, _P, _P, _P, _P],
+    "gspn_threenn_nested": [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
     "gspn_threeinterpolate": [_I, _I, _I, _I, _P, _P, _P, _P, _P],
     "gspn_threeinterpolate_grad": [_I, _I, _I, _I, _P, _P, _P, _P, _P],
     "gspn_fp_concat": [_I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P],
@@ -142,7 +143,7 @@ SPECIAL = {
     "gspn_nmdistance_grad_ws_bytes": ([_I, _I, _I], _L),
 }
 
-ABI_VERSION = 9         # == GSPN_ABI_VERSION of include/gspn_hip.h this binding was written against
+ABI_VERSION = 10        # == GSPN_ABI_VERSION of include/gspn_hip.h this binding was written against
 
 _lib = None
 

@@ -109,13 +109,20 @@ def fp_geometry(xyz1, xyz2, scan_order=None):
     """pointnet_util.py:155-160: three nearest sparse points of every dense point and their normalised 1/d weights.
     scan_order: a spatial order of xyz1 (SAGeometry.scan_order of the level that sampled xyz1), see three_nn."""
     dist, idx = three_nn(xyz1.detach(), xyz2.detach(), order=scan_order)
+    return fp_geometry_from_nn(dist, idx, xyz2.shape[1])
+
+
+def fp_geometry_from_nn(dist, idx, m):
+    """fp_geometry's second half: the FPGeometry of a 3-NN result dist / idx (b,n1,3) against m known points -- for 3-NN results that
+    come from elsewhere (three_nn_nested, or rows of another query set's result: spn_trunks.spn_geometry)."""
+    dist, idx = dist.contiguous(), idx.contiguous()
     # :157-160 -- dist = max(dist, 1e-10); norm = sum(1/dist); weight = (1/dist)/norm, in one kernel
     weight = torch.empty_like(dist)
     with torch.cuda.device(dist.device):
         L.check(L.lib().gspn_three_nn_weights(dist.numel() // 3, L.ptr(dist), L.ptr(weight), L.stream()), "three_nn_weights")
     # inverse lists for the gradient (three_interpolate_grad as a gather in the reference's own summation order)
     b, n1, _ = idx.shape
-    order, offsets = inverse_lists(idx.reshape(b, 3 * n1), xyz2.shape[1])
+    order, offsets = inverse_lists(idx.reshape(b, 3 * n1), m)
     return FPGeometry(idx, weight, order, offsets)
 
 

@@ -36,8 +36,9 @@ extern "C" {
  *   4: round 3 (gspn_mlp_bwd_fused, gspn_mlp_bwd_fused_work_bytes).   5: round 3 (gspn_dense_rsum; the fused launch's pooled form).
  *   6: round 3 (gspn_fps_cells_prepass_order, gspn_bn_colsum / gspn_bn_apply_grad of tf_util's stand-alone batch norm).
  *   8: round 4 (gspn_pool32_select_groups).
- *   7: round 4 (gspn_nmdistance_grad_csr, gspn_bn_finalize_parts_pivot, gspn_mlp_bwd_fused_coef, gspn_dot, gspn_queryballpoint_ws; gspn_queryballpoint now launches a prefix scan + a continuation kernel -- same output). */
-#define GSPN_ABI_VERSION 9
+ *   7: round 4 (gspn_nmdistance_grad_csr, gspn_bn_finalize_parts_pivot, gspn_mlp_bwd_fused_coef, gspn_dot, gspn_queryballpoint_ws; gspn_queryballpoint now launches a prefix scan + a continuation kernel -- same output).
+ *   9: round 6 (the *_ws drop-in gradient launchers, gspn_fp_concat_grad_csr_split).   10: gspn_threenn_nested. */
+#define GSPN_ABI_VERSION 10
 int gspn_dist_policy(void);
 int gspn_abi_version(void);
 
@@ -149,6 +150,13 @@ int gspn_threenn(int b, int n, int m, const float* xyz1, const float* xyz2, floa
  * coherent one makes the exact re-evaluations of a wave coincide (8 x 32768 <- 2048: 171 us in the given order, 108 us in the FPS
  * pre-pass order, 81 us in an 8^3 voxel order). */
 int gspn_threenn_ordered(int b, int n, int m, const float* xyz1, const float* xyz2, const int* order, float* dist, int* idx, void* stream);
+/* three_nn of one query set against L <= 8 subsets of one known cloud in a single scan (ABI 10; gspn_amd/csrc/threenn_nested.hip):
+ *   xyz1 (b,n,3), xyz2 (b,m,3), local (L,b,m) i32: the index of known point k inside level l, or -1 if k is not in that level;
+ *   order (b,n) i32 or NULL as in gspn_threenn_ordered;  dist (L,b,n,3) f32, idx (L,b,n,3) i32 in each level's own indexing.
+ * For every level bit-identical to gspn_threenn(b, n, m_l, xyz1, <the points of level l in local order>, ...), ties included.
+ * GSPN_ERR_ARG for L < 1 or negative sizes, GSPN_ERR_UNSUPPORTED for L > 8 or sizes whose grid / row counts overflow an int. */
+int gspn_threenn_nested(int b, int n, int m, int L, const float* xyz1, const float* xyz2, const int* local, const int* order, float* dist, int* idx,
+                        void* stream);
 /* threeinterpolate_cpu(b,m,c,n,points,idx,weight,out)  tf_interpolate.cpp:107-127 */
 int gspn_threeinterpolate(int b, int m, int c, int n, const float* points, const int* idx, const float* weight, float* out, void* stream);
 /* threeinterpolate_grad_cpu(b,n,c,m,grad_out,idx,weight,grad_points)  tf_interpolate.cpp:131-153;

@@ -118,6 +118,9 @@ SIGNATURES = {
     "gspn_adam_flat_dev": [_L, _P, _P, _P, _P, _F, _F, _F, _F, _F, _F, _P, _P],
     "gspn_dot": [_L, _P, _P, _P, _P, _P],
     "gspn_fill_zero": [_P, _L, _P],
+    "gspn_deconv_fwd": [_I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
+    "gspn_deconv_bwd_input": [_I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
+    "gspn_deconv_bwd_kernel": [_I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
 }
 
 # entry points that do not return an int status: symbol -> (argtypes, restype)
@@ -141,9 +144,10 @@ SPECIAL = {
     "gspn_scatteraddpoint_ws_bytes": ([_I, _I, _I], _L),
     "gspn_threeinterpolate_grad_ws_bytes": ([_I, _I, _I, _I], _L),
     "gspn_nmdistance_grad_ws_bytes": ([_I, _I, _I], _L),
+    "gspn_deconv_bwd_kernel_work_bytes": ([_I, _I, _I, _I, _I, _I, _I, _I, _I], _L),
 }
 
-ABI_VERSION = 10        # == GSPN_ABI_VERSION of include/gspn_hip.h this binding was written against
+ABI_VERSION = 11        # == GSPN_ABI_VERSION of include/gspn_hip.h this binding was written against
 
 _lib = None
 

@@ -122,6 +122,9 @@ def weight_decay_loss():
 
 
 # --------------------------------------------------------------------------- layers
+_MLP_MAX_CHANNELS = 1024        # GSPN_MLP_MAX_CHANNELS of include/gspn_hip.h: the widest layer one gspn_mlp_fwd launch takes
+
+
 def _bn_variables(c):
     """tf.contrib.layers.batch_norm(center=True, scale=True) variables under scope 'bn' (tf_util.py:529-534)."""
     beta = get_variable("beta", (c,), constant_initializer(0.0))
@@ -157,6 +160,34 @@ def conv2d(inputs, num_output_channels, kernel_size, scope, stride=[1, 1], paddi
     return out.view(*inputs.shape[:-1], num_output_channels)
 
 
+def conv2d_transpose(inputs, num_output_channels, kernel_size, scope, stride=[1, 1], padding='SAME', data_format='NHWC',
+                     use_xavier=True, stddev=1e-3, weight_decay=None, activation_fn=torch.relu, bn=False, bn_decay=None, is_training=None):
+    """tf_util.py:188-267 for padding='VALID', NHWC (the decoder's calls, model_rpointnet.py:286-301).
+    inputs: (B,H,W,C) -> (B, H*sh + max(kh-sh,0), W*sw + max(kw-sw,0), num_output_channels).
+    Variables in the reference's creation order: <scope>/weights (kh,kw,Cout,Cin) -- created and never used, the only one weight_decay
+    applies to --, then tf.layers.conv2d_transpose's <scope>/conv2d_transpose/kernel (Glorot uniform, (kh,kw,Cout,Cin)) and .../bias
+    (zeros), then <scope>/bn/... .  The arithmetic runs on the HIP kernels of csrc/deconv.hip, the batch norm on _BatchNormRows."""
+    from .deconv import conv2d_transpose_valid
+    if padding != 'VALID' or data_format != 'NHWC':
+        raise NotImplementedError("gspn_amd.tf_util.conv2d_transpose implements padding='VALID', NHWC (the decoder's calls)")
+    if activation_fn is not None and activation_fn is not torch.relu and activation_fn is not torch.nn.functional.relu:
+        raise NotImplementedError("activation_fn must be relu or None")
+    kh, kw = kernel_size
+    inputs = L.need(inputs, torch.float32, 4, "inputs")
+    cin = inputs.shape[-1]
+    with variable_scope(scope):
+        _variable_with_weight_decay("weights", shape=[kh, kw, num_output_channels, cin], use_xavier=use_xavier, stddev=stddev, wd=weight_decay)
+        with variable_scope("conv2d_transpose"):
+            kernel = get_variable("kernel", (kh, kw, num_output_channels, cin), xavier_initializer())
+            bias = get_variable("bias", (num_output_channels,), constant_initializer(0.0))
+        outputs = conv2d_transpose_valid(inputs, kernel, bias, stride)
+        if bn:
+            outputs = batch_norm_for_conv2d(outputs, is_training, bn_decay=bn_decay, scope="bn", data_format=data_format)
+    if activation_fn is not None:
+        outputs = torch.relu(outputs)
+    return outputs
+
+
 def conv1d(inputs, num_output_channels, kernel_size, scope, stride=1, padding='SAME', data_format='NHWC',
            use_xavier=True, stddev=1e-3, weight_decay=None, activation_fn=torch.relu, bn=False, bn_decay=None, is_training=None):
     """tf_util.py:52-115 for kernel_size 1.  inputs: (B,L,C)."""
@@ -182,7 +213,14 @@ def _apply_layer(x2d, cin, lp, activation_fn, is_training, bn_decay):
     if activation_fn is torch.relu or activation_fn is torch.nn.functional.relu:
         return mlp_stack(x2d, cin, [lp], is_training, bn_decay, None)
     if activation_fn is None and not lp.bn:
-        return mlp_linear(x2d, cin, lp)           # plain linear head (model_rpointnet.py:71-73, 262-263)
+        cout = lp.weights.shape[1]
+        if cout <= _MLP_MAX_CHANNELS:
+            return mlp_linear(x2d, cin, lp)           # plain linear head (model_rpointnet.py:71-73, 262-263)
+        # wider than one MLP launch takes (decoding_net's de_fc4, model_rpointnet.py:307: up to 3*1024 outputs): column blocks of the same
+        # variables, concatenated
+        return torch.cat([mlp_linear(x2d, cin, LayerParams(lp.weights[:, a:a + _MLP_MAX_CHANNELS].contiguous(),
+                                                           lp.biases[a:a + _MLP_MAX_CHANNELS].contiguous(), False))
+                          for a in range(0, cout, _MLP_MAX_CHANNELS)], dim=1)
     raise NotImplementedError("activation_fn must be relu, or None without batch-norm (the cases the set-abstraction path and its heads use)")
 
 

@@ -37,8 +37,9 @@ extern "C" {
  *   6: round 3 (gspn_fps_cells_prepass_order, gspn_bn_colsum / gspn_bn_apply_grad of tf_util's stand-alone batch norm).
  *   8: round 4 (gspn_pool32_select_groups).
  *   7: round 4 (gspn_nmdistance_grad_csr, gspn_bn_finalize_parts_pivot, gspn_mlp_bwd_fused_coef, gspn_dot, gspn_queryballpoint_ws; gspn_queryballpoint now launches a prefix scan + a continuation kernel -- same output).
- *   9: round 6 (the *_ws drop-in gradient launchers, gspn_fp_concat_grad_csr_split).   10: gspn_threenn_nested. */
-#define GSPN_ABI_VERSION 10
+ *   9: round 6 (the *_ws drop-in gradient launchers, gspn_fp_concat_grad_csr_split).   10: gspn_threenn_nested.
+ *  11: gspn_deconv_fwd / gspn_deconv_bwd_input / gspn_deconv_bwd_kernel (+ _work_bytes). */
+#define GSPN_ABI_VERSION 11
 int gspn_dist_policy(void);
 int gspn_abi_version(void);
 
@@ -222,6 +223,26 @@ int gspn_threeinterpolate_grad_ws(int b, int n, int c, int m, const float* grad_
 long gspn_nmdistance_grad_ws_bytes(int b, int n, int m);
 int gspn_nmdistance_grad_ws(int b, int n, const float* xyz1, int m, const float* xyz2, const float* grad_dist1, const int* idx1, const float* grad_dist2,
                             const int* idx2, float* grad_xyz1, float* grad_xyz2, void* ws, void* stream);
+
+/* ---------------- utils/tf_util.py conv2d_transpose (tf.layers.conv2d_transpose, VALID, NHWC) -------------------------------
+ * The reference's decoder (model_rpointnet.py:274-322) upsamples with tf_util.conv2d_transpose (tf_util.py:188-267), which runs
+ * tf.layers.conv2d_transpose; TensorFlow supplies its arithmetic.  Here (gspn_amd/csrc/deconv.hip) it is three implicit GEMMs on the FP32
+ * MFMA, with no im2col buffer:
+ *   Ho = hi*sh + max(kh - sh, 0)   (wo alike)
+ *   Y[n, oy, ox, co] = bias[co] + sum over (iy, ix, ky, kx) with iy*sh + ky == oy and ix*sw + kx == ox of X[n, iy, ix, ci] * K[ky, kx, co, ci]
+ * X (n, hi, wi, cin), K (kh, kw, cout, cin) -- no kernel flip --, bias (cout) or NULL, Y (n, Ho, Wo, cout).  Output pixels that no tap
+ * reaches (k < s) hold bias only.  Any sizes >= 1 (GSPN_ERR_ARG below that; GSPN_ERR_UNSUPPORTED when n*Ho*Wo or kh*kw*cin*cout exceeds
+ * 2^30, or sh*sw / kh*kw exceeds 65535).  No atomics: every sum has a fixed order, two identical calls give identical bits. */
+int gspn_deconv_fwd(int n, int hi, int wi, int cin, int cout, int kh, int kw, int sh, int sw, const float* X, const float* K,
+                    const float* bias, float* Y, void* stream);
+/* dX (n, hi, wi, cin) = the gradient of Y with respect to X for the upstream gradient dY (n, Ho, Wo, cout); dX is overwritten. */
+int gspn_deconv_bwd_input(int n, int hi, int wi, int cin, int cout, int kh, int kw, int sh, int sw, const float* dY, const float* K,
+                          float* dX, void* stream);
+/* dK (kh, kw, cout, cin) and dbias (cout), both overwritten; either may be NULL (not both).  ws: gspn_deconv_bwd_kernel_work_bytes(...)
+ * bytes of scratch (a function of the shape alone; 0 for arguments the launcher rejects) for the split reduction's partial tiles. */
+long gspn_deconv_bwd_kernel_work_bytes(int n, int hi, int wi, int cin, int cout, int kh, int kw, int sh, int sw);
+int gspn_deconv_bwd_kernel(int n, int hi, int wi, int cin, int cout, int kh, int kw, int sh, int sw, const float* dY, const float* X,
+                           float* dK, float* dbias, void* ws, void* stream);
 
 /* ---------------- utils/pointnet_util.py composition helpers --------------------------- */
 

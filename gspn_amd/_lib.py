@@ -121,6 +121,9 @@ SIGNATURES = {
     "gspn_deconv_fwd": [_I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     "gspn_deconv_bwd_input": [_I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
     "gspn_deconv_bwd_kernel": [_I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
+    "gspn_box_shrink": [_I, _I, _I, _P, _P, _P, _P],
+    "gspn_points_bbox": [_I, _I, _P, _P, _P, _P],
+    "gspn_spn_target_gen": [_I, _I, _I, _P, _P, _P, _P, _P, _P],
 }
 
 # entry points that do not return an int status: symbol -> (argtypes, restype)
@@ -147,7 +150,7 @@ SPECIAL = {
     "gspn_deconv_bwd_kernel_work_bytes": ([_I, _I, _I, _I, _I, _I, _I, _I, _I], _L),
 }
 
-ABI_VERSION = 11        # == GSPN_ABI_VERSION of include/gspn_hip.h this binding was written against
+ABI_VERSION = 12        # == GSPN_ABI_VERSION of include/gspn_hip.h this binding was written against
 
 _lib = None
 

@@ -1,5 +1,6 @@
 """Synthetic point clouds of SURVEY.md section 8(d): U (uniform), D (duplicates: tie stress, mirrors
-dataset.py:100-105), S (room-like surfaces).  numpy.random.default_rng(seed), float32."""
+dataset.py:100-105), S (room-like surfaces), and spn_batch: a labelled scene batch for the shape proposal stage.
+numpy.random.default_rng(seed), float32."""
 import numpy as np
 
 
@@ -40,3 +41,45 @@ def cloud_s(n, seed):
 def batch(kind, b, n, seed0=0):
     f = {"U": cloud_u, "D": cloud_d, "S": cloud_s}[kind]
     return np.stack([f(n, seed0 + i) for i in range(b)]).astype(np.float32)
+
+
+def spn_batch(kind, b, n, ngroup, nsmp_ins, ncat, seed0=0, invalid=(), stray=0.0):
+    """Inputs of rpointnet() (models/model_rpointnet.py:1051) on synthetic clouds: a dict of
+      pc, color (b,n,3) f32; group_label (b,n) i64 -- the nearest of one seeded centre per group not listed in `invalid`, a fraction
+      `stray` of the points labelled with an invalid group instead (the reference allows it: such a seed gets a zero instance feature);
+      group_indicator (b,ngroup) f32 (0 for the invalid groups); seg_label (b,n) i64 -- one category in [0, ncat) per group, about a quarter
+      of the groups background (0); pc_ins (b,ngroup,nsmp_ins,3) f32 -- nsmp_ins points of each valid group drawn with replacement, zeros
+      for the others; bbox_ins (b,ngroup,6) f32 -- (centre, size) of pc_ins, zeros for the others; smpw (b,n) f32 with about 30 % zeros."""
+    out = {k: [] for k in ("pc", "color", "group_label", "group_indicator", "seg_label", "pc_ins", "bbox_ins", "smpw")}
+    f = {"U": cloud_u, "D": cloud_d, "S": cloud_s}[kind]
+    valid = np.array([g for g in range(ngroup) if g not in set(invalid)])
+    bad = np.array(sorted(set(invalid)), dtype=np.int64)
+    for i in range(b):
+        rng = np.random.default_rng(1000003 * (seed0 + i) + 17)
+        pc = f(n, seed0 + i)
+        centres = pc[rng.choice(n, size=min(len(valid), n), replace=False)]
+        label = valid[((pc[:, None, :] - centres[None, :, :]) ** 2).sum(-1).argmin(1)]
+        if len(bad) and stray > 0:
+            s = rng.random(n) < stray
+            label[s] = bad[rng.integers(0, len(bad), size=int(s.sum()))]
+        cat = rng.integers(1, ncat, size=ngroup) * (rng.random(ngroup) >= 0.25)
+        ins = np.zeros((ngroup, nsmp_ins, 3), np.float32)
+        box = np.zeros((ngroup, 6), np.float32)
+        for g in valid:
+            members = np.nonzero(label == g)[0]
+            if len(members) == 0:
+                members = np.array([0])
+            ins[g] = pc[members[rng.integers(0, len(members), size=nsmp_ins)]]
+            hi, lo = ins[g].max(0), ins[g].min(0)
+            box[g] = np.concatenate([(hi + lo) / 2, hi - lo])
+        ind = np.ones(ngroup, np.float32)
+        ind[bad] = 0.0
+        out["pc"].append(pc)
+        out["color"].append(rng.random((n, 3), dtype=np.float32))
+        out["group_label"].append(label.astype(np.int64))
+        out["group_indicator"].append(ind)
+        out["seg_label"].append(cat[label].astype(np.int64))
+        out["pc_ins"].append(ins)
+        out["bbox_ins"].append(box)
+        out["smpw"].append((rng.random(n, dtype=np.float32) * (rng.random(n) >= 0.3)).astype(np.float32))
+    return {k: np.stack(v) for k, v in out.items()}

@@ -209,8 +209,29 @@ def fully_connected(inputs, num_outputs, scope, use_xavier=True, stddev=1e-3, we
     return _apply_layer(inputs, cin, lp, activation_fn, bool(is_training) if is_training is not None else False, bn_decay)
 
 
+def _apply_wide_input_layer(x2d, cin, lp, relu, is_training, bn_decay):
+    """A layer with more input channels than one MLP launch takes (shape_proposal_net's mu_sigma_x/conv0, model_rpointnet.py:385:
+    128 + 768 + 256 = 1152 inputs): row blocks of the same weights on column blocks of the input, added in order, then the stand-alone
+    batch norm and ReLU.  Same variables, same arithmetic up to the order of the sum over input channels."""
+    if lp.weights.shape[1] > _MLP_MAX_CHANNELS:
+        raise NotImplementedError("a layer with more than %d input AND output channels" % _MLP_MAX_CHANNELS)
+    y = None
+    for a in range(0, cin, _MLP_MAX_CHANNELS):
+        w = lp.weights[a:a + _MLP_MAX_CHANNELS]
+        bias = lp.biases if a == 0 else torch.zeros_like(lp.biases)
+        part = mlp_linear(x2d[:, a:a + w.shape[0]].contiguous(), w.shape[0], LayerParams(w, bias, False))
+        y = part if y is None else y + part
+    if lp.bn:
+        y = _BatchNormRows.apply(y, lp.gamma, lp.beta, lp.moving_mean, lp.moving_variance, bool(is_training),
+                                 0.9 if bn_decay is None else float(bn_decay))
+    return torch.relu(y) if relu else y
+
+
 def _apply_layer(x2d, cin, lp, activation_fn, is_training, bn_decay):
-    if activation_fn is torch.relu or activation_fn is torch.nn.functional.relu:
+    relu = activation_fn is torch.relu or activation_fn is torch.nn.functional.relu
+    if cin > _MLP_MAX_CHANNELS and (relu or (activation_fn is None and not lp.bn)):
+        return _apply_wide_input_layer(x2d, cin, lp, relu, is_training, bn_decay)
+    if relu:
         return mlp_stack(x2d, cin, [lp], is_training, bn_decay, None)
     if activation_fn is None and not lp.bn:
         cout = lp.weights.shape[1]

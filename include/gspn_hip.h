@@ -38,8 +38,9 @@ extern "C" {
  *   8: round 4 (gspn_pool32_select_groups).
  *   7: round 4 (gspn_nmdistance_grad_csr, gspn_bn_finalize_parts_pivot, gspn_mlp_bwd_fused_coef, gspn_dot, gspn_queryballpoint_ws; gspn_queryballpoint now launches a prefix scan + a continuation kernel -- same output).
  *   9: round 6 (the *_ws drop-in gradient launchers, gspn_fp_concat_grad_csr_split).   10: gspn_threenn_nested.
- *  11: gspn_deconv_fwd / gspn_deconv_bwd_input / gspn_deconv_bwd_kernel (+ _work_bytes). */
-#define GSPN_ABI_VERSION 11
+ *  11: gspn_deconv_fwd / gspn_deconv_bwd_input / gspn_deconv_bwd_kernel (+ _work_bytes).
+ *  12: gspn_box_shrink / gspn_points_bbox / gspn_spn_target_gen. */
+#define GSPN_ABI_VERSION 12
 int gspn_dist_policy(void);
 int gspn_abi_version(void);
 
@@ -243,6 +244,28 @@ int gspn_deconv_bwd_input(int n, int hi, int wi, int cin, int cout, int kh, int 
 long gspn_deconv_bwd_kernel_work_bytes(int n, int hi, int wi, int cin, int cout, int kh, int kw, int sh, int sw);
 int gspn_deconv_bwd_kernel(int n, int hi, int wi, int cin, int cout, int kh, int kw, int sh, int sw, const float* dY, const float* X,
                            float* dK, float* dbias, void* ws, void* stream);
+
+/* ---------------- models/model_rpointnet.py box arithmetic of the shape proposal stage (gspn_amd/csrc/spn_boxes.hip) -------
+ * Boxes are (centre x, y, z, size l, w, h).  fp32, no atomics, no workspace; every expression is evaluated as written (no contraction). */
+
+/* box_shrink (:529-551).  box (b,s,6), pc (b,n,3) -> out (b,s,6).  A point is inside a box when pc >= c - size/2 and pc <= c + size/2 on
+ * all three axes.  With hi / lo the per-axis max / min over the inside points: out = [(hi + lo)/2, hi - lo + 1e-3] if hi - lo > 0 on all
+ * three axes, else six zeros (no point inside, or the inside points flat on an axis).  Equal to the reference's gamma = 1e4 formulation
+ * while |coordinate| < 5e3. */
+int gspn_box_shrink(int b, int s, int n, const float* box, const float* pc, float* out, void* stream);
+
+/* Per-row bounding box: out[r] = [(hi + lo)/2, hi - lo], hi / lo the max / min over the m points of pts[r] + offset[r].
+ * pts (rows,m,3), offset (rows,3) or NULL, out (rows,6).  bbox_ins_pred (:406-408, offset = the seed) and pc_ins_center (:358). */
+int gspn_points_bbox(int rows, int m, const float* pts, const float* offset, float* out, void* stream);
+
+/* spn_target_gen (:599-644) for a whole batch, one workgroup per scene.  proposals (b,s,6), seed_cls (b,s) f32 (1 = foreground seed),
+ * gt_cls (b,g) f32 (rows with gt_cls <= 0 are padding and skipped in place), gt_boxes (b,g,6) -> spn_match (b,s) i32:
+ *   +1  largest IoU >= 0.5 and foreground seed, or the foreground-seed proposal of largest IoU (> 0; ties: lowest index) of a valid box
+ *   -1  largest IoU < 0.5 and not positive (every proposal of a scene without a valid box)
+ *    0  otherwise.
+ * IoU = intersection / (vol_a + vol_b - intersection + 1e-8). */
+int gspn_spn_target_gen(int b, int s, int g, const float* proposals, const float* seed_cls, const float* gt_cls, const float* gt_boxes,
+                        int* spn_match, void* stream);
 
 /* ---------------- utils/pointnet_util.py composition helpers --------------------------- */
 

@@ -1,13 +1,17 @@
-"""Times shape_proposal_net's two trunks (gspn_amd/spn_trunks.py) on one GPU.
+"""Times shape_proposal_net's two trunks (gspn_amd/spn_trunks.py) and the whole SPN training step (gspn_amd/rpointnet.py) on one GPU.
 
   step      one training step of shift_pred_net + sem_net (forward + backward), (a) each trunk building its own geometry inline, as
             code written against the reference's modules does, and (b) with one spn_geometry shared by both (computed inside the step)
   full_fwd  the full-feature forward (return_fullfea=True, eval, mode='inference') with the dense 3-NN of spn_geometry by one three_nn per
             level vs one three_nn_nested scan
   nn        the dense 3-NN alone: three_nn onto l1, l2, l3, l4 (four launches) vs three_nn_nested (one launch)
+  spn       one full SPN training step -- rpointnet + get_loss + backward, eager, geometry computed inside the step -- at the reference's
+            configuration (256 seeds, 100 groups of 512 points, 19 categories, SHRINK_BOX on), and box_shrink on its HIP kernel against the
+            reference's broadcast formulation written in torch, alternating in one process, at 256 and 2048 boxes per scene
 
 Prints one JSON line per (shape, measurement): median / min milliseconds over --iters timed runs after --warmup runs.
     python tools/spn_step.py --shapes 2x18000,8x32768
+    python tools/spn_step.py --shapes 2x18000 --measures spn
 """
 import argparse
 import json
@@ -45,8 +49,80 @@ def trunks(xyz, col, ns, nm, ncat, training, full, mode, geo):
     return S.sem_net(xyz, col, nm, ncat, ep['ind_seed'], ep, 'sem_predictor', training, 0.5, return_fullfea=full, mode=mode, geometry=geo)
 
 
+def box_shrink_torch(box, pc):
+    """box_shrink as models/model_rpointnet.py:529-551 writes it: boxes broadcast against points, (B, S, N, 3) temporaries"""
+    pc_aug, box_aug = pc.unsqueeze(1), box.unsqueeze(2)
+    masks = (pc_aug >= box_aug[..., :3] - box_aug[..., 3:] / 2) & (pc_aug <= box_aug[..., :3] + box_aug[..., 3:] / 2)
+    out = 1 - (masks[..., 0] & masks[..., 1] & masks[..., 2]).float().unsqueeze(-1)
+    gamma = 1e4
+    box_max, box_min = (pc_aug - gamma * out).amax(2), (pc_aug + gamma * out).amin(2)
+    keep = (box_max - box_min > 0).all(-1, keepdim=True).float()
+    return torch.cat(((box_max + box_min) / 2, box_max - box_min + 1e-3), 2) * keep
+
+
+def timed_alternating(fns, warmup, iters):
+    """median / min of each of several callables, run in turn (a, b, a, b, ...) so that clocks and neighbours hit them alike"""
+    for _ in range(warmup):
+        for fn in fns.values():
+            fn()
+    torch.cuda.synchronize()
+    ts = {k: [] for k in fns}
+    for _ in range(iters):
+        for k, fn in fns.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            ts[k].append(a.elapsed_time(b))
+    return {k: {"median_ms": round(sorted(v)[len(v) // 2], 4), "min_ms": round(min(v), 4)} for k, v in ts.items()}
+
+
+def measure_spn(a, shape, b, n, dev):
+    from gspn_amd import rpointnet as RP
+    from gspn_amd.spn_boxes import box_shrink
+    cfg = RP.Config()
+    cfg.BATCH_SIZE, cfg.NUM_POINT, cfg.SHRINK_BOX = b, n, True
+    sc = {k: torch.from_numpy(v).to(dev) for k, v in
+          synth.spn_batch(a.kind, b, n, cfg.NUM_GROUP, cfg.NUM_POINT_INS, cfg.NUM_CATEGORY, seed0=7).items()}
+    store = tf_util.set_variable_store(tf_util.VariableStore(device=dev, seed=1))
+
+    def step():
+        for p in store.parameters():
+            p.grad = None
+        ep = RP.rpointnet(sc["pc"], sc["color"], sc["pc_ins"], sc["group_label"], sc["group_indicator"], sc["seg_label"], sc["bbox_ins"], cfg,
+                          True, bn_decay=0.5)
+        loss, _ = RP.get_loss(ep, cfg, 1.0, sc["smpw"])
+        loss.backward()
+
+    res = timed(step, a.warmup, a.iters)
+    # get_loss alone (forward + gradients with respect to the network's outputs) on the detached end_points of one forward pass
+    ep = RP.rpointnet(sc["pc"], sc["color"], sc["pc_ins"], sc["group_label"], sc["group_indicator"], sc["seg_label"], sc["bbox_ins"], cfg, True,
+                      bn_decay=0.5)
+    ep = {k: v.detach() for k, v in ep.items()}
+    outs = ('fb_logits', 'pc_ins_pred', 'shift_pred_seed_4d', 'sem_class_logits', 'mean', 'log_var', 'cmean', 'clog_var')
+    for k in outs:
+        ep[k].requires_grad_(True)
+
+    def loss_only():
+        loss, _ = RP.get_loss(dict(ep), cfg, 1.0, sc["smpw"])
+        torch.autograd.grad(loss, [ep[k] for k in outs])
+
+    print(json.dumps({"shape": shape, "kind": a.kind, "measure": "spn", "seeds": cfg.NUM_SAMPLE, "groups": cfg.NUM_GROUP,
+                      "points_per_instance": cfg.NUM_POINT_INS, "step": res, "get_loss_fwd_bwd": timed(loss_only, a.warmup, a.iters)}), flush=True)
+    for s in (256, 2048):
+        g = torch.Generator().manual_seed(s)
+        ext = sc["pc"].amax((0, 1)).cpu()
+        box = torch.cat((torch.rand(b, s, 3, generator=g) * ext, torch.rand(b, s, 3, generator=g) * 1.5 + 0.05), -1).to(dev)
+        same = bool(torch.equal(box_shrink(box, sc["pc"]), box_shrink_torch(box, sc["pc"])))
+        res = timed_alternating({"hip": lambda: box_shrink(box, sc["pc"]), "torch_broadcast": lambda: box_shrink_torch(box, sc["pc"])},
+                                a.warmup, a.iters)
+        print(json.dumps({"shape": "%dx%dx%d" % (b, s, n), "kind": a.kind, "measure": "box_shrink", "equal": same, **res}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--measures", default="step,full_fwd,nn,spn")
     ap.add_argument("--shapes", default="2x18000,8x32768")
     ap.add_argument("--kind", default="S")
     ap.add_argument("--seed-points", type=int, default=128)          # shape_proposal_net's nsmp
@@ -57,8 +133,13 @@ def main():
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     ns, nm, ncat = a.seed_points, a.sem_points, a.categories
+    measures = a.measures.split(",")
     for shape in a.shapes.split(","):
         b, n = (int(v) for v in shape.split("x"))
+        if "spn" in measures:
+            measure_spn(a, shape, b, n, dev)
+        if not set(measures) & {"step", "full_fwd", "nn"}:
+            continue
         xyz = torch.from_numpy(synth.batch(a.kind, b, n)).to(dev)
         col = torch.rand(b, n, 3, device=dev)
         tf_util.set_variable_store(tf_util.VariableStore(device=dev, seed=1))
@@ -75,8 +156,9 @@ def main():
 
         step(False)()
         params[:] = tf_util.get_variable_store().parameters()
-        res = {"inline_geometry": timed(step(False), a.warmup, a.iters), "shared_geometry": timed(step(True), a.warmup, a.iters)}
-        print(json.dumps({"shape": shape, "kind": a.kind, "measure": "step", **res}), flush=True)
+        if "step" in measures:
+            res = {"inline_geometry": timed(step(False), a.warmup, a.iters), "shared_geometry": timed(step(True), a.warmup, a.iters)}
+            print(json.dumps({"shape": shape, "kind": a.kind, "measure": "step", **res}), flush=True)
 
         def full(nested):
             def run():
@@ -84,8 +166,11 @@ def main():
                     trunks(xyz, col, ns, nm, ncat, False, True, 'inference', S.spn_geometry(xyz, ns, nm, True, points=col, nested=nested))
             return run
 
-        res = {"per_level_three_nn": timed(full(False), a.warmup, a.iters), "three_nn_nested": timed(full(True), a.warmup, a.iters)}
-        print(json.dumps({"shape": shape, "kind": a.kind, "measure": "full_fwd", **res}), flush=True)
+        if "full_fwd" in measures:
+            res = {"per_level_three_nn": timed(full(False), a.warmup, a.iters), "three_nn_nested": timed(full(True), a.warmup, a.iters)}
+            print(json.dumps({"shape": shape, "kind": a.kind, "measure": "full_fwd", **res}), flush=True)
+        if "nn" not in measures:
+            continue
 
         # the dense 3-NN alone, on the geometry spn_geometry builds
         fps, order, cur, lv = [], None, xyz, []

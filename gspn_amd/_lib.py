@@ -124,6 +124,11 @@ SIGNATURES = {
     "gspn_box_shrink": [_I, _I, _I, _P, _P, _P, _P],
     "gspn_points_bbox": [_I, _I, _P, _P, _P, _P],
     "gspn_spn_target_gen": [_I, _I, _I, _P, _P, _P, _P, _P, _P],
+    "gspn_nms3d": [_I, _I, _I, _I, _F, _F, _P, _P, _P, _P],
+    "gspn_box_point_count": [_I, _I, _I, _F, _P, _P, _P, _P],
+    "gspn_sample_points_in_boxes": [_I, _I, _I, _I, _F, _P, _P, _P, _P, _P],
+    "gspn_detection_target_select": [_I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P],
+    "gspn_crop_gather_grad": [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
 }
 
 # entry points that do not return an int status: symbol -> (argtypes, restype)
@@ -148,9 +153,10 @@ SPECIAL = {
     "gspn_threeinterpolate_grad_ws_bytes": ([_I, _I, _I, _I], _L),
     "gspn_nmdistance_grad_ws_bytes": ([_I, _I, _I], _L),
     "gspn_deconv_bwd_kernel_work_bytes": ([_I, _I, _I, _I, _I, _I, _I, _I, _I], _L),
+    "gspn_crop_gather_grad_part_floats": ([_I, _I, _I], _L),
 }
 
-ABI_VERSION = 12        # == GSPN_ABI_VERSION of include/gspn_hip.h this binding was written against
+ABI_VERSION = 13        # == GSPN_ABI_VERSION of include/gspn_hip.h this binding was written against
 
 _lib = None
 

@@ -3,17 +3,22 @@ SPN terms of get_loss (:1325), with the helpers they use (box_shrink :529, spn_t
 :1223, get_spn_class_loss :1232).  Same names, argument order and end_points keys as the reference.
 
 Every shape here is static and nothing reads a value back to the host, so with the geometry, the valid-instance index and the noise
-prepared outside, rpointnet + get_loss + backward capture in a graph.CapturedStep.  What needs the detection heads (NMS, detection
-targets, cropping, classification_head, segmentation_head, their losses, inference) is not implemented and raises NotImplementedError."""
+prepared outside, rpointnet + get_loss + backward capture in a graph.CapturedStep.  The ROI stage behind it -- nms_3d (:436),
+detection_target_gen (:647), mask_selection_gen (:749), points_cropping (:785), box_refinement (:553), apply_box_delta (:570) -- lives in
+roi.py and is re-exported here under the reference's names.  What needs the detection heads (the FPN layers, classification_head,
+segmentation_head, their losses, refine_detections, inference) is not implemented and raises NotImplementedError."""
 import torch
 
 from . import _lib as L
 from .proposal_head import chamfer_recons_loss
+from .roi import (apply_box_delta, box_point_count, box_refinement, detection_target_gen, detection_target_gen_batch, mask_selection_gen,
+                  mask_selection_gen_batch, nms_3d, points_cropping, sample_points_in_boxes)
 from .shape_proposal import shape_proposal_net
 from .spn_boxes import box_shrink, points_bbox, spn_target_gen_batch
 
 __all__ = ["Config", "box_shrink", "spn_target_gen", "spn_target_gen_batch", "gather_selection", "smooth_l1_loss", "get_spn_class_loss",
-           "seg_label_per_group", "rpointnet", "get_loss"]
+           "seg_label_per_group", "rpointnet", "get_loss", "nms_3d", "box_point_count", "sample_points_in_boxes", "detection_target_gen",
+           "detection_target_gen_batch", "mask_selection_gen", "mask_selection_gen_batch", "points_cropping", "box_refinement", "apply_box_delta"]
 
 
 class Config(object):
@@ -103,11 +108,11 @@ def rpointnet(pc, color, pc_ins, group_label, group_indicator, seg_label, bbox_i
     geometry / noise / valid_idx (extensions) are handed on to shape_proposal_net."""
     assert mode in ['training', 'inference']
     if mode == 'inference':
-        raise NotImplementedError("rpointnet: mode='inference' needs nms_3d, mask_selection_gen, points_cropping, classification_head, "
-                                  "segmentation_head and refine_detections, which are not implemented")
+        raise NotImplementedError("rpointnet: mode='inference' needs the FPN layers, classification_head, segmentation_head and "
+                                  "refine_detections, which are not implemented")
     if 'RPOINTNET' in config.TRAIN_MODULE:
-        raise NotImplementedError("rpointnet: 'RPOINTNET' in TRAIN_MODULE needs nms_3d, detection_target_gen, points_cropping, "
-                                  "classification_head and segmentation_head, which are not implemented")
+        raise NotImplementedError("rpointnet: 'RPOINTNET' in TRAIN_MODULE needs the FPN layers, classification_head and segmentation_head, "
+                                  "which are not implemented")
     if 'SPN' not in config.TRAIN_MODULE:
         raise NotImplementedError("rpointnet: TRAIN_MODULE must be ['SPN']")
     if not config.USE_COLOR:

@@ -39,8 +39,9 @@ extern "C" {
  *   7: round 4 (gspn_nmdistance_grad_csr, gspn_bn_finalize_parts_pivot, gspn_mlp_bwd_fused_coef, gspn_dot, gspn_queryballpoint_ws; gspn_queryballpoint now launches a prefix scan + a continuation kernel -- same output).
  *   9: round 6 (the *_ws drop-in gradient launchers, gspn_fp_concat_grad_csr_split).   10: gspn_threenn_nested.
  *  11: gspn_deconv_fwd / gspn_deconv_bwd_input / gspn_deconv_bwd_kernel (+ _work_bytes).
- *  12: gspn_box_shrink / gspn_points_bbox / gspn_spn_target_gen. */
-#define GSPN_ABI_VERSION 12
+ *  12: gspn_box_shrink / gspn_points_bbox / gspn_spn_target_gen.
+ *  13: gspn_nms3d / gspn_box_point_count / gspn_sample_points_in_boxes / gspn_detection_target_select / gspn_crop_gather_grad. */
+#define GSPN_ABI_VERSION 13
 int gspn_dist_policy(void);
 int gspn_abi_version(void);
 
@@ -266,6 +267,56 @@ int gspn_points_bbox(int rows, int m, const float* pts, const float* offset, flo
  * IoU = intersection / (vol_a + vol_b - intersection + 1e-8). */
 int gspn_spn_target_gen(int b, int s, int g, const float* proposals, const float* seed_cls, const float* gt_cls, const float* gt_boxes,
                         int* spn_match, void* stream);
+
+/* ---------------- models/model_rpointnet.py ROI stage: from shape proposals to the inputs of the heads (gspn_amd/csrc/roi.hip) -------
+ * Same rules as the box arithmetic above: fp32, no atomics, no workspace, no host synchronisation, nothing contracted.
+ *
+ * Random numbers.  A stateless counter-based generator; with 64-bit unsigned arithmetic modulo 2^64 and
+ *   mix(z):  z ^= z >> 30;  z *= 0xBF58476D1CE4E5B9;  z ^= z >> 27;  z *= 0x94D049BB133111EB;  z ^= z >> 31
+ *   gspn_roi_rand32(seed, scene, a, b) = (uint32)(mix(mix(seed + 0x9E3779B97F4A7C15 * (scene + 1)) ^ ((uint64)a << 32 | b)) >> 32)
+ * (the finaliser of splitmix64, twice).  seed is read from ONE int64 on the device (seed_dev), so a captured launch draws afresh on every
+ * replay once the caller has added to that word.  A uniform rank below count is (uint64(rand32) * count) >> 32. */
+
+/* nms_3d (:436-466) for a whole batch, one workgroup per scene.  boxes (b,n,6), scores (b,n) -> selected (b,max_output_size) i32, -1 padded.
+ * Candidates in descending score, the lower index first among equal scores (the reference's argsort leaves that order open); the first
+ * pre_nms_limit of them (all when <= 0) whose score is > score_threshold.  Greedy: the first live candidate is written out, then every live
+ * candidate -- the pick included -- with iou > iou_threshold leaves, iou = inter / (((vol_cand + vol_pick) - inter) + 1e-8f), bounds
+ * c - s/2 and c + s/2, volume (l*w)*h.  A pick whose own iou does not exceed the threshold (zero volume) is picked again, as in the
+ * reference.  n <= 4096. */
+int gspn_nms3d(int b, int n, int pre_nms_limit, int max_output_size, float iou_threshold, float score_threshold, const float* boxes,
+               const float* scores, int* selected, void* stream);
+
+/* count (b,s) i32: the points of pc (b,n,3) with pc >= (c - s/2) - margin && pc <= (c + s/2) + margin on all axes, per box of boxes (b,s,6)
+ * (:673-676 with margin 0, :764-766 with margin 1e-3f). */
+int gspn_box_point_count(int b, int s, int n, float margin, const float* boxes, const float* pc, int* count, void* stream);
+
+/* sample_points_within_box (:584-597) from the boxes themselves: idx_out (b,r,nsmp) i32, draw j of box (scene, roi) is the inside point
+ * (same test as gspn_box_point_count) of ascending rank (uint64(gspn_roi_rand32(seed, scene, roi, j)) * count) >> 32.  A box without an
+ * inside point and an all-zero box give a row of zeros.  n <= 32768. */
+int gspn_sample_points_in_boxes(int b, int r, int n, int nsmp, float margin, const long long* seed_dev, const float* boxes, const float* pc,
+                                int* idx_out, void* stream);
+
+/* The decisions of detection_target_gen (:662-720) for a whole batch, one workgroup per scene.  proposals (b,s,6), count (b,s) i32 (of
+ * gspn_box_point_count, margin 0), gt_cls (b,g) f32 (not read: the reference trims its ground truth by all-zero boxes alone, :664; the
+ * caller gathers the class by roi_gt), gt_boxes (b,g,6) -> roi_src, roi_gt (b,rois_per_image) i32.
+ * A proposal takes part when it is not an all-zero row and count > 0; a ground-truth box when it is not an all-zero row.  Positive: the
+ * largest IoU (as gspn_spn_target_gen) >= 0.5; negative: < 0.5, all of them when no ground-truth box takes part.  Candidate i has the key
+ * gspn_roi_rand32(seed, scene, i, 0xFFFFFFFF); the npos = min(P, max_positive) positives of smallest (key, index) fill rows 0..npos-1 in
+ * that order, then the min(N, (int)(inv_ratio * (float)npos) - npos) negatives of smallest (key, index), the product in fp32.  roi_src: the
+ * proposal of each row, -1 for padding; roi_gt: the ground-truth box of largest IoU (lowest index on ties, untrimmed numbering), -1 for
+ * negatives and padding.  Rows past rois_per_image are dropped.  s <= 1024. */
+int gspn_detection_target_select(int b, int s, int g, int rois_per_image, int max_positive, float inv_ratio, const long long* seed_dev,
+                                 const float* proposals, const int* count, const float* gt_cls, const float* gt_boxes, int* roi_src,
+                                 int* roi_gt, void* stream);
+
+/* The gradient of points_cropping's gathers (:801-803): grad_points (b,n,c) = the sum of grad_out (b,len,c) over the positions whose idx
+ * (b,len) names the point, through the inverse lists order / offsets of idx (gspn_inverse_lists).  The result is the one of
+ * gspn_sa_group_concat_grad_csr up to the grouping of the sum: the sorted positions are cut into chunks of 64, summed per chunk, and the
+ * partial sums of a list that crosses chunks are added in chunk order -- a fixed order, so the bits repeat, and a list of any length (the
+ * rows of zeros of negative and padding ROIs all name point 0) is spread over the chip.  part: gspn_crop_gather_grad_part_floats floats. */
+long gspn_crop_gather_grad_part_floats(int b, int len, int c);
+int gspn_crop_gather_grad(int b, int n, int c, int len, const int* idx, const int* order, const int* offsets, const float* grad_out,
+                          float* part, float* grad_points, void* stream);
 
 /* ---------------- utils/pointnet_util.py composition helpers --------------------------- */
 

@@ -8,16 +8,23 @@
   spn       one full SPN training step -- rpointnet + get_loss + backward, eager, geometry computed inside the step -- at the reference's
             configuration (256 seeds, 100 groups of 512 points, 19 categories, SHRINK_BOX on), and box_shrink on its HIP kernel against the
             reference's broadcast formulation written in torch, alternating in one process, at 256 and 2048 boxes per scene
+  roi       the ROI stage (gspn_amd/roi.py) per op, at the training shape (256 -> 192 -> 128 proposals, 64 ROIs x 256 points) and the inference
+            shape (2048 -> 1536 -> 384, 1024 points per ROI): nms_3d on the device against the host formulation the reference runs (copy to
+            the host, a numpy loop, copy back) alternating in one process, box_point_count, detection_target_gen_batch,
+            mask_selection_gen_batch, and points_cropping forward + backward with --crop-channels feature channels (forward only at the
+            inference shape, which has no backward)
 
 Prints one JSON line per (shape, measurement): median / min milliseconds over --iters timed runs after --warmup runs.
     python tools/spn_step.py --shapes 2x18000,8x32768
     python tools/spn_step.py --shapes 2x18000 --measures spn
+    python tools/spn_step.py --shapes 2x18000 --measures roi
 """
 import argparse
 import json
 import os
 import sys
 
+import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -120,6 +127,84 @@ def measure_spn(a, shape, b, n, dev):
         print(json.dumps({"shape": "%dx%dx%d" % (b, s, n), "kind": a.kind, "measure": "box_shrink", "equal": same, **res}), flush=True)
 
 
+def nms_3d_host(boxes, scores, pre_nms_limit, max_output_size, iou_threshold, score_threshold=float("-inf")):
+    """nms_3d the way the reference runs it: device tensors to the host, greedy suppression per scene in numpy, the indices back"""
+    bx, sc = boxes.cpu().numpy(), scores.cpu().numpy()
+    out = np.full((bx.shape[0], max_output_size), -1, dtype=np.int32)
+    for i in range(bx.shape[0]):
+        lo, hi = bx[i, :, :3] - bx[i, :, 3:] / 2, bx[i, :, :3] + bx[i, :, 3:] / 2
+        vol = bx[i, :, 3] * bx[i, :, 4] * bx[i, :, 5]
+        cand = np.argsort(-sc[i])
+        if pre_nms_limit > 0:
+            cand = cand[:pre_nms_limit]
+        cand = cand[sc[i][cand] > score_threshold]
+        for k in range(max_output_size):
+            if len(cand) == 0:
+                break
+            top = cand[0]
+            out[i, k] = top
+            inter = np.prod(np.maximum(np.minimum(hi[top], hi[cand]) - np.maximum(lo[top], lo[cand]), 0), axis=1)
+            cand = cand[~(inter / (vol[cand] + vol[top] - inter + 1e-8) > iou_threshold)]
+    return torch.from_numpy(out).to(boxes.device)
+
+
+def roi_proposals(gt_boxes, ext, s, gen):
+    """s boxes per scene as SPN hands them on: three quarters jittered copies of ground-truth boxes, the rest random in the room, sizes
+    + 1e-3 like box_shrink's; scores from a permutation (pairwise distinct)"""
+    b, g, _ = gt_boxes.shape
+    nj = (3 * s) // 4
+    src = torch.gather(gt_boxes, 1, torch.randint(0, g, (b, nj), generator=gen).unsqueeze(-1).expand(-1, -1, 6))
+    jit = torch.cat((src[..., :3] + 0.12 * src[..., 3:] * torch.randn(b, nj, 3, generator=gen),
+                     src[..., 3:] * (1 + 0.15 * torch.randn(b, nj, 3, generator=gen)).clamp(min=0.3)), -1)
+    rnd = torch.cat((torch.rand(b, s - nj, 3, generator=gen) * ext, torch.rand(b, s - nj, 3, generator=gen) * 0.9 + 0.6), -1)
+    boxes = torch.cat((jit, rnd), 1)
+    boxes[..., 3:] += 1e-3
+    scores = torch.stack([(torch.randperm(s, generator=gen).float() + 0.5) / s for _ in range(b)])
+    return boxes.contiguous(), scores.contiguous()
+
+
+def measure_roi(a, shape, b, n, dev):
+    from gspn_amd import rpointnet as RP
+    sc = {k: torch.from_numpy(v) for k, v in synth.spn_batch(a.kind, b, n, 100, 512, 19, seed0=7).items()}
+    ext = sc["pc"].amax((0, 1))
+    pc, gt_boxes, group_label = sc["pc"].to(dev), sc["bbox_ins"].to(dev), sc["group_label"].to(dev)
+    gt_cls = RP.seg_label_per_group(sc["seg_label"].to(dev), group_label, 100)
+    seed = torch.zeros(1, dtype=torch.int64, device=dev)
+    for name, cfg in (("training", RP.Config()), ("inference", RP.Config(istrain=False))):
+        train = name == "training"
+        m = cfg.SPN_NMS_MAX_SIZE_TRAINING if train else cfg.SPN_NMS_MAX_SIZE_INFERENCE
+        r, p = (cfg.TRAIN_ROIS_PER_IMAGE, cfg.NUM_POINT_INS_MASK) if train else (m, cfg.NUM_POINT_INS_MASK)
+        boxes, scores = roi_proposals(sc["bbox_ins"], ext, cfg.NUM_SAMPLE, torch.Generator().manual_seed(cfg.NUM_SAMPLE))
+        boxes, scores = boxes.to(dev), scores.to(dev)
+        nms_args = (cfg.SPN_PRE_NMS_LIMIT, m, cfg.SPN_IOU_THRESHOLD)
+        sel = RP.nms_3d(boxes, scores, *nms_args)
+        res = {"nms_equal_to_host": bool(torch.equal(sel, nms_3d_host(boxes, scores, *nms_args))), "nms_picks": (sel >= 0).sum(1).tolist()}
+        res.update(timed_alternating({"nms_3d": lambda: RP.nms_3d(boxes, scores, *nms_args),
+                                      "nms_3d_host_round_trip": lambda: nms_3d_host(boxes, scores, *nms_args)}, a.warmup, a.iters))
+        spn_rois = RP.gather_selection(boxes, sel, m)
+        res["box_point_count"] = timed(lambda: RP.box_point_count(spn_rois, pc), a.warmup, a.iters)
+        fea = torch.randn(b, n, a.crop_channels, device=dev).requires_grad_(train)
+        cen = (pc + 0.1 * torch.randn(b, n, 3, device=dev)).requires_grad_(train)
+        if train:
+            targets = lambda: RP.detection_target_gen_batch(spn_rois, gt_cls, gt_boxes, group_label, pc, cfg, seed)
+            res["detection_target_gen_batch"] = timed(targets, a.warmup, a.iters)
+            rois, _, _, idx, _ = targets()
+        selection = lambda: RP.mask_selection_gen_batch(spn_rois, pc, m, cfg, True, seed)
+        res["mask_selection_gen_batch"] = timed(selection, a.warmup, a.iters)
+        if not train:
+            rois, idx = selection()
+
+        def crop():
+            fea.grad = cen.grad = None
+            out = RP.points_cropping(pc, fea, cen, rois, idx, r, p, cfg.NORMALIZE_CROP_REGION)
+            if train:
+                (out[0].sum() + out[1].sum()).backward()
+
+        res["points_cropping_fwd_bwd" if train else "points_cropping_fwd"] = timed(crop, a.warmup, a.iters)
+        print(json.dumps({"shape": shape, "kind": a.kind, "measure": "roi", "config": name, "proposals": [cfg.NUM_SAMPLE, cfg.SPN_PRE_NMS_LIMIT, m],
+                          "rois": r, "points_per_roi": p, "crop_channels": a.crop_channels, **res}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--measures", default="step,full_fwd,nn,spn")
@@ -128,6 +213,7 @@ def main():
     ap.add_argument("--seed-points", type=int, default=128)          # shape_proposal_net's nsmp
     ap.add_argument("--sem-points", type=int, default=1024)          # model_rpointnet.py:345
     ap.add_argument("--categories", type=int, default=20)
+    ap.add_argument("--crop-channels", type=int, default=1024)       # feature channels of points_cropping in --measures roi
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--iters", type=int, default=10)
     a = ap.parse_args()
@@ -138,6 +224,8 @@ def main():
         b, n = (int(v) for v in shape.split("x"))
         if "spn" in measures:
             measure_spn(a, shape, b, n, dev)
+        if "roi" in measures:
+            measure_roi(a, shape, b, n, dev)
         if not set(measures) & {"step", "full_fwd", "nn"}:
             continue
         xyz = torch.from_numpy(synth.batch(a.kind, b, n)).to(dev)

@@ -2613,6 +2613,8 @@ static bool wgrad_lean_try(long rows, int cin, int cout, const gspn_dy_args* a, 
     int pool_sh = 0;
     if (pooled) {
         if (a->ns < 32 || (a->ns & (a->ns - 1)) || rows % a->ns) return false;
+        // (dPool, pool_arg) are fetched as one quad each per stage; wgrad_choose -- whose use_stream let us in -- looks at X, Y and a dense dZ only
+        if (((uintptr_t)a->dPool % 16) || ((uintptr_t)a->pool_arg % 16)) return false;
         pool_sh = __builtin_ctz(a->ns);
     }
     const long ldmax = std::max(std::max((long)ldx, (long)a->ldy), (long)(pooled ? 0 : a->ldz));
@@ -3347,6 +3349,8 @@ extern "C" int gspn_preagg_bwd_dy(long rows, int cout, const gspn_dy_args* a, co
     if (side_n > 0 && (!side || !part || (!dWside && !nslots_out) || side_ld < side_n)) return GSPN_ERR_ARG;
     if (!preagg_shape_ok(cout) || rows >= (1L << 31) || (a->ldy & 3) || (a->ldz & 3)) return GSPN_ERR_UNSUPPORTED;
     if (((uintptr_t)a->Y % 16) || ((uintptr_t)a->dZ % 16) || ((uintptr_t)dY % 16)) return GSPN_ERR_ARG;
+    // (the kernel takes its five per-channel vectors as quads too)
+    if (((uintptr_t)a->scale | (uintptr_t)a->shift | (uintptr_t)a->cA | (uintptr_t)a->cB | (uintptr_t)a->cC) % 16) return GSPN_ERR_ARG;
     const int rpi = 256 / (cout >> 2);
     long nb = (rows + rpi - 1) / rpi;
     if (nb > PREAGG_BWD_BLOCKS) nb = PREAGG_BWD_BLOCKS;

@@ -152,6 +152,17 @@ def _grad_buffer(param, sunk):
     return torch.empty_like(param)
 
 
+def _grad_release(param, buf, sunk):
+    """undo _grad_buffer(param, sunk) for a launch that declined before it wrote `buf`: the slice is claimable again, so whichever launch does
+    produce the gradient writes it there (a slot left claimed but unwritten would get that gradient ADDED by flatten(), onto whatever the
+    slice held -- the previous step's gradient)"""
+    if buf.data_ptr() in sunk:
+        e = GRAD_SINKS.get(param.data_ptr())
+        if e is not None:
+            e.bucket._written.discard(e.index)
+        sunk.discard(buf.data_ptr())
+
+
 def _zeros(n, dev, dtype=torch.float32):
     return torch.zeros(n, dtype=dtype, device=dev)
 
@@ -399,6 +410,7 @@ class _MlpStack(torch.autograd.Function):
                     npart = ctypes.c_int(0)
                     ev = _tic()
                     merged = None
+                    pg = None
                     try:
                         if want_rsum and sw == 1 and FUSED_COEF:
                             # the previous layer's coefficient kernel and this layer's dW reduction depend on the fused launch only: one launch
@@ -416,6 +428,9 @@ class _MlpStack(torch.autograd.Function):
                         fused = True
                     except NotImplementedError:
                         fused = False
+                        if pg is not None:           # the declined launch filled none of the previous layer's sinks: hand them back
+                            for prm, buf in zip((prev.gamma, prev.beta, prev.biases), pg):
+                                _grad_release(prm, buf, sunk)
                     if fused:
                         _toc(ev, "fused", rows, cin, cout, 4.0 * rows * cin * cout)
                         if merged is not None:
@@ -614,8 +629,14 @@ def _coef_from_parts(lib, rows, c, nparts, part, mean, var, lp, dev, st, sw=1, s
         dgamma, dbeta, dbias = dgb[0], dgb[1], dgb[2]
     if sw > 1:
         _allreduce_sum(part[:int(nparts) * 2 * c])
-    L.check(lib.gspn_mlp_bwd_coef(rows * sw, c, int(nparts), L.ptr(part), L.ptr(mean), L.ptr(var), L.ptr(lp.gamma), BN_EPS,
-                                  L.ptr(cA), L.ptr(cB), L.ptr(cC), L.ptr(dgamma), L.ptr(dbeta), L.ptr(dbias), st), "mlp_bwd_coef")
+    try:
+        L.check(lib.gspn_mlp_bwd_coef(rows * sw, c, int(nparts), L.ptr(part), L.ptr(mean), L.ptr(var), L.ptr(lp.gamma), BN_EPS,
+                                      L.ptr(cA), L.ptr(cB), L.ptr(cC), L.ptr(dgamma), L.ptr(dbeta), L.ptr(dbias), st), "mlp_bwd_coef")
+    except NotImplementedError:
+        if dgb is None:                          # (the dense_rsum block catches this and runs the two-product pass A, which must find the sinks unclaimed; harmless where the caller lets it propagate)
+            for prm, buf in zip((lp.gamma, lp.beta, lp.biases), (dgamma, dbeta, dbias)):
+                _grad_release(prm, buf, sunk)
+        raise
     if sw > 1:
         dgb.mul_(1.0 / sw)
     return cA, cB, cC, dgamma, dbeta, dbias
@@ -691,11 +712,19 @@ def _mlp_stack_sync_bn(x, cin, layers, decay, pool_ns):
     return cur
 
 
-def preagg_ok(layers, is_training, c):
+def _aligned16(t):
+    return t is None or not t.is_contiguous() or t.data_ptr() % 16 == 0          # (a non-contiguous tensor is copied -- to a fresh allocation -- before use)
+
+
+def preagg_ok(layers, is_training, c, x=None):
     """can the stack's first layer be pre-aggregated?  (training-mode BN on the first two layers -- the second layer's pass B hands the
-    first its BN coefficients --, a kernel-friendly width, enough feature columns for the saved GEMM work to matter)"""
+    first its BN coefficients --, a kernel-friendly width, enough feature columns for the saved GEMM work to matter, and operands the
+    pre-aggregation kernels take: they read the first layer's weights and biases, and the source rows `x` in backward, 16 bytes at a time,
+    and their launchers REJECT (not decline) a 4-byte-aligned one -- e.g. a parameter that lives in a flat optimiser buffer behind a
+    tensor of odd length.  Such a stack takes the materialised input rows and the general kernels.)"""
     return (PREAGG and EARLY_R and not DEFER_DW and not (SYNC_BN and not SYNC_BN_FUSED) and is_training and len(layers) >= 2 and layers[0].bn and layers[1].bn
-            and c >= PREAGG_MIN_C and bool(L.lib().gspn_preagg_ok(layers[0].weights.shape[1])))
+            and c >= PREAGG_MIN_C and bool(L.lib().gspn_preagg_ok(layers[0].weights.shape[1]))
+            and _aligned16(layers[0].weights) and _aligned16(layers[0].biases) and _aligned16(x))
 
 
 def mlp_stack(x, cin, layers, is_training, bn_decay, pool_ns=None, grad_cols=None, gather=None, preagg=None):
@@ -711,12 +740,12 @@ def mlp_stack(x, cin, layers, is_training, bn_decay, pool_ns=None, grad_cols=Non
         raise ValueError("mlp_stack needs at least one layer")
     x = L.need(x, torch.float32, 2, "x")
     if gather is not None:
-        if x.shape[1] % 4 or gather["c"] > x.shape[1] or cin != 3 + gather["c"] or len(layers) < 2 or layers[0].weights.shape[1] % 4:
-            raise NotImplementedError("mlp_stack(gather=): needs 16-byte feature rows, >= 2 layers and a first layer of 4k output channels")
+        if x.shape[1] % 4 or x.data_ptr() % 16 or gather["c"] > x.shape[1] or cin != 3 + gather["c"] or len(layers) < 2 or layers[0].weights.shape[1] % 4:
+            raise NotImplementedError("mlp_stack(gather=): needs 16-byte aligned feature rows, >= 2 layers and a first layer of 4k output channels")
         if SYNC_BN and not SYNC_BN_FUSED:
             raise NotImplementedError("mlp_stack(gather=) with the layer-by-layer SyncBN form")
     if preagg is not None:
-        if gather is not None or not preagg_ok(layers, is_training, preagg["c"]) or cin != preagg["c"] + preagg["side_n"]:
+        if gather is not None or not preagg_ok(layers, is_training, preagg["c"], x) or cin != preagg["c"] + preagg["side_n"]:
             raise NotImplementedError("mlp_stack(preagg=): training-mode BN stacks of >= 2 layers, cin = c + side_n, no gather")
     if pool_ns and (preagg["rows"] if preagg is not None else (gather["rows"] if gather is not None else x.shape[0])) % pool_ns:
         raise ValueError("rows must be a multiple of pool_ns")

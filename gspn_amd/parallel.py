@@ -210,7 +210,7 @@ class FlatAdam:
         self.m = torch.zeros_like(self.flat)
         self.v = torch.zeros_like(self.flat)
         self._t = 0
-        self._dev_state = torch.zeros(2, dtype=torch.int64, device=self.flat.device) if device_step else None
+        self._dev_state = torch.zeros(2, dtype=torch.int64, device=self.flat.device) if device_step else None      # (updates done, tickets drawn): both start at 0
 
     @property
     def t(self):
@@ -221,7 +221,9 @@ class FlatAdam:
     def t(self, value):
         self._t = int(value)
         if self._dev_state is not None:
-            self._dev_state[0] = int(value)
+            # both words: the ticket word is cleared only by the workgroup that draws the LAST ticket of a launch, so a launch that did not
+            # complete leaves it non-zero -- and no later launch would then draw "last" where it should, i.e. publish its step
+            self._dev_state.copy_(torch.tensor([int(value), 0], dtype=torch.int64))
 
     def zero_grad(self, set_to_none=True):
         for p in self.bucket.params:

@@ -163,7 +163,7 @@ def _sa_stack_gathered(points, geometry, xyz_first, cin, layers, is_training, bn
             feat = f4                                                                        # padded ahead of time beside the coordinates (sa_geometry(points=...))
         else:
             feat = _PadCols.apply(feat, (c + 3) // 4 * 4)                                      # 16-byte feature rows (the pad columns are ignored)
-    if preagg_ok(layers, bool(is_training), c):
+    if preagg_ok(layers, bool(is_training), c, feat):
         # the first layer's feature part on the b*n points instead of the b*m*ns grouped rows (mlp.py: PREAGG)
         order, offsets, idx = geometry.order, geometry.offsets, geometry.idx
 
@@ -337,7 +337,7 @@ def pointnet_fp_module(xyz1, xyz2, points1, points2, mlp, is_training, bn_decay,
         layers = _mlp_layers(mlp, cin, 'conv_', bn)
         c1 = 0 if points1 is None else points1.shape[2]
         if (FUSE_FP_FRONT and c1 <= 4 and (points1 is None or not points1.requires_grad) and points2.shape[2] % 4 == 0
-                and preagg_ok(layers, bool(is_training), points2.shape[2])):
+                and preagg_ok(layers, bool(is_training), points2.shape[2], points2)):
             # the first layer's interpolated part on the n2 sparse points (linear: interpolate(points2) . W = interpolate(points2 . W)),
             # the <= 4 skip-link columns per dense row on the side (mlp.py: PREAGG) -- the (b*n1, c2 + c1) matrix is never written
             out = _fp_stack_preagg(points2, points1, geometry, cin, layers, is_training, bn_decay)

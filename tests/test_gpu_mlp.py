@@ -35,17 +35,65 @@ def make_params(chans, cin, seed, bn=True):
     return ps
 
 
-def to_layers(ps):
+def misaligned(t, k=1):
+    """the same values in a contiguous view whose data pointer is 4 * k bytes past a 16-byte boundary (fresh torch allocations are aligned far
+    beyond 16 bytes): what a parameter of a flat optimiser buffer, or a gradient slice of a flat bucket, is behind a tensor of odd length"""
+    assert 1 <= k <= 3 and t.dtype in (torch.float32, torch.int32)
+    buf = torch.empty(t.numel() + 4, dtype=t.dtype, device=t.device)
+    assert buf.data_ptr() % 16 == 0
+    v = buf[k:k + t.numel()].view_as(t)
+    v.copy_(t)
+    assert v.is_contiguous() and v.data_ptr() % 16 == 4 * k
+    return v
+
+
+PLACES = ("x", "params", "grad", "all")      # which operands of a stack check_stack / check_stack_routed put through misaligned()
+
+
+def _placed(place, what):
+    assert place is None or place in PLACES
+    return place is not None and place in (what, "all")
+
+
+def to_layers(ps, place=None):
     from gspn_amd.mlp import LayerParams
     layers = []
+    mis = _placed(place, "params")
+    k = [0]
+
+    def put(t):
+        t = t.float().cuda()
+        if mis:
+            k[0] = k[0] % 3 + 1                  # residues 4, 8, 12 in turn
+            t = misaligned(t, k[0])
+        return t
     for p in ps:
-        f = lambda t, rg=True: torch.nn.Parameter(t.float().cuda(), requires_grad=rg)
+        f = lambda t, rg=True: torch.nn.Parameter(put(t), requires_grad=rg)
         if p["bn"]:
             layers.append(LayerParams(f(p["w"]), f(p["b"]), True, f(p["beta"]), f(p["gamma"]),
-                                      p["moving_mean"].float().cuda(), p["moving_var"].float().cuda()))
+                                      put(p["moving_mean"]), put(p["moving_var"])))
         else:
             layers.append(LayerParams(f(p["w"]), f(p["b"]), False))
+    if mis:
+        for lp in layers:
+            for t in lp.tensors() + ([lp.moving_mean, lp.moving_variance] if lp.bn else []):
+                assert t.data_ptr() % 16 != 0
     return layers
+
+
+def place_x(x, place):
+    """the stack's input as a leaf, through misaligned() when `place` names it"""
+    if _placed(place, "x"):
+        x = misaligned(x)
+        assert x.data_ptr() % 16 == 4
+    return x.requires_grad_(True)
+
+
+def place_grad(go, place):
+    if _placed(place, "grad"):
+        go = misaligned(go)
+        assert go.data_ptr() % 16 == 4 and go.is_contiguous()
+    return go
 
 
 def fragile_entries(zs, ns):
@@ -72,8 +120,10 @@ def fragile_entries(zs, ns):
     return near | frag_rows[win_row] | win_small, frag_rows
 
 
-def check_stack(rows, ld, cin, chans, ns, training, ref_device="cpu", neg_gamma=False, max_fragile=0.02):
-    """mlp_stack forward + backward against oracle/mlp_ref.py evaluated in float64 on `ref_device`"""
+def check_stack(rows, ld, cin, chans, ns, training, ref_device="cpu", neg_gamma=False, max_fragile=0.02, place=None, results=None):
+    """mlp_stack forward + backward against oracle/mlp_ref.py evaluated in float64 on `ref_device`.
+    place (one of PLACES): the operands handed to the stack through misaligned() -- same values, 4-byte aligned only; the float64 side is the same.
+    results (a dict): receives the GPU's output, dX and parameter gradients, for a caller that compares two runs of one case."""
     from gspn_amd.mlp import mlp_stack
     g = torch.Generator().manual_seed(rows + cin)
     x64 = torch.randn(rows, ld, generator=g, dtype=torch.float64)
@@ -85,8 +135,8 @@ def check_stack(rows, ld, cin, chans, ns, training, ref_device="cpu", neg_gamma=
         for p in ps:
             p["moving_mean"] = torch.randn(p["w"].shape[1], generator=g, dtype=torch.float64) * 0.1
             p["moving_var"] = torch.rand(p["w"].shape[1], generator=g, dtype=torch.float64) + 0.5
-    layers = to_layers(ps)
-    x = x64.float().cuda().requires_grad_(True)
+    layers = to_layers(ps, place)
+    x = place_x(x64.float().cuda(), place)
     out = mlp_stack(x, cin, layers, training, 0.7, pool_ns=ns)
 
     xr = x64[:, :cin].to(ref_device).clone().requires_grad_(True)
@@ -136,7 +186,9 @@ def check_stack(rows, ld, cin, chans, ns, training, ref_device="cpu", neg_gamma=
     go = torch.randn(ref.shape, generator=g, dtype=torch.float64).to(ref_device)
     go[fragile] = 0
     ref.backward(go)
-    out.backward(go.float().cuda())
+    out.backward(place_grad(go.float().cuda(), place))
+    if results is not None:
+        results.update(out=out.detach(), dX=x.grad[:, :cin].detach(), layers=layers, grads=[t.grad.detach() for lp in layers for t in lp.tensors()])
     tol = 1e-4
     keep = ~frag_rows
     assert rel_err(x.grad[:, :cin][keep.to(x.device)], xr.grad[keep]) < tol
@@ -149,21 +201,23 @@ def check_stack(rows, ld, cin, chans, ns, training, ref_device="cpu", neg_gamma=
         assert float((lp.biases.grad.double().cpu() - p["b"].grad.cpu()).abs().max()) < tol * max(scale, float(p["b"].grad.abs().max()))
 
 
-def check_stack_routed(rows, ld, cin, chans, ns, ref_device="cuda", tol=1e-5):
+def check_stack_routed(rows, ld, cin, chans, ns, ref_device="cuda", tol=1e-5, place=None, results=None):
     """Gradients at north_star's 1e-5, NOTHING silenced.  check_stack above compares against a float64 evaluation that makes its
     own ReLU / arg-max decisions and therefore has to zero the upstream gradient wherever float32 might decide differently.  Here the float64
     backward is ROUTED by the decisions the GPU forward actually took: layer l's ReLU mask is sign(fma(y, scale, shift)) of the GPU's own float32
     (y, scale, shift) -- the expression every kernel applies (csrc/mlp.hip) -- and the pool takes the row the GPU's arg-max names.  With the routing equal,
     every remaining difference is float32 arithmetic, and all of dX (every row), dW, dgamma, dbeta, dbias are held to `tol` of their largest element.
     (That the decisions themselves are right is what the forward comparison at 1e-5 and check_stack establish: a wrong mask away from the kink would show
-    there.)"""
+    there.)
+    place (one of PLACES): the operands handed to the stack through misaligned(); the float64 side does not change.  results (a dict): receives the
+    GPU's output, dX and parameter gradients, for a caller that compares two runs of one case."""
     from gspn_amd.mlp import mlp_stack
     g = torch.Generator().manual_seed(rows + cin + 1)
     x64 = torch.randn(rows, ld, generator=g, dtype=torch.float64)
     x64[:, cin:] = 0
     ps = make_params(chans, cin, seed=cin + 1)
-    layers = to_layers(ps)
-    x = x64.float().cuda().requires_grad_(True)
+    layers = to_layers(ps, place)
+    x = place_x(x64.float().cuda(), place)
     out = mlp_stack(x, cin, layers, True, 0.7, pool_ns=ns)
     node = out.grad_fn                                    # the autograd node IS the ctx of _MlpStack.forward
     masks = []
@@ -191,7 +245,10 @@ def check_stack_routed(rows, ld, cin, chans, ns, ref_device="cuda", tol=1e-5):
     assert rel_err(out, ref) < 1e-5
     go = torch.randn(ref.shape, generator=g, dtype=torch.float64).to(ref_device)
     ref.backward(go)
-    out.backward(go.float().cuda())
+    out.backward(place_grad(go.float().cuda(), place))
+    if results is not None:
+        results.update(out=out.detach(), dX=x.grad[:, :cin].detach(), layers=layers,
+                       grads=[t.grad.detach() for lp in layers for t in lp.tensors()])
     errs = {"dX": rel_err(x.grad[:, :cin], xr.grad)}
     for li, (lp, p) in enumerate(zip(layers, ps)):
         errs["dW%d" % li] = rel_err(lp.weights.grad, p["w"].grad)

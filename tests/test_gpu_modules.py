@@ -506,6 +506,60 @@ def test_flat_adam_with_the_step_counter_on_the_device_equals_the_host_counted_o
     assert torch.equal(outs[0], outs[2])
 
 
+def test_flat_adam_device_step_has_the_host_counted_bits_at_every_step_count():
+    """the bias corrections 1 - b^t are computed in double by the host's pow for gspn_adam_flat and by the device's pow for gspn_adam_flat_dev, then
+    rounded to float: ONE update at each t in 1..64 and at 100, 1000, 4096, 1e4, 1e5, 1e6 (set through the `t` setter, fresh moments) leaves the same
+    bits in every parameter"""
+    from gspn_amd.parallel import FlatAdam, FlatGradBucket
+    g = torch.Generator().manual_seed(21)
+    init = torch.randn(70001, generator=g)
+    grad = torch.randn(70001, generator=g).cuda()
+    differ = []
+    for t in list(range(1, 65)) + [100, 1000, 4096, 10 ** 4, 10 ** 5, 10 ** 6]:
+        outs = []
+        for device_step in (False, True):
+            bucket = FlatGradBucket([torch.nn.Parameter(init.clone().cuda())])
+            opt = FlatAdam(bucket, lr=1e-2, weight_decay=1e-3, device_step=device_step)
+            opt.t = t - 1
+            bucket.flat.copy_(grad)
+            opt.step(grad_scale=0.5)
+            torch.cuda.synchronize()
+            assert opt.t == t
+            outs.append(opt.flat.clone())
+        if not torch.equal(outs[0], outs[1]):
+            differ.append((t, int((outs[0] != outs[1]).sum())))
+    assert not differ, "update number, elements that differ: %s" % differ
+
+
+def test_flat_adam_t_setter_clears_a_ticket_word_left_by_an_unfinished_launch():
+    """state[1] counts the workgroups of the running launch that are done; only the one that draws the last ticket clears it.  A non-zero value left
+    behind (written from the host here) must not survive the `t` setter: the counter then advances by one per step() and the parameters equal the
+    host-counted run's"""
+    from gspn_amd.parallel import FlatAdam, FlatGradBucket
+    g = torch.Generator().manual_seed(22)
+    init = torch.randn(70001, generator=g)
+    grads = [torch.randn(70001, generator=g).cuda() for _ in range(4)]
+    outs = []
+    for device_step in (False, True):
+        bucket = FlatGradBucket([torch.nn.Parameter(init.clone().cuda())])
+        opt = FlatAdam(bucket, lr=1e-2, weight_decay=1e-3, device_step=device_step)
+        if device_step:
+            opt._dev_state[1] = 5
+            torch.cuda.synchronize()
+        opt.t = 3
+        if device_step:
+            assert opt._dev_state.tolist() == [3, 0]
+        for k, gr in enumerate(grads):
+            bucket.flat.copy_(gr)
+            opt.step()
+            torch.cuda.synchronize()
+            assert opt.t == 4 + k
+            if device_step:
+                assert int(opt._dev_state[1].item()) == 0
+        outs.append(opt.flat.clone())
+    assert torch.equal(outs[0], outs[1])
+
+
 @pytest.mark.parametrize("n", [1, 3, 4096, 1_000_003, 16_777_216])
 def test_dot_kernel_is_deterministic_and_close_to_float64(n):
     """gspn_dot (r04: the bench's loss <out, g> on the library's own kernel instead of a library reduction): two launches, 1024 partials added

@@ -411,3 +411,85 @@ def test_spn_step_captured_full_size():
     assert torch.allclose(st["out"][1], out0[1], rtol=1e-5, atol=1e-6)
     assert torch.isfinite(st["out"][3])
     assert torch.allclose(st["bucket"].flat, flat0, rtol=1e-4, atol=1e-7)
+
+
+def test_spn_step_captured_full_size_with_the_flat_optimiser():
+    """the step of test_spn_step_captured_full_size after parallel.FlatAdam has moved every parameter into one flat buffer, with the gradient sinks
+    off and on.  sem_net's fc2 has 19 biases, so every parameter stored behind them -- and every gradient slice of the bucket -- starts on a 4-byte
+    boundary only: the configuration in which the shared MLP, the transposed convolutions, the stand-alone batch norm and the row-blocked
+    1152-channel layer see parameters that no fresh allocation would hand them.  Eager against a replay from CapturedStep and sinks off against
+    sinks on at that test's tolerances; the moved step against the unmoved one: loss within rtol 1e-4 (what that test grants two executions of
+    one step's gradients; a loss is smoother than a gradient), the bucket difference printed."""
+    from gspn_amd import mlp, parallel
+    from gspn_amd.graph import CapturedStep
+    from gspn_amd.rpointnet import Config, get_loss, rpointnet
+    from gspn_amd.shape_proposal import check_spn_inputs, valid_instances
+    from gspn_amd.spn_trunks import spn_geometry
+    cfg = Config()
+    cfg.SHRINK_BOX = True
+    sc = scene(seed=50, b=cfg.BATCH_SIZE, n=cfg.NUM_POINT, ngroup=cfg.NUM_GROUP, nins=cfg.NUM_POINT_INS, ncat=cfg.NUM_CATEGORY,
+               invalid=(7, 31, 64, 99), stray=0.01)
+    check_spn_inputs(sc["pc"], sc["pc_ins"], sc["group_label"], sc["group_indicator"])
+    geo = spn_geometry(sc["pc"], cfg.NUM_SAMPLE, SEM, points=sc["color"])
+    valid = valid_instances(sc["group_indicator"])
+    noise = torch.randn(cfg.BATCH_SIZE, cfg.NUM_SAMPLE, 256, device="cuda")
+    runs = {}
+    for mode in ("unmoved", "moved", "moved+sinks"):
+        store = fresh_store(48)
+        st = {}
+
+        def step():
+            for p in store.parameters():
+                p.grad = None
+            ep = rpointnet(sc["pc"], sc["color"], sc["pc_ins"], sc["group_label"], sc["group_indicator"], sc["seg_label"], sc["bbox_ins"], cfg,
+                           True, bn_decay=DECAY, geometry=geo, noise=noise, valid_idx=valid)
+            _, ep = get_loss(ep, cfg, 1.0, sc["smpw"])
+            loss = ep['kl_loss'] * 1.0 + ep['recons_loss'] + ep['shift_loss'] + ep['spn_class_loss'] + 0.0 * ep['sem_loss']
+            loss.backward()
+            if "bucket" not in st:                          # the first call creates the variables: bucket, optimiser and sinks come after it
+                st["bucket"] = parallel.FlatGradBucket(store.parameters())
+                if mode != "unmoved":
+                    st["opt"] = parallel.FlatAdam(st["bucket"], lr=0.0)          # lr 0: the parameters move, their values stay
+                if mode == "moved+sinks":
+                    st["bucket"].attach_sinks()
+            st["bucket"].flatten()
+            st["out"] = [ep[k].detach() for k in ('pc_ins_pred', 'bbox_ins_pred', 'spn_match', 'sem_loss')]
+            return loss.detach()
+
+        try:
+            step()
+            bucket = st["bucket"]
+            if mode != "unmoved":
+                pres = sorted({p.data_ptr() % 16 for p in store.parameters()})
+                gres = sorted({v.data_ptr() % 16 for v in bucket._views})
+                print("%s: data-pointer residues of the parameters %s, of the gradient slices %s" % (mode, pres, gres))
+                assert any(r != 0 for r in pres) and any(r != 0 for r in gres)
+            bucket.flat.fill_(float("nan"))
+            loss0 = step().clone()
+            out0 = [o.clone() for o in st["out"]]
+            flat0 = bucket.flat.clone()
+            assert all(p.grad.data_ptr() == v.data_ptr() for p, v in zip(store.parameters(), bucket._views))
+            cap = CapturedStep(step)
+            bucket.flat.fill_(float("nan"))
+            loss1 = cap.replay()
+            torch.cuda.synchronize()
+            assert torch.isfinite(loss0) and torch.isfinite(flat0).all() and all(bool(torch.isfinite(o.float()).all()) for o in out0)
+            assert torch.isfinite(bucket.flat).all() and float(flat0.abs().max()) > 0
+            assert torch.allclose(loss1, loss0, rtol=1e-6)
+            assert torch.allclose(st["out"][0], out0[0], rtol=1e-5, atol=1e-6)
+            assert torch.allclose(st["out"][1], out0[1], rtol=1e-5, atol=1e-6)
+            assert torch.allclose(bucket.flat, flat0, rtol=1e-4, atol=1e-7)
+            runs[mode] = (loss0, out0, flat0)
+        finally:
+            if "bucket" in st:
+                for k in [k for k, e in mlp.GRAD_SINKS.items() if e.bucket is st["bucket"]]:
+                    del mlp.GRAD_SINKS[k]
+    a, b = runs["moved"], runs["moved+sinks"]
+    assert torch.allclose(b[0], a[0], rtol=1e-6)
+    assert torch.allclose(b[1][0], a[1][0], rtol=1e-5, atol=1e-6) and torch.allclose(b[1][1], a[1][1], rtol=1e-5, atol=1e-6)
+    assert torch.allclose(b[2], a[2], rtol=1e-4, atol=1e-7)
+    u = runs["unmoved"]
+    d = (a[2] - u[2]).abs()
+    print("moved against unmoved step: loss %.9g / %.9g; bucket: largest difference %.3g (largest element %.3g), %d of %d elements outside rtol 1e-4, atol 1e-7"
+          % (float(a[0]), float(u[0]), float(d.max()), float(u[2].abs().max()), int((d > 1e-7 + 1e-4 * u[2].abs()).sum()), d.numel()))
+    assert torch.allclose(a[0], u[0], rtol=1e-4)

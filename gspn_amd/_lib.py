@@ -129,6 +129,8 @@ SIGNATURES = {
     "gspn_sample_points_in_boxes": [_I, _I, _I, _I, _F, _P, _P, _P, _P, _P],
     "gspn_detection_target_select": [_I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P],
     "gspn_crop_gather_grad": [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
+    "gspn_class_nms3d": [_I, _I, _I, _I, _F, _P, _P, _P, _P, _P],
+    "gspn_nearest_in_sets": [_I, _I, _I, _I, _P, _P, _P, _P, _P],
 }
 
 # entry points that do not return an int status: symbol -> (argtypes, restype)
@@ -156,7 +158,7 @@ SPECIAL = {
     "gspn_crop_gather_grad_part_floats": ([_I, _I, _I], _L),
 }
 
-ABI_VERSION = 13        # == GSPN_ABI_VERSION of include/gspn_hip.h this binding was written against
+ABI_VERSION = 14        # == GSPN_ABI_VERSION of include/gspn_hip.h this binding was written against
 
 _lib = None
 

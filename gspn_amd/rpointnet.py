@@ -5,11 +5,15 @@ SPN terms of get_loss (:1325), with the helpers they use (box_shrink :529, spn_t
 Every shape here is static and nothing reads a value back to the host, so with the geometry, the valid-instance index and the noise
 prepared outside, rpointnet + get_loss + backward capture in a graph.CapturedStep.  The ROI stage behind it -- nms_3d (:436),
 detection_target_gen (:647), mask_selection_gen (:749), points_cropping (:785), box_refinement (:553), apply_box_delta (:570) -- lives in
-roi.py and is re-exported here under the reference's names.  What needs the detection heads (the FPN layers, classification_head,
-segmentation_head, their losses, refine_detections, inference) is not implemented and raises NotImplementedError."""
+roi.py and is re-exported here under the reference's names, and so is the detection output stage behind the heads -- refine_detections
+(:818), select_segmentation (:986), unmold_segmentation (:1008), with the extensions class_nms_3d and nearest_in_sets -- which lives in
+detect.py.  What needs the detection heads themselves (the FPN layers, classification_head, segmentation_head, their losses, inference)
+is not implemented and raises NotImplementedError."""
 import torch
 
 from . import _lib as L
+from .detect import (class_nms_3d, nearest_in_sets, refine_detections, refine_detections_batch, select_segmentation,
+                     unmold_segmentation)
 from .proposal_head import chamfer_recons_loss
 from .roi import (apply_box_delta, box_point_count, box_refinement, detection_target_gen, detection_target_gen_batch, mask_selection_gen,
                   mask_selection_gen_batch, nms_3d, points_cropping, sample_points_in_boxes)
@@ -18,7 +22,8 @@ from .spn_boxes import box_shrink, points_bbox, spn_target_gen_batch
 
 __all__ = ["Config", "box_shrink", "spn_target_gen", "spn_target_gen_batch", "gather_selection", "smooth_l1_loss", "get_spn_class_loss",
            "seg_label_per_group", "rpointnet", "get_loss", "nms_3d", "box_point_count", "sample_points_in_boxes", "detection_target_gen",
-           "detection_target_gen_batch", "mask_selection_gen", "mask_selection_gen_batch", "points_cropping", "box_refinement", "apply_box_delta"]
+           "detection_target_gen_batch", "mask_selection_gen", "mask_selection_gen_batch", "points_cropping", "box_refinement", "apply_box_delta",
+           "class_nms_3d", "refine_detections", "refine_detections_batch", "select_segmentation", "nearest_in_sets", "unmold_segmentation"]
 
 
 class Config(object):

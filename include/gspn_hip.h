@@ -40,8 +40,9 @@ extern "C" {
  *   9: round 6 (the *_ws drop-in gradient launchers, gspn_fp_concat_grad_csr_split).   10: gspn_threenn_nested.
  *  11: gspn_deconv_fwd / gspn_deconv_bwd_input / gspn_deconv_bwd_kernel (+ _work_bytes).
  *  12: gspn_box_shrink / gspn_points_bbox / gspn_spn_target_gen.
- *  13: gspn_nms3d / gspn_box_point_count / gspn_sample_points_in_boxes / gspn_detection_target_select / gspn_crop_gather_grad. */
-#define GSPN_ABI_VERSION 13
+ *  13: gspn_nms3d / gspn_box_point_count / gspn_sample_points_in_boxes / gspn_detection_target_select / gspn_crop_gather_grad.
+ *  14: gspn_class_nms3d / gspn_nearest_in_sets. */
+#define GSPN_ABI_VERSION 14
 int gspn_dist_policy(void);
 int gspn_abi_version(void);
 
@@ -317,6 +318,26 @@ int gspn_detection_target_select(int b, int s, int g, int rois_per_image, int ma
 long gspn_crop_gather_grad_part_floats(int b, int len, int c);
 int gspn_crop_gather_grad(int b, int n, int c, int len, const int* idx, const int* order, const int* offsets, const float* grad_out,
                           float* part, float* grad_points, void* stream);
+
+/* ---------------- models/model_rpointnet.py detection output stage: behind the two heads (gspn_amd/csrc/detect.hip) -------------------
+ * Same rules as the ROI stage: fp32, no atomics, no workspace, no host synchronisation, nothing contracted. */
+
+/* The per-class NMS of refine_detections (:855-901) for a whole batch, one workgroup per scene.  boxes (b,n,6), scores (b,n), class_ids
+ * (b,n) i32 -> selected (b,max_output_size) i32, -1 padded.  A row is a candidate when class_ids > 0 (the caller folds its confidence filter
+ * in by zeroing the class id).  Within one class the picks are those of gspn_nms3d with pre_nms_limit -1 and score_threshold -inf on the
+ * rows of that class -- descending score, the lower index first among equal scores, iou = inter / (((vol_cand + vol_pick) - inter) + 1e-8f),
+ * a candidate leaves when iou > iou_threshold -- with max_per_class picks at most; a pick that survives its own test is picked again until
+ * the class is full (zero volume; at a threshold of 0.1 any volume below about 1.1e-9), and the repeated picks count as one row (:893).
+ * Classes do not suppress each other.  selected: the picked rows of all classes in descending score, the lower index first among equal
+ * scores, the first max_output_size of them (:897-901).  n <= 4096. */
+int gspn_class_nms3d(int b, int n, int max_per_class, int max_output_size, float iou_threshold, const float* boxes, const float* scores,
+                     const int* class_ids, int* selected, void* stream);
+
+/* The nearest point of r sets per scene for every query point, behind a box test (unmold_segmentation, :1032-1044, without its (B,R,N,P)
+ * distance tensor).  query (b,n,3), sets (b,r,p,3), boxes (b,r,6) or NULL -> idx (b,r,n) i32: the position j that minimises
+ * (dx*dx + dy*dy) + dz*dz, d = query[s,i] - sets[s,k,j], the smallest j among equal distances (tf.argmin).  With boxes, a query that is
+ * not inside box k -- q >= c - s/2 && q <= c + s/2 on all axes -- gets -1 and is not searched.  p <= 4096, n <= 32768. */
+int gspn_nearest_in_sets(int b, int r, int n, int p, const float* query, const float* sets, const float* boxes, int* idx, void* stream);
 
 /* ---------------- utils/pointnet_util.py composition helpers --------------------------- */
 

@@ -1,0 +1,388 @@
+"""GPU tests of the detection output stage (gspn_amd/detect.py on csrc/detect.hip).  Every comparison is exact: class_nms_3d against the
+reference's own nms_3d run class by class (tests/golden/detect/class_nms_ref.npz) and against the restatement of tests/detect_ref.py,
+refine_detections_batch against the restatement run from the device's own refined boxes (exp differs by an ulp between host and device),
+nearest_in_sets index by index against a float32 first-index argmin -- with duplicated crop points, lattice clouds with equidistant
+candidates, queries exactly on the faces of a box, an all-zero box and a box without a point --, unmold_segmentation and
+select_segmentation against their restatements, and the whole chain captured in a graph."""
+import functools
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from tests import detect_ref as DR
+from tests import roi_ref as RR
+
+pytestmark = pytest.mark.gpu
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "detect", "class_nms_ref.npz")
+ROOM = torch.tensor(RR.ROOM)
+
+
+def config(max_instances=100, min_confidence=0.7, shrink=False, nsmp=256):
+    from gspn_amd.rpointnet import Config
+    cfg = Config(istrain=False)
+    cfg.DETECTION_MAX_INSTANCES, cfg.DETECTION_MIN_CONFIDENCE, cfg.SHRINK_BOX, cfg.NUM_POINT_INS_MASK = max_instances, min_confidence, shrink, nsmp
+    return cfg
+
+
+# ---- class_nms_3d ------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("name", sorted(DR.CLASS_NMS_CASES))
+def test_class_nms_3d_equals_the_reference_function_per_class(name):
+    from gspn_amd.rpointnet import class_nms_3d
+    z = np.load(GOLDEN)
+    per_class, m, thr = z[name + "/args"].tolist()
+    boxes, scores, cls = (torch.from_numpy(z[name + "/" + k]) for k in ("boxes", "scores", "class_ids"))
+    got = class_nms_3d(boxes.cuda(), scores.cuda(), cls.cuda(), int(per_class), int(m), thr)
+    assert got.dtype == torch.int32 and got.is_cuda and got.shape == (boxes.shape[0], int(m))
+    assert torch.equal(got.cpu(), torch.from_numpy(z[name + "/selected"]))
+
+
+@pytest.mark.parametrize("b,n,classes,per_class,m,thr,zero_volume,empty", [
+    (2, 384, 19, 100, 100, 0.1, 4, ()), (1, 4096, 3, 50, 128, 0.25, 8, ()), (3, 1, 2, 4, 4, 0.5, 0, (1,)), (2, 65, 70, 3, 70, 0.3, 2, (0,)),
+    (1, 100, 1, 10, 10, 0.1, 0, ())])
+def test_class_nms_3d_equals_the_restatement(b, n, classes, per_class, m, thr, zero_volume, empty):
+    """classes counts the background: the ids are 0 .. classes - 1, so one class means that no row is a candidate"""
+    from gspn_amd.rpointnet import class_nms_3d
+    boxes, scores, cls = DR.class_boxes(b, n, classes - 1, 2000 + n + b, zero_volume, empty)
+    for row in scores:
+        assert row.unique().numel() == n
+    want = DR.class_nms(boxes, scores, cls, per_class, m, thr)
+    got = class_nms_3d(boxes.cuda(), scores.cuda(), cls.cuda(), per_class, m, thr).cpu()
+    assert torch.equal(got, want)
+    none = (cls > 0).sum(1) == 0
+    assert bool(none.any()) == (classes == 1 or len(empty) > 0) and (want[none] == -1).all()
+    if n >= 65 and not none.all():
+        assert (want[~none] >= 0).any(1).all()
+
+
+def test_class_nms_3d_ties_zero_volume_and_limits():
+    from gspn_amd.rpointnet import class_nms_3d
+    # equal scores within and across classes: the lower index first; row 3 overlaps row 0 and leaves, row 5 overlaps it from another class
+    boxes = torch.tensor([[[0.0, 0, 0, 1, 1, 1], [5.0, 0, 0, 1, 1, 1], [10.0, 0, 0, 1, 1, 1], [0.1, 0, 0, 1, 1, 1], [20.0, 0, 0, 1, 1, 1],
+                           [0.1, 0, 0, 1, 1, 1]]])
+    scores = torch.tensor([[0.5, 0.9, 0.5, 0.5, 0.95, 0.5]])
+    cls = torch.tensor([[1, 2, 2, 1, 0, 2]], dtype=torch.int32)
+    assert class_nms_3d(boxes.cuda(), scores.cuda(), cls.cuda(), 6, 6, 0.5).cpu().tolist() == [[1, 0, 2, 5, -1, -1]]
+    assert class_nms_3d(boxes.cuda(), scores.cuda(), cls.cuda(), 1, 6, 0.5).cpu().tolist() == [[1, 0, -1, -1, -1, -1]]
+    assert class_nms_3d(boxes.cuda(), scores.cuda(), cls.cuda(), 6, 3, 0.5).cpu().tolist() == [[1, 0, 2]]
+    # a zero-volume box on top of class 1 exhausts class 1 only: row 3 does not overlap it and is still never picked
+    boxes[0, 0, 3] = 0.0
+    scores[0, 0] = 0.99
+    boxes[0, 3, 0] = 7.0
+    assert DR.class_nms(boxes, scores, cls, 6, 6, 0.5).tolist() == [[0, 1, 2, 5, -1, -1]]
+    assert class_nms_3d(boxes.cuda(), scores.cuda(), cls.cuda(), 6, 6, 0.5).cpu().tolist() == [[0, 1, 2, 5, -1, -1]]
+    # many equal scores among 512 boxes of 5 classes, negative scores among them
+    bx, sc, ci = DR.class_boxes(2, 512, 5, 5, 3)
+    sc = (torch.floor(sc * 16) / 16 - 0.5).contiguous()
+    assert sc[0].unique().numel() == 16
+    for per_class, m, thr in ((100, 100, 0.1), (4, 30, 0.4), (100, 7, 0.25)):
+        assert torch.equal(class_nms_3d(bx.cuda(), sc.cuda(), ci.cuda(), per_class, m, thr).cpu(), DR.class_nms(bx, sc, ci, per_class, m, thr))
+    zeros = torch.zeros(1, 4097, device="cuda")
+    with pytest.raises(NotImplementedError):
+        class_nms_3d(torch.zeros(1, 4097, 6, device="cuda"), zeros, zeros.int(), 8, 8, 0.1)
+    zeros = torch.zeros(1, 4, device="cuda")
+    with pytest.raises(ValueError):
+        class_nms_3d(torch.zeros(1, 4, 5, device="cuda"), zeros, zeros.int(), 8, 8, 0.1)
+    with pytest.raises(ValueError):
+        class_nms_3d(torch.zeros(1, 4, 6, device="cuda"), zeros, zeros.int()[:, :3], 8, 8, 0.1)
+    with pytest.raises(ValueError):
+        class_nms_3d(torch.zeros(1, 4, 6, device="cuda"), zeros, zeros, 8, 8, 0.1)             # float class ids
+    with pytest.raises(ValueError):
+        class_nms_3d(torch.zeros(1, 4, 6, device="cuda"), zeros, zeros.int(), 8, 0, 0.1)
+
+
+# ---- refine_detections -------------------------------------------------------------------------------------------------------------
+
+def detection_inputs(b, r, c, seed, n=2000):
+    """zero-padded ROIs in a random cloud, peaked class probabilities (so that some pass 0.7) with two equal maxima in every eighth row,
+    flat ones in the last scene of a batch of two (none passes 0.7 there), deltas, and the two extra probabilities"""
+    g = torch.Generator().manual_seed(seed)
+    pc = (torch.rand(b, n, 3, generator=g) * ROOM).contiguous()
+    rois, _ = RR.nms_boxes(b, r, seed, zero_rows=max(r // 8, 1))
+    logits = torch.randn(b, r, c, generator=g) * 4.0
+    if b > 1:
+        logits[-1] *= 0.05
+    probs = torch.softmax(logits, -1)
+    for k in range(0, r, 8):                                                # two equal maxima: the first of them is the class
+        top = probs[:, k].max(-1).values
+        cols = torch.randperm(c, generator=g)[:2]
+        probs[:, k, cols[0]] = top
+        probs[:, k, cols[1]] = top
+    deltas = torch.randn(b, r, c, 6, generator=g) * 0.5
+    return rois, probs.contiguous(), deltas, pc, torch.rand(b, r, generator=g), torch.rand(b, r, generator=g)
+
+
+@pytest.mark.parametrize("shrink", [False, True])
+@pytest.mark.parametrize("min_confidence", [0.7, 0])
+@pytest.mark.parametrize("b,r,c,max_instances", [(2, 384, 19, 100), (1, 7, 3, 4)])
+def test_refine_detections_batch(b, r, c, max_instances, min_confidence, shrink):
+    from gspn_amd import rpointnet as RP
+    from gspn_amd.detect import classified_boxes
+    cfg = config(max_instances, min_confidence, shrink)
+    rois, probs, deltas, pc, fb, sem = detection_inputs(b, r, c, 7 * r + c)
+    dev = [t.cuda() for t in (rois, probs, deltas, pc, fb, sem)]
+    ids, cls_scores, refined = classified_boxes(*dev[:4], cfg)
+    want_ids, want_scores = DR.first_argmax(probs)
+    tied = (probs == probs.max(-1, keepdim=True).values).sum(-1) > 1
+    assert int(tied.sum()) >= b * ((r + 7) // 8) and (rois.abs().sum(-1) == 0).any()          # equal maxima and zero-padded ROIs are there
+    assert ids.dtype == torch.int32 and torch.equal(ids.cpu(), want_ids) and torch.equal(cls_scores.cpu(), want_scores)
+    std = torch.tensor(cfg.BBOX_STD_DEV)
+    specific = torch.gather(deltas, 2, want_ids.long().reshape(b, r, 1, 1).expand(b, r, 1, 6)).squeeze(2)
+    host = RR.apply_box_delta(rois.reshape(-1, 6), (specific * std).reshape(-1, 6)).reshape(b, r, 6)
+    if not shrink:
+        assert torch.allclose(refined.cpu(), host, rtol=1e-6, atol=1e-7)                       # exp: an ulp between host and device
+    else:
+        assert torch.equal(refined, RP.box_shrink(RP.apply_box_delta(dev[0], dev[2].gather(2, ids.long().reshape(b, r, 1, 1).expand(b, r, 1, 6))
+                                                                     .squeeze(2) * std.cuda()), dev[3]))
+    # from the device's own refined boxes on, everything is exact
+    want = DR.refine_detections(refined.cpu(), ids.cpu(), cls_scores.cpu(), fb, sem, min_confidence, max_instances, cfg.DETECTION_NMS_THRESHOLD)
+    got = RP.refine_detections_batch(*dev, cfg)
+    assert got.shape == (b, max_instances, 8) and got.dtype == torch.float32
+    assert torch.equal(got.cpu(), want)
+    found = (want[..., 6] > 0).sum(1)
+    assert int(found[0]) > 0 and (want[..., 6][want[..., 6] > 0] < c).all()
+    if b > 1 and min_confidence:
+        assert int(found[1]) == 0 and not want[1].any()                                        # the confidence filter removed the whole scene
+    elif b > 1 and not shrink:
+        assert int(found[1]) == max_instances                                                  # more survivors than instances
+    for i in range(b):                                                                         # the per-scene signature
+        one = RP.refine_detections(*(t[i] for t in dev), cfg)
+        assert torch.equal(one, got[i])
+    with pytest.raises(ValueError):
+        RP.refine_detections_batch(dev[0], dev[1], dev[2][:, :, :2], dev[3], dev[4], dev[5], cfg)
+    with pytest.raises(ValueError):
+        RP.refine_detections_batch(dev[0], dev[1], dev[2], dev[3], dev[4][:, :3], dev[5], cfg)
+
+
+# ---- nearest_in_sets ---------------------------------------------------------------------------------------------------------------
+
+FACE_BOX = torch.tensor([2.0, 3.0, 1.0, 1.0, 0.5, 0.25])                    # every bound c -+ s/2 is exact in fp32
+
+
+def nearest_case(b, r, n, p, kind, seed):
+    """kind "replacement": a random cloud, the crop points drawn from it with replacement (exact duplicates, exact zero distances);
+    kind "lattice": cloud and crop points on lattices of 0.25 and 0.5, so that distinct crop points are equally far from a query.
+    Box 0 is FACE_BOX with queries 0-5 exactly on its six faces and 6-11 one ulp outside them (n >= 63); the last box is all zeros
+    (r >= 2), the one before it far from every point (r >= 3), the one before that the whole room (r >= 4)."""
+    g = torch.Generator().manual_seed(seed)
+    if kind == "lattice":
+        query = torch.randint(0, 17, (b, n, 3), generator=g).float() * 0.25
+        sets = torch.randint(0, 9, (b, r, p, 3), generator=g).float() * 0.5
+        rois = torch.cat((torch.randint(2, 15, (b, r, 3), generator=g).float() * 0.25, torch.randint(1, 9, (b, r, 3), generator=g).float() * 0.5), -1)
+    else:
+        query = torch.rand(b, n, 3, generator=g) * ROOM
+        pick = torch.randint(0, n, (b, r, p), generator=g)
+        half = (p + 1) // 2                                                 # the second half repeats draws of the first: duplicates for sure
+        pick[:, :, half:] = torch.gather(pick[:, :, :half], 2, torch.randint(0, half, (b, r, p - half), generator=g))
+        sets = torch.gather(query, 1, pick.reshape(b, r * p, 1).expand(-1, -1, 3)).reshape(b, r, p, 3)
+        rois = torch.cat((torch.rand(b, r, 3, generator=g) * ROOM, torch.rand(b, r, 3, generator=g) * 2.0 + 0.5), -1)
+    if n >= 63:
+        rois[:, 0] = FACE_BOX
+        for a in range(3):
+            for side, sign in enumerate((-1.0, 1.0)):
+                face = FACE_BOX[a] + sign * FACE_BOX[3 + a] / 2
+                query[:, 2 * a + side] = FACE_BOX[:3]
+                query[:, 2 * a + side, a] = face
+                query[:, 6 + 2 * a + side] = FACE_BOX[:3]
+                query[:, 6 + 2 * a + side, a] = torch.nextafter(face, torch.tensor(sign * float("inf")))
+    if r >= 2:
+        rois[:, r - 1] = 0.0
+    if r >= 3:
+        rois[:, r - 2] = torch.tensor([100.0, 100.0, 100.0, 1.0, 1.0, 1.0])
+    if r >= 4:
+        rois[:, r - 3] = torch.cat((ROOM / 2, ROOM))                        # most of the cloud: tiles walked by one lane per query, gated
+    return query.contiguous(), sets.contiguous(), rois.contiguous()
+
+
+def tied_queries(query, sets, limit=256):
+    """how many of the first `limit` queries of scene 0 have their smallest distance to set 0 at more than one position"""
+    q, s = query[0, :limit].numpy(), sets[0, 0].numpy()
+    d = q[:, None, :] - s[None, :, :]
+    dist = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+    return int(((dist == dist.min(1, keepdims=True)).sum(1) > 1).sum())
+
+
+# the last two reach the kernel's tiles of 1024 queries, four per lane (b * r * ceil(n / 1024) >= 512), with a partial tail tile
+NEAREST_SHAPES = [(1, 1, 1, 1), (2, 3, 63, 7), (1, 2, 65, 65), (2, 5, 257, 256), (1, 100, 1000, 1024), (1, 2, 300, 1025), (1, 1, 500, 4096),
+                  (2, 300, 1100, 64), (1, 512, 1030, 33)]
+WIDE_TILE, SHARED_WALK_LIMIT = 1024, 128       # of csrc/detect.hip: a tile with at most 128 inside queries shares each among several lanes
+
+
+@functools.lru_cache(maxsize=None)
+def nearest_reference(b, r, n, p, kind):
+    """the case and its ungated restatement, computed once and shared by the gated and the ungated test"""
+    query, sets, rois = nearest_case(b, r, n, p, kind, 31 * n + p)
+    return query, sets, rois, DR.nearest_in_sets(query, sets)
+
+
+@pytest.mark.parametrize("gated", [False, True])
+@pytest.mark.parametrize("kind", ["replacement", "lattice"])
+@pytest.mark.parametrize("b,r,n,p", NEAREST_SHAPES)
+def test_nearest_in_sets(b, r, n, p, kind, gated):
+    from gspn_amd.rpointnet import nearest_in_sets
+    query, sets, rois, everywhere = nearest_reference(b, r, n, p, kind)
+    inside = torch.stack([RR.inside(rois[i], query[i]) for i in range(b)])
+    want = torch.where(inside, everywhere, -torch.ones_like(everywhere)) if gated else everywhere
+    got = nearest_in_sets(query.cuda(), sets.cuda(), rois.cuda() if gated else None)
+    assert got.dtype == torch.int32 and got.shape == (b, r, n)
+    assert torch.equal(got.cpu(), want)                                                        # the indices, not only the values behind them
+    if gated:
+        assert torch.equal(want, DR.nearest_in_sets(query, sets, rois))
+    # what the case is there for really occurs in it
+    if p >= 7 and n >= 63:
+        assert tied_queries(query, sets) > 0
+    if n >= 63:
+        assert inside[:, 0, :6].all() and not inside[:, 0, 6:12].any()                         # on the six faces: inside; an ulp beyond: outside
+        assert 0 < int(inside[:, 0].sum()) < b * n
+    if r >= 2:
+        zero_box_members = (query == 0).all(-1)                                                # only a query at the origin is inside an all-zero box
+        assert torch.equal(inside[:, r - 1], zero_box_members)
+    if r >= 4:
+        assert float(inside[:, r - 3].float().mean()) > 0.7
+    if b * r * ((n + WIDE_TILE - 1) // WIDE_TILE) >= 512:
+        # four queries per lane: tiles walked by one lane per query (more than 128 inside, full and partial) and tiles that share
+        # queries among lanes both occur, and so does the tile cut short by n
+        assert n % WIDE_TILE != 0
+        per_tile = torch.nn.functional.pad(inside, (0, -n % WIDE_TILE)).reshape(b, r, -1, WIDE_TILE).sum(-1)
+        assert (per_tile > SHARED_WALK_LIMIT).any() and ((per_tile > 0) & (per_tile <= SHARED_WALK_LIMIT)).any() and (per_tile == 0).any()
+        assert (per_tile[:, :, 0] > 256).any()                                                 # compacted entries past a lane's first
+    if r >= 3:
+        assert not inside[:, r - 2].any()
+        if gated:
+            assert (got[:, r - 2] == -1).all()
+
+
+def test_nearest_in_sets_one_set_form_and_limits():
+    from gspn_amd.rpointnet import nearest_in_sets
+    g = torch.Generator().manual_seed(3)
+    for b, n, p in ((2, 257, 256), (1, 1500, 300)):
+        query = torch.rand(b, n, 3, generator=g) * ROOM
+        seeds = torch.gather(query, 1, torch.randint(0, n, (b, p), generator=g).unsqueeze(-1).expand(-1, -1, 3)).contiguous()
+        got = nearest_in_sets(query.cuda(), seeds.cuda())
+        assert got.shape == (b, 1, n)
+        assert torch.equal(got.cpu(), DR.nearest_in_sets(query, seeds.unsqueeze(1)))
+        assert torch.equal(got, nearest_in_sets(query.cuda(), seeds.unsqueeze(1).cuda()))
+    q = torch.zeros(1, 8, 3, device="cuda")
+    with pytest.raises(NotImplementedError):
+        nearest_in_sets(q, torch.zeros(1, 1, 4097, 3, device="cuda"))
+    with pytest.raises(NotImplementedError):
+        nearest_in_sets(torch.zeros(1, 32769, 3, device="cuda"), torch.zeros(1, 1, 4, 3, device="cuda"))
+    with pytest.raises(ValueError):
+        nearest_in_sets(q, torch.zeros(1, 2, 4, 2, device="cuda"))
+    with pytest.raises(ValueError):
+        nearest_in_sets(q, torch.zeros(2, 2, 4, 3, device="cuda"))
+    with pytest.raises(ValueError):
+        nearest_in_sets(q, torch.zeros(1, 2, 4, 3, device="cuda"), torch.zeros(1, 3, 6, device="cuda"))
+    with pytest.raises(ValueError):
+        nearest_in_sets(q.double(), torch.zeros(1, 2, 4, 3, device="cuda"))
+
+
+# ---- select_segmentation, unmold_segmentation --------------------------------------------------------------------------------------
+
+def unmold_case(b, r, n, p, c, seed):
+    """random boxes in a random cloud (the last one all zeros, the one before it empty), p crop points per box drawn with replacement from
+    the points inside it (as mask_selection_gen draws them; the origin for a box without a point), logits as masks"""
+    g = torch.Generator().manual_seed(seed)
+    pc = (torch.rand(b, n, 3, generator=g) * ROOM).contiguous()
+    rois = torch.cat((torch.rand(b, r, 3, generator=g) * ROOM, torch.rand(b, r, 3, generator=g) * 1.5 + 0.5), -1)
+    rois[:, r - 1] = 0.0
+    rois[:, r - 2] = torch.tensor([100.0, 100.0, 100.0, 1.0, 1.0, 1.0])
+    crop = torch.zeros(b, r, p, 3)
+    for i in range(b):
+        members = RR.inside(rois[i], pc[i])
+        for k in range(r):
+            rows = torch.nonzero(members[k])[:, 0]
+            if len(rows):
+                crop[i, k] = pc[i][rows[torch.randint(0, len(rows), (p,), generator=g)]]
+    logits = torch.randn(b, r, p, c, generator=g) * 3.0
+    ids = torch.randint(0, c, (b, r), generator=g).int()
+    return logits.contiguous(), rois.contiguous(), ids, crop.contiguous(), pc
+
+
+@pytest.mark.parametrize("b,r,n,p,c", [(2, 100, 18000, 256, 19), (1, 3, 50, 5, 2)])
+def test_unmold_and_select_segmentation(b, r, n, p, c):
+    from gspn_amd import rpointnet as RP
+    logits, rois, ids, crop, pc = unmold_case(b, r, n, p, c, n + p)
+    inside = torch.stack([RR.inside(rois[i], pc[i]) for i in range(b)])
+    assert inside.any() and not inside[:, r - 2:].any()
+    for masks in (logits, torch.sigmoid(logits)):                                              # negative logits as well as probabilities
+        assert bool((masks < 0).any()) == (masks is logits)
+        sel = RP.select_segmentation(masks.cuda(), ids.cuda())
+        assert sel.shape == (b, r, p) and torch.equal(sel.cpu(), DR.select_segmentation(masks, ids))
+        assert torch.equal(RP.select_segmentation(masks.cuda(), ids.cuda().float()), sel)      # the class column of the detections is float
+        got = RP.unmold_segmentation(masks.cuda(), rois.cuda(), ids.cuda(), crop.cuda(), pc.cuda())
+        want = DR.unmold_segmentation(masks, rois, ids, crop, pc)
+        assert got.shape == (b, r, n) and got.dtype == torch.float32
+        assert torch.equal(got.cpu(), want)                                                    # -0.0 == 0.0
+        assert not got.cpu()[~inside].any() and got.cpu()[inside].abs().min() > 0
+    with pytest.raises(ValueError):
+        RP.unmold_segmentation(logits.cuda(), rois.cuda(), ids.cuda(), crop.cuda()[:, :, :p - 1], pc.cuda())
+    with pytest.raises(ValueError):
+        RP.select_segmentation(logits.cuda(), ids.cuda()[:, :r - 1])
+
+
+# ---- the chain, captured -----------------------------------------------------------------------------------------------------------
+
+def test_output_chain_captured():
+    """refine_detections_batch -> mask_selection_gen_batch -> points_cropping -> select_segmentation -> unmold_segmentation in one graph, on
+    the current stream alone: the capture itself proves that nothing synchronises with the host"""
+    from gspn_amd import rpointnet as RP
+    from gspn_amd.graph import CapturedStep
+    sc = RR.target_scene()
+    cfg = config(100, 0.7, False, 128)
+    b, r, c, m, p = 2, 384, 19, 100, 128
+    pc = sc["pc"].cuda()
+    rois = RR.target_proposals(sc["bbox_ins"], r, 288, 77).cuda()
+
+    def heads(seed):
+        """the zero-padded ROIs are background: as a detection such a row would be trimmed by mask_selection_gen and shift the rest"""
+        g = torch.Generator().manual_seed(seed)
+        probs = torch.softmax(torch.randn(b, r, c, generator=g) * 2.0, -1)
+        probs[rois.cpu().abs().sum(-1) == 0] = torch.nn.functional.one_hot(torch.tensor(0), c).float()
+        return (probs, torch.randn(b, r, c, 6, generator=g) * 0.3, torch.rand(b, r, generator=g), torch.rand(b, r, generator=g),
+                torch.randn(b, m, p, c, generator=g) * 3.0)
+
+    probs, deltas, fb, sem, logits = (t.cuda() for t in heads(1))
+    gen = torch.Generator().manual_seed(9)
+    fea = torch.randn(b, 18000, 8, generator=gen).cuda()
+    cen = (sc["pc"] + 0.1 * torch.randn(b, 18000, 3, generator=gen)).cuda()
+    seed = torch.tensor([5], dtype=torch.int64, device="cuda")
+    st = {}
+
+    def step():
+        with torch.no_grad():
+            det = RP.refine_detections_batch(rois, probs, deltas, pc, fb, sem, cfg)
+            det_rois, idx = RP.mask_selection_gen_batch(det[:, :, :6], pc, m, cfg, False, seed)
+            crop = RP.points_cropping(pc, fea, cen, det_rois, idx, m, p, cfg.NORMALIZE_CROP_REGION)
+            sel = RP.select_segmentation(torch.sigmoid(logits), det[:, :, 6])
+            full = RP.unmold_segmentation(torch.sigmoid(logits), det_rois, det[:, :, 6], crop[3], pc)
+        st["out"] = [det, det_rois, idx, crop[3], sel, full]
+        return full.sum()
+
+    step()
+    out0 = [o.clone() for o in st["out"]]
+    cap = CapturedStep(step)
+    cap.replay()
+    torch.cuda.synchronize()
+    for a, w in zip(st["out"], out0):
+        assert torch.equal(a, w)                                                               # the replay equals the eager run, bit for bit
+    det = out0[0].cpu()
+    found = (det[..., 6] > 0).sum(1)
+    assert (found > 5).all() and (found < m).all()                                             # detections, and rows of zeros behind them
+    assert torch.equal(out0[1], out0[0][:, :, :6])                                             # the zero rows are at the end: nothing moves
+    want = DR.unmold_segmentation(torch.sigmoid(logits).cpu(), det[:, :, :6], det[:, :, 6], out0[3].cpu(), sc["pc"])
+    assert torch.equal(out0[5].cpu(), want) and float(out0[5].abs().max()) > 0
+    # other head outputs, written in place: the replay equals a fresh eager run on them
+    for dst, src in zip((probs, deltas, fb, sem, logits), heads(2)):
+        dst.copy_(src.cuda())
+    cap.replay()
+    torch.cuda.synchronize()
+    replayed = [o.clone() for o in st["out"]]
+    step()
+    torch.cuda.synchronize()
+    assert not torch.equal(replayed[0], out0[0])
+    for a, w in zip(replayed, st["out"]):
+        assert torch.equal(a, w)

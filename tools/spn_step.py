@@ -13,11 +13,16 @@
             the host, a numpy loop, copy back) alternating in one process, box_point_count, detection_target_gen_batch,
             mask_selection_gen_batch, and points_cropping forward + backward with --crop-channels feature channels (forward only at the
             inference shape, which has no backward)
+  detect    the detection output stage (gspn_amd/detect.py) at the inference shape: refine_detections_batch on 384 ROIs per scene,
+            nearest_in_sets with and without the box gate and unmold_segmentation on 100 detections x 1024 crop points, and
+            unmold_segmentation as the reference states it -- the broadcast distance tensor, written in torch and chunked over the ROIs so
+            that it fits -- alternating in one process; median / min / max, the inside share and the distance evaluations per launch
 
 Prints one JSON line per (shape, measurement): median / min milliseconds over --iters timed runs after --warmup runs.
     python tools/spn_step.py --shapes 2x18000,8x32768
     python tools/spn_step.py --shapes 2x18000 --measures spn
     python tools/spn_step.py --shapes 2x18000 --measures roi
+    python tools/spn_step.py --shapes 2x18000 --measures detect
 """
 import argparse
 import json
@@ -68,7 +73,8 @@ def box_shrink_torch(box, pc):
 
 
 def timed_alternating(fns, warmup, iters):
-    """median / min of each of several callables, run in turn (a, b, a, b, ...) so that clocks and neighbours hit them alike"""
+    """median / min / max of each of several callables, run in turn (a, b, a, b, ...) so that clocks and neighbours hit them alike; the
+    spread of the repeats is what a difference between two of them is judged against"""
     for _ in range(warmup):
         for fn in fns.values():
             fn()
@@ -82,7 +88,7 @@ def timed_alternating(fns, warmup, iters):
             b.record()
             b.synchronize()
             ts[k].append(a.elapsed_time(b))
-    return {k: {"median_ms": round(sorted(v)[len(v) // 2], 4), "min_ms": round(min(v), 4)} for k, v in ts.items()}
+    return {k: {"median_ms": round(sorted(v)[len(v) // 2], 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4)} for k, v in ts.items()}
 
 
 def measure_spn(a, shape, b, n, dev):
@@ -205,6 +211,60 @@ def measure_roi(a, shape, b, n, dev):
                           "rois": r, "points_per_roi": p, "crop_channels": a.crop_channels, **res}), flush=True)
 
 
+def unmold_segmentation_torch(masks, rois, class_ids, crop, pc, chunk):
+    """unmold_segmentation as models/model_rpointnet.py:1008-1048 writes it -- the (B, R, N, P) distances, argmin, gather, times the box
+    mask -- `chunk` ROIs at a time (the whole tensor is 3.7 G floats at 2 x 100 x 18000 x 1024)"""
+    b, r, p, _ = masks.shape
+    sel = torch.gather(masks, 3, class_ids.long().reshape(b, r, 1, 1).expand(b, r, p, 1)).squeeze(3)
+    out = torch.empty((b, r, pc.shape[1]), dtype=masks.dtype, device=masks.device)
+    pc_aug = pc.unsqueeze(1)
+    for k in range(0, r, chunk):
+        dist = (pc_aug.unsqueeze(3) - crop[:, k:k + chunk].unsqueeze(2)).square().sum(-1)
+        val = torch.gather(sel[:, k:k + chunk], 2, dist.argmin(3))
+        box = rois[:, k:k + chunk].unsqueeze(2)
+        inside = ((pc_aug >= box[..., :3] - box[..., 3:] / 2) & (pc_aug <= box[..., :3] + box[..., 3:] / 2)).all(-1)
+        out[:, k:k + chunk] = val * inside.float()
+    return out
+
+
+def measure_detect(a, shape, b, n, dev):
+    from gspn_amd import rpointnet as RP
+    cfg = RP.Config(istrain=False)
+    sc = {k: torch.from_numpy(v) for k, v in synth.spn_batch(a.kind, b, n, 100, 512, 19, seed0=7).items()}
+    ext = sc["pc"].amax((0, 1))
+    pc = sc["pc"].to(dev)
+    seed = torch.zeros(1, dtype=torch.int64, device=dev)
+    gen = torch.Generator().manual_seed(384)
+    r, c = cfg.SPN_NMS_MAX_SIZE_INFERENCE, cfg.NUM_CATEGORY
+    rois = roi_proposals(sc["bbox_ins"], ext, r, gen)[0].to(dev)
+    probs = torch.softmax(torch.randn(b, r, c, generator=gen) * 2.5, -1).to(dev)
+    deltas = (torch.randn(b, r, c, 6, generator=gen) * 0.3).to(dev)
+    fb, sem = torch.rand(b, r, generator=gen).to(dev), torch.rand(b, r, generator=gen).to(dev)
+    det = RP.refine_detections_batch(rois, probs, deltas, pc, fb, sem, cfg)
+    res = {"detections": (det[..., 6] > 0).sum(1).tolist()}
+    res.update(timed_alternating({"refine_detections_batch": lambda: RP.refine_detections_batch(rois, probs, deltas, pc, fb, sem, cfg)}, a.warmup, a.iters))
+    # 100 detections per scene: boxes around the instances, 1024 crop points drawn inside each
+    m, p = cfg.DETECTION_MAX_INSTANCES, cfg.NUM_POINT_INS_MASK
+    boxes = roi_proposals(sc["bbox_ins"], ext, m, gen)[0].to(dev)
+    det_rois, idx = RP.mask_selection_gen_batch(boxes, pc, m, cfg, False, seed)
+    crop = RP.points_cropping(pc, pc, pc, det_rois, idx, m, p, cfg.NORMALIZE_CROP_REGION)[3].contiguous()
+    masks = torch.sigmoid(torch.randn(b, m, p, c, generator=gen) * 3.0).to(dev)
+    ids = torch.randint(1, c, (b, m), generator=gen).int().to(dev)
+    gated = RP.nearest_in_sets(pc, crop, det_rois)
+    inside = int((gated >= 0).sum())
+    ours = RP.unmold_segmentation(masks, det_rois, ids, crop, pc)
+    theirs = unmold_segmentation_torch(masks, det_rois, ids, crop, pc, a.unmold_chunk)
+    res.update({"inside_share": round(inside / gated.numel(), 5), "distance_evals_gated": inside * p, "distance_evals_ungated": gated.numel() * p,
+                "unmold_values_differing_from_torch": int((ours != theirs).sum())})       # torch's argmin leaves the choice among equals open
+    res.update(timed_alternating({"nearest_in_sets_gated": lambda: RP.nearest_in_sets(pc, crop, det_rois),
+                             "nearest_in_sets_ungated": lambda: RP.nearest_in_sets(pc, crop),
+                             "unmold_segmentation": lambda: RP.unmold_segmentation(masks, det_rois, ids, crop, pc),
+                             "unmold_segmentation_torch_broadcast": lambda: unmold_segmentation_torch(masks, det_rois, ids, crop, pc, a.unmold_chunk)},
+                            a.warmup, a.iters))
+    print(json.dumps({"shape": shape, "kind": a.kind, "measure": "detect", "rois": r, "detections_per_scene": m, "points_per_roi": p,
+                      "unmold_chunk": a.unmold_chunk, **res}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--measures", default="step,full_fwd,nn,spn")
@@ -214,6 +274,7 @@ def main():
     ap.add_argument("--sem-points", type=int, default=1024)          # model_rpointnet.py:345
     ap.add_argument("--categories", type=int, default=20)
     ap.add_argument("--crop-channels", type=int, default=1024)       # feature channels of points_cropping in --measures roi
+    ap.add_argument("--unmold-chunk", type=int, default=4)          # ROIs per slice of the torch formulation in --measures detect
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--iters", type=int, default=10)
     a = ap.parse_args()
@@ -226,6 +287,8 @@ def main():
             measure_spn(a, shape, b, n, dev)
         if "roi" in measures:
             measure_roi(a, shape, b, n, dev)
+        if "detect" in measures:
+            measure_detect(a, shape, b, n, dev)
         if not set(measures) & {"step", "full_fwd", "nn"}:
             continue
         xyz = torch.from_numpy(synth.batch(a.kind, b, n)).to(dev)

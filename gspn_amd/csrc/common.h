@@ -92,6 +92,21 @@ static inline int gspn_launch_status() {
     return e == hipSuccess ? 0 : (int)e;
 }
 
+// Raises KERNEL's dynamic-LDS limit to `bytes` (above the 48 KiB a launch gets by default), once per (kernel, device): the attribute belongs to
+// that pair, so a flag per process would leave every device after the first without it.  The error of a failed call goes back to the caller
+// (and the call is tried again next time); two threads racing here at worst both make the call.
+template <auto KERNEL>
+static inline hipError_t gspn_dyn_lds_optin(int bytes) {
+    static bool raised[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) dev = -1;
+    const bool slot = dev >= 0 && dev < 64;
+    if (slot && raised[dev]) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess && slot) raised[dev] = true;
+    return e;
+}
+
 // Straggler experiment: a geometry kernel that leaves part of its CU's 160 KiB of LDS free lets a workgroup of the
 // layers' persistent grids land on that CU, where it shares the SIMDs with the geometry waves and finishes last.  GSPN_GEOM_CLAIM_LDS is a
 // bit mask (1 = fps_cell_kernel, 2 = fps_small_kernel, 4 = csr_build_lds_kernel, 8 = fps_resident_kernel) of kernels that then ask for

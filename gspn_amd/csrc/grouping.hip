@@ -432,12 +432,8 @@ static int ball_query_impl(int b, int n, int m, float radius, int nsample, const
     const unsigned char* resolved = nullptr;
     static const int cells_on = getenv("GSPN_BALL_CELLS") ? atoi(getenv("GSPN_BALL_CELLS")) : 1;      // (A/B hook)
     if (ws && cells_on && n >= 8192 && ((uintptr_t)ws % 16) == 0 && nsample <= BQG_CAP) {
-        static bool attr_done = false;
-        if (!attr_done) {
-            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&ball_grid_build_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(int) * BQG_CELLS));
-            if (ea != hipSuccess) return (int)ea;
-            attr_done = true;
-        }
+        const hipError_t ea = gspn_dyn_lds_optin<&ball_grid_build_kernel>((int)(sizeof(int) * BQG_CELLS));
+        if (ea != hipSuccess) return (int)ea;
         const size_t sb = bqg_scene_bytes(n);
         unsigned char* res = reinterpret_cast<unsigned char*>((char*)ws + (size_t)b * sb);
         hipLaunchKernelGGL(ball_grid_build_kernel, dim3(b), dim3(1024), sizeof(int) * BQG_CELLS, (hipStream_t)stream, n, m, radius, nsample, xyz1, (char*)ws, sb, res);
@@ -1079,24 +1075,15 @@ extern "C" int gspn_inverse_lists(int b, int L, int n, const int* idx, int* work
         int* tmp = work + (size_t)b * n;
         const long nwaves = (long)b * n;
         if ((nwaves + 3) / 4 > 0x7FFFFFFFl) return GSPN_ERR_UNSUPPORTED;
-        static bool attr_done = false;
-        if (!attr_done) {
-            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&csr_build_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                (int)(sizeof(int) * CSR_LDS_MAX_N));
-            if (ea != hipSuccess) return (int)ea;
-            attr_done = true;
-        }
+        const hipError_t ea = gspn_dyn_lds_optin<&csr_build_lds_kernel>((int)(sizeof(int) * CSR_LDS_MAX_N));
+        if (ea != hipSuccess) return (int)ea;
         const int G = csr_slices(L, n);
         if (G > 1) {
             int* hist = tmp + (size_t)b * L;
-            static bool attr2_done = false;
-            if (!attr2_done) {
-                hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&csr_hist_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(int) * CSR_LDS_MAX_N));
-                hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&csr_slice_fill_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(int) * CSR_LDS_MAX_N));
-                if (e1 != hipSuccess) return (int)e1;
-                if (e2 != hipSuccess) return (int)e2;
-                attr2_done = true;
-            }
+            const hipError_t e1 = gspn_dyn_lds_optin<&csr_hist_kernel>((int)(sizeof(int) * CSR_LDS_MAX_N));
+            const hipError_t e2 = gspn_dyn_lds_optin<&csr_slice_fill_kernel>((int)(sizeof(int) * CSR_LDS_MAX_N));
+            if (e1 != hipSuccess) return (int)e1;
+            if (e2 != hipSuccess) return (int)e2;
             hipLaunchKernelGGL(csr_hist_kernel, dim3(G, b), dim3(1024), sizeof(int) * (size_t)n, st, L, n, G, idx, hist);
             hipLaunchKernelGGL(csr_slice_scan_kernel, dim3(b), dim3(1024), 0, st, n, G, hist, offsets);
             hipLaunchKernelGGL(csr_slice_fill_kernel, dim3(G, b), dim3(1024), sizeof(int) * (size_t)n, st, L, n, G, idx, hist, tmp);

@@ -775,6 +775,27 @@ __global__ __launch_bounds__(256) void mlp_fwd_stream_kernel(int rows, int cin, 
     }
 }
 
+// LDS plan of a launch of mlp_fwd_stream_kernel: W (BNs columns of QX quads), the constants and two row tiles of 32 * trg rows -- plus, for BWDP, W^T of the
+// ctop top channels and the (arg, V) pairs of a tile's pool groups (ctop = 0: the forward) -- within 53 KB at trg = 4, else 80 KB at trg = 2 (>= 2 workgroups
+// per CU).  trg = 0: the layer does not fit.
+struct StreamPlan { int trg; size_t dyn; };
+static StreamPlan stream_plan(int BNs, int QX, int ctop) {
+    auto bytes = [&](int t) { return 16L * QX * (BNs + 64 * t) + 32L * QX + 4L * ctop * BNs + 2L * t * ctop * 8; };      // (32 * QX = 8 * KP: the constants)
+    int trg = 0;
+    if (bytes(4) <= 53 * 1024 && 4 * ctop <= 512) trg = 4;
+    else if (BNs >= 64 && bytes(2) <= 80 * 1024 && 2 * ctop <= 512) trg = 2;
+    if (trg && (32 * trg * QX) % 64 != 0) trg = 0;
+    if (trg && 32 * trg * QX / 64 > 32) trg = 0;                                      // <= 8 pieces per wave
+    return StreamPlan{trg, trg ? (size_t)bytes(trg) : 0};
+}
+template <int BN, int TRG, bool G, bool BWDP, class... Args>
+static int stream_launch(dim3 grid, size_t dyn, hipStream_t st, Args... args) {
+    const hipError_t e = gspn_dyn_lds_optin<&mlp_fwd_stream_kernel<BN, TRG, G, BWDP>>(96 * 1024);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL((mlp_fwd_stream_kernel<BN, TRG, G, BWDP>), grid, dim3(256), dyn, st, args...);
+    return gspn_launch_status();
+}
+
 static inline unsigned row_grid(long rows, int ytiles, int per_cu) {
     const long ntiles = (rows + TM - 1) / TM;
     long cap = (long)GSPN_PLAN_CUS * per_cu / (ytiles > 0 ? ytiles : 1);
@@ -1167,15 +1188,11 @@ static bool fwd_split_go(long rows, int cin, int cout, const float* X, int ldx, 
     if (!on || rows < 65536 || (rows & 127) || rows >= (1L << 31) || !vec_ok(X, ldx) || !vec_ok(W, cout)) return false;
     if (!((cin == 32 || cin == 64) && (cout == 32 || cout == 64 || cout == 128))) return false;
     const dim3 g(fwd_blocks(rows, cout));
-#define FS_GO(K_, N_, A_, P_) do { const size_t dyn = 3 * N_ * (K_ * 2 + 16) + 2 * K_ * 4 + 8 * N_ * 4;                                              \
-        hipLaunchKernelGGL((fwd_split_kernel<K_, N_, A_, P_>), g, dim3(256), dyn, st, (int)rows, X, ldx, in_scale, in_shift, W, bias, Y, ldy, stats, po); } while (0)
-#define FS_P(K_, N_, A_) do { if (po.vmax) FS_GO(K_, N_, A_, true); else FS_GO(K_, N_, A_, false); } while (0)
-#define FS_A(K_, N_) do { if (in_scale) FS_P(K_, N_, true); else FS_P(K_, N_, false); } while (0)
-#define FS_N(K_) do { if (cout == 32) FS_A(K_, 32); else if (cout == 64) FS_A(K_, 64); else FS_A(K_, 128); } while (0)
-    if (cin == 32) FS_N(32); else FS_N(64);
+#define FS_GO(K_, N_) do { const size_t dyn = 3 * N_ * (K_ * 2 + 16) + 2 * K_ * 4 + 8 * N_ * 4;                                                          \
+        hipLaunchKernelGGL((fwd_split_kernel<K_, N_, decltype(A)::value, decltype(P)::value>), g, dim3(256), dyn, st, (int)rows, X, ldx, in_scale, in_shift, W, bias, Y, ldy, stats, po); } while (0)
+#define FS_N(K_) do { if (cout == 32) FS_GO(K_, 32); else if (cout == 64) FS_GO(K_, 64); else FS_GO(K_, 128); } while (0)
+    with_bool(in_scale != nullptr, [&](auto A) { with_bool(po.vmax != nullptr, [&](auto P) { if (cin == 32) FS_N(32); else FS_N(64); }); });
 #undef FS_N
-#undef FS_A
-#undef FS_P
 #undef FS_GO
     return true;
 }
@@ -1222,12 +1239,8 @@ static int mlp_fwd_impl(long rows, int cin, int cout, const float* X, int ldx, c
                 float* sts = stats ? stats + (size_t)sl * nbs * 2 * cout : nullptr;
                 PoolOut pos = po;
                 if (po.vmax) { pos.vmax = po.vmax + (size_t)sl * (srows / 32) * cout; pos.amax = po.amax + (size_t)sl * (srows / 32) * cout; }
-#define FL_GO(NT_, A_, P_) hipLaunchKernelGGL((fwd_lean_kernel<NT_, A_, P_>), g, dim3(256), dyn, st, (int)srows, cin, cout, Xs, ldx, in_scale, in_shift, W, bias, Ys, ldy, sts, pos)
-#define FL_P(NT_, A_) do { if (po.vmax) FL_GO(NT_, A_, true); else FL_GO(NT_, A_, false); } while (0)
-#define FL_A(NT_) do { if (in_scale) FL_P(NT_, true); else FL_P(NT_, false); } while (0)
-                if (bn == 64) FL_A(2); else FL_A(1);
-#undef FL_A
-#undef FL_P
+#define FL_GO(NT_) hipLaunchKernelGGL((fwd_lean_kernel<NT_, decltype(A)::value, decltype(P)::value>), g, dim3(256), dyn, st, (int)srows, cin, cout, Xs, ldx, in_scale, in_shift, W, bias, Ys, ldy, sts, pos)
+                with_bool(in_scale != nullptr, [&](auto A) { with_bool(po.vmax != nullptr, [&](auto P) { if (bn == 64) FL_GO(2); else FL_GO(1); }); });
 #undef FL_GO
             }
             return gspn_launch_status();
@@ -1238,16 +1251,12 @@ static int mlp_fwd_impl(long rows, int cin, int cout, const float* X, int ldx, c
         const int BNs = cout <= 32 ? 32 : (cout <= 64 ? 64 : 128);
         const int yt = (cout + BNs - 1) / BNs;
         const int QX = (cin + 3) / 4;
-        const long lds4 = 16L * QX * (BNs + 64 * 4), lds2 = 16L * QX * (BNs + 64 * 2);      // bytes with TRG = 4 / 2 (+ 8*KP for the constants)
-        int trg = 0;
-        if (lds4 + 32L * QX <= 53 * 1024) trg = 4;
-        else if (BNs >= 64 && lds2 + 32L * QX <= 80 * 1024) trg = 2;
-        if (trg && (32 * trg * QX) % 64 != 0) trg = 0;
-        if (trg && 32 * trg * QX / 64 > 32) trg = 0;                                      // <= 8 pieces per wave
+        const StreamPlan sp = stream_plan(BNs, QX, 0);
+        const int trg = sp.trg;
         const bool src_ok = gsrc ? true : (vec_ok(X, ldx) && ldx >= 4 && rows * (long)ldx < (1L << 31));
         if (gsrc && !trg) return GSPN_ERR_UNSUPPORTED;
         if (trg && src_ok && rows < (1L << 31) && rows * (long)ldy < (1L << 31) && (gsrc || getenv("GSPN_FWD_NO_STREAM") == nullptr)) {
-            const size_t dyn = (size_t)(trg == 4 ? lds4 : lds2) + 32u * QX;
+            const size_t dyn = sp.dyn;
             const long ntiles = (rows + 32 * trg - 1) / (32 * trg);
             long bpc = (160L * 1024) / (long)(dyn + 2 * trg * BNs * 4 + 512);
             static int bpc_cap = 0;
@@ -1259,43 +1268,24 @@ static int mlp_fwd_impl(long rows, int cin, int cout, const float* X, int ldx, c
             if (gx > ntiles) gx = ntiles;
             if (gx > (long)nparts) gx = nparts;
             if (gx < 1) gx = 1;
-#define FWDS_GO1(BN_, TRG_, G_, GS_)                                                                                                  \
-            do {                                                                                                                       \
-                static bool attr_done = false;                                                                                         \
-                if (!attr_done) {                                                                                                      \
-                    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_fwd_stream_kernel<BN_, TRG_, G_>),           \
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);                         \
-                    if (e != hipSuccess) return (int)e;                                                                                \
-                    attr_done = true;                                                                                                  \
-                }                                                                                                                      \
-                hipLaunchKernelGGL((mlp_fwd_stream_kernel<BN_, TRG_, G_>), dim3((unsigned)gx, yt), dim3(256), dyn, st, (int)rows, cin, cout, X, ldx, \
-                                   in_scale, in_shift, W, bias, Y, ldy, stats, (int)nparts, po, GS_, BwdPool{});                                  \
-                return gspn_launch_status();                                                                                           \
-            } while (0)
-#define FWDS_GO(BN_, TRG_)                                                                                                             \
-            do {                                                                                                                       \
-                if (gsrc) FWDS_GO1(BN_, TRG_, true, *gsrc);                                                                            \
-                else FWDS_GO1(BN_, TRG_, false, GatherSrc{});                                                                          \
-            } while (0)
-            if (BNs == 32 && trg == 4) FWDS_GO(32, 4);
-            if (BNs == 64 && trg == 4) FWDS_GO(64, 4);
-            if (BNs == 64 && trg == 2) FWDS_GO(64, 2);
-            if (BNs == 128 && trg == 4) FWDS_GO(128, 4);
-            if (BNs == 128 && trg == 2) FWDS_GO(128, 2);
+            const dim3 grid((unsigned)gx, yt);
+#define FWDS_GO(BN_, TRG_)                                                                                                                   \
+            (gsrc ? stream_launch<BN_, TRG_, true, false>(grid, dyn, st, (int)rows, cin, cout, X, ldx, in_scale, in_shift, W, bias, Y, ldy, stats, (int)nparts, po, *gsrc, BwdPool{})     \
+                  : stream_launch<BN_, TRG_, false, false>(grid, dyn, st, (int)rows, cin, cout, X, ldx, in_scale, in_shift, W, bias, Y, ldy, stats, (int)nparts, po, GatherSrc{}, BwdPool{}))
+            if (BNs == 32) return FWDS_GO(32, 4);
+            if (BNs == 64) return trg == 4 ? FWDS_GO(64, 4) : FWDS_GO(64, 2);
+            return trg == 4 ? FWDS_GO(128, 4) : FWDS_GO(128, 2);
 #undef FWDS_GO
-#undef FWDS_GO1
         }
     }
     if (gsrc) return GSPN_ERR_UNSUPPORTED;
     const bool v = vec_ok(X, ldx) && vec_ok(W, cout);
-#define FWD_LAUNCH(BN_, V_, YT_)                                                                                                   \
-    hipLaunchKernelGGL((mlp_fwd_kernel<BN_, V_>), dim3(fwd_blocks(rows, cout), YT_), dim3(256), sizeof(float) * 2 * chan_pad(cin), st, rows, cin, cout, X, ldx, \
+#define FWD_LAUNCH(BN_)                                                                                                            \
+    hipLaunchKernelGGL((mlp_fwd_kernel<BN_, decltype(V)::value>), dim3(fwd_blocks(rows, cout), yt), dim3(256), sizeof(float) * 2 * chan_pad(cin), st, rows, cin, cout, X, ldx, \
                        in_scale, in_shift, W, bias, Y, ldy, stats, po)
     const int bn = pick_bn(rows, cout, "GSPN_FWD_FORCE_BN");
     const int yt = (cout + bn - 1) / bn;
-    if (bn == 32) { if (v) FWD_LAUNCH(32, true, yt); else FWD_LAUNCH(32, false, yt); }
-    else if (bn == 64) { if (v) FWD_LAUNCH(64, true, yt); else FWD_LAUNCH(64, false, yt); }
-    else { if (v) FWD_LAUNCH(128, true, yt); else FWD_LAUNCH(128, false, yt); }
+    with_bool(v, [&](auto V) { if (bn == 32) FWD_LAUNCH(32); else if (bn == 64) FWD_LAUNCH(64); else FWD_LAUNCH(128); });
 #undef FWD_LAUNCH
     return gspn_launch_status();
 }
@@ -2627,13 +2617,9 @@ static bool wgrad_lean_try(long rows, int cin, int cout, const gspn_dy_args* a, 
     const dim3 g((unsigned)((p.nch + 7) / 8 * 8 * nbm * nbn));
     const size_t dyn = sizeof(float) * (2 * chan_pad(cin) + 5 * chan_pad(cout));
     const bool act = in_scale != nullptr;
-#define WL_GO(MB_, PK_, A_) hipLaunchKernelGGL((wgrad_lean_kernel<MB_, 2, PK_, A_>), g, dim3(256), dyn, st, (int)rows, cin, cout, *a, X, ldx, in_scale, in_shift, PP, \
-                                               (int)p.rpc, (int)p.nch, nbm, nbn, pool_sh)
-#define WL_A(MB_, PK_) do { if (act) WL_GO(MB_, PK_, true); else WL_GO(MB_, PK_, false); } while (0)
-#define WL_P(MB_) do { if (pooled) WL_A(MB_, 1); else WL_A(MB_, 0); } while (0)
-    if (MBs == 4) WL_P(4); else WL_P(2);
-#undef WL_P
-#undef WL_A
+#define WL_GO(MB_) hipLaunchKernelGGL((wgrad_lean_kernel<MB_, 2, decltype(P)::value ? 1 : 0, decltype(A)::value>), g, dim3(256), dyn, st, (int)rows, cin, cout, *a, X, ldx, \
+                                      in_scale, in_shift, PP, (int)p.rpc, (int)p.nch, nbm, nbn, pool_sh)
+    with_bool(pooled, [&](auto P) { with_bool(act, [&](auto A) { if (MBs == 4) WL_GO(4); else WL_GO(2); }); });
 #undef WL_GO
     return true;
 }
@@ -2651,6 +2637,16 @@ static WgradPlan wgrad_choose(long rows, int cin, int cout, const gspn_dy_args* 
     if (!use_stream) p = wgrad_plan(rows, cin, cout, true);
     *use_stream_out = use_stream;
     return p;
+}
+// the dW job of a layer whose pass A (gspn_mlp_bwd_wgrad(..., dW = NULL, ...) with the same rows/cin/cout/a/X/ldx_in, so that the workspace layout is found
+// again) left its partial tiles and sums in `work`
+static DwJob dw_job_from_work(long rows, int cin, int cout, const gspn_dy_args* a, const float* X, int ldx_in, const float* work, const float* var,
+                              const float* gamma, float eps, int use_bn, int is_training, float* dW) {
+    bool use_stream;
+    const WgradPlan p = wgrad_choose(rows, cin, cout, a, X, ldx_in, &use_stream);
+    const char* wb = reinterpret_cast<const char*>(work);
+    return dw_job(rows, cin, cout, p.nslots, reinterpret_cast<const float*>(wb + ws_off_pp(p.nch, cin, cout)), reinterpret_cast<const double*>(wb),
+                  reinterpret_cast<const float*>(wb + ws_off_g3(cout)), var, gamma, eps, use_bn, is_training, dW);
 }
 
 static int wgrad_impl(long rows, int cin, int cout, const gspn_dy_args* a, const float* X, int ldx,
@@ -2741,10 +2737,9 @@ static int wgrad_impl(long rows, int cin, int cout, const gspn_dy_args* a, const
         // any alignment / pool size: register-staged kernel with scalar loads, 128x128 tiles
         const dim3 grid((unsigned)p.nch, p.nrow, p.ncol);
 #define WG_ARGS rows, cin, cout, *a, X, ldx, in_scale, in_shift, mu, vr, eps, RP, GP, PP, p.rpc, (int)p.nslots
-#define WG_GO(G_, P_) hipLaunchKernelGGL((mlp_bwd_wgrad_kernel<4, 4, 32, false, G_, P_>), grid, dim3(256), sizeof(float) * 2 * chan_pad(cin), st, WG_ARGS)
-        if (tr) { if (pooled) WG_GO(true, true); else WG_GO(true, false); }
-        else    { if (pooled) WG_GO(false, true); else WG_GO(false, false); }
-#undef WG_GO
+        with_bool(tr, [&](auto G) { with_bool(pooled, [&](auto P) {
+            hipLaunchKernelGGL((mlp_bwd_wgrad_kernel<4, 4, 32, false, decltype(G)::value, decltype(P)::value>), grid, dim3(256), sizeof(float) * 2 * chan_pad(cin), st, WG_ARGS);
+        }); });
 #undef WG_ARGS
     }
     const int cmax = cin > cout ? cin : cout;
@@ -3370,13 +3365,7 @@ extern "C" int gspn_mlp_bwd_dw(long rows, int cin, int cout, const gspn_dy_args*
     if (rows <= 0 || cin <= 0 || cout <= 0 || ldx < cin || !a || !a->Y || !work || !dW) return GSPN_ERR_ARG;
     if (use_bn && !var) return GSPN_ERR_ARG;
     if (cin > MAXCH || cout > MAXCH || rows >= (1L << 31)) return GSPN_ERR_UNSUPPORTED;
-    bool use_stream;
-    const WgradPlan p = wgrad_choose(rows, cin, cout, a, X, ldx, &use_stream);
-    const char* wb = reinterpret_cast<const char*>(work);
-    const double* red = reinterpret_cast<const double*>(wb);
-    const float* g3 = reinterpret_cast<const float*>(wb + ws_off_g3(cout));
-    const float* PP = reinterpret_cast<const float*>(wb + ws_off_pp(p.nch, cin, cout));
-    const DwJob j = dw_job(rows, cin, cout, p.nslots, PP, red, g3, var, gamma, eps, use_bn, is_training, dW);
+    const DwJob j = dw_job_from_work(rows, cin, cout, a, X, ldx, work, var, gamma, eps, use_bn, is_training, dW);
     hipLaunchKernelGGL(wgrad_dw_kernel, dim3((unsigned)dw_blocks((long)j.cin * j.cout, j.nslots, 1024)), dim3(1024), 0, (hipStream_t)stream, j);
     return gspn_launch_status();
 }
@@ -3867,14 +3856,10 @@ static bool bwd_lean_try(long rows, int cin, int cout, const gspn_dy_args* a, co
     dj.rowgrid = (int)rg;
     const dim3 g(rg * (unsigned)yt + extra);
     const size_t dyn = sizeof(float) * 5 * chan_pad(cout);
-#define BL_GO(NT_, P_, R_, D_) hipLaunchKernelGGL((bwd_lean_kernel<NT_, P_, R_, D_>), g, dim3(256), dyn, st, (int)rows, cout, *a, W, dX, ldx, col0, dj, rs, (int)rg, pool_sh, col0 + ncols)
-#define BL_D(NT_, P_, R_) do { if (dwj) BL_GO(NT_, P_, R_, true); else BL_GO(NT_, P_, R_, false); } while (0)
-#define BL_R(NT_, P_) do { if (rs.Yp) BL_D(NT_, P_, true); else BL_D(NT_, P_, false); } while (0)
-#define BL_P(NT_) do { if (!pooled) BL_R(NT_, 0); else if (pool_sh == 5) BL_R(NT_, 1); else BL_R(NT_, 2); } while (0)
-    if (bn == 64) BL_P(2); else BL_P(1);
+#define BL_GO(NT_, P_) hipLaunchKernelGGL((bwd_lean_kernel<NT_, P_, decltype(R)::value, decltype(D)::value>), g, dim3(256), dyn, st, (int)rows, cout, *a, W, dX, ldx, col0, dj, rs, (int)rg, pool_sh, col0 + ncols)
+#define BL_P(NT_) do { if (!pooled) BL_GO(NT_, 0); else if (pool_sh == 5) BL_GO(NT_, 1); else BL_GO(NT_, 2); } while (0)
+    with_bool(rs.Yp != nullptr, [&](auto R) { with_bool(dwj != nullptr, [&](auto D) { if (bn == 64) BL_P(2); else BL_P(1); }); });
 #undef BL_P
-#undef BL_R
-#undef BL_D
 #undef BL_GO
     return true;
 }
@@ -4186,20 +4171,16 @@ static int bwd_fused_impl(long rows, int cin, int cout, const gspn_dy_args* a, c
     // in_scale / in_shift ARE the previous layer's forward scale / shift: the epilogue's mask uses the same pair
     RsumArgs rs{Xp, ldxp, in_scale, in_shift, mean_p, var_p, eps_p, part};
     float* PP = work;
-#define BF_GO(CI_, CO_)                                                                                                                   \
-    do {                                                                                                                                   \
-        if (pooled) {                                                                                                                      \
-            if (part) hipLaunchKernelGGL((bwd_fused_kernel<CI_, CO_, true, true>), dim3(g), dim3(256), 0, st, (int)rows, *a, W, Xp, ldxp, in_scale, in_shift, dX, ldx, PP, rs);  \
-            else hipLaunchKernelGGL((bwd_fused_kernel<CI_, CO_, false, true>), dim3(g), dim3(256), 0, st, (int)rows, *a, W, Xp, ldxp, in_scale, in_shift, dX, ldx, PP, rs); \
-        } else if (part) hipLaunchKernelGGL((bwd_fused_kernel<CI_, CO_, true, false>), dim3(g), dim3(256), 0, st, (int)rows, *a, W, Xp, ldxp, in_scale, in_shift, dX, ldx, PP, rs);  \
-        else hipLaunchKernelGGL((bwd_fused_kernel<CI_, CO_, false, false>), dim3(g), dim3(256), 0, st, (int)rows, *a, W, Xp, ldxp, in_scale, in_shift, dX, ldx, PP, rs); \
-    } while (0)
-    if (cin == 32 && cout == 32) BF_GO(1, 1);
-    else if (cin == 32 && cout == 64) BF_GO(1, 2);
-    else if (cin == 32) BF_GO(1, 4);
-    else if (cout == 32) BF_GO(2, 1);
-    else if (cout == 64) BF_GO(2, 2);
-    else BF_GO(2, 4);
+#define BF_GO(CI_, CO_) \
+    hipLaunchKernelGGL((bwd_fused_kernel<CI_, CO_, decltype(R)::value, decltype(P)::value>), dim3(g), dim3(256), 0, st, (int)rows, *a, W, Xp, ldxp, in_scale, in_shift, dX, ldx, PP, rs)
+    with_bool(part != nullptr, [&](auto R) { with_bool(pooled, [&](auto P) {
+        if (cin == 32 && cout == 32) BF_GO(1, 1);
+        else if (cin == 32 && cout == 64) BF_GO(1, 2);
+        else if (cin == 32) BF_GO(1, 4);
+        else if (cout == 32) BF_GO(2, 1);
+        else if (cout == 64) BF_GO(2, 2);
+        else BF_GO(2, 4);
+    }); });
 #undef BF_GO
     if (nparts_out) *nparts_out = (int)g;
     DwJob j = dw_job(rows, cin, cout, (long)g, PP, nullptr, nullptr, nullptr, nullptr, 0.f, 0, 0, dW);
@@ -4241,23 +4222,18 @@ static int bwd_data_launch(long rows, int cin, int cout, const gspn_dy_args* a, 
     // the fourth quarter of the workgroups fills the slots the first finishers free.  GSPN_BWD_BPC overrides (tuning hook).
     const int bpc_narrow = bwd_bpc_narrow();
     if (bwd_lean_try(rows, cin, cout, a, W, col0, ncols, dX, ldx, dwj, st, rs, nparts_out, none)) return gspn_launch_status();
-#define BD_GO(BN_, V_, P_, YT_)                                                                                                       \
-    do {                                                                                                                               \
-        const unsigned rg = row_grid(rows, YT_, BN_ >= 128 ? 2 : bpc_narrow);                                                          \
-        const dim3 g(dwj ? rg * (unsigned)(YT_) + extra : rg, dwj ? 1 : YT_);                                                          \
-        if (nparts_out) *nparts_out = (int)rg;                                                                                         \
-        DwJob dj = dwj ? *dwj : none;                                                                                                  \
-        dj.rowgrid = (int)rg;                                                                                                          \
-        if (dwj) hipLaunchKernelGGL((mlp_bwd_data_kernel<BN_, V_, P_, true>), g, dim3(256), sizeof(float) * 5 * chan_pad(cout), st, rows, cend, cout, *a, W, dX, ldx, col0, dj, rs);   \
-        else     hipLaunchKernelGGL((mlp_bwd_data_kernel<BN_, V_, P_, false>), g, dim3(256), sizeof(float) * 5 * chan_pad(cout), st, rows, cend, cout, *a, W, dX, ldx, col0, none, rs);  \
-    } while (0)
-#define BD_LAUNCH(BN_, V_, YT_) do { if (pooled) BD_GO(BN_, V_, true, YT_); else BD_GO(BN_, V_, false, YT_); } while (0)
     const int bn = pick_bn(rows, ncols, "GSPN_BWD_FORCE_BN");
     const int yt = (ncols + bn - 1) / bn;
-    if (bn == 32) { if (v) BD_LAUNCH(32, true, yt); else BD_LAUNCH(32, false, yt); }
-    else if (bn == 64) { if (v) BD_LAUNCH(64, true, yt); else BD_LAUNCH(64, false, yt); }
-    else { if (v) BD_LAUNCH(128, true, yt); else BD_LAUNCH(128, false, yt); }
-#undef BD_LAUNCH
+    const unsigned rg = row_grid(rows, yt, bn >= 128 ? 2 : bpc_narrow);
+    const dim3 g(dwj ? rg * (unsigned)yt + extra : rg, dwj ? 1 : yt);
+    if (nparts_out) *nparts_out = (int)rg;
+    DwJob dj = none;                                      // (with no job to carry, the kernel is handed the empty one as it is)
+    if (dwj) { dj = *dwj; dj.rowgrid = (int)rg; }
+#define BD_GO(BN_) hipLaunchKernelGGL((mlp_bwd_data_kernel<BN_, decltype(V)::value, decltype(P)::value, decltype(D)::value>), g, dim3(256), sizeof(float) * 5 * chan_pad(cout), st, \
+                                      rows, cend, cout, *a, W, dX, ldx, col0, dj, rs)
+    with_bool(v, [&](auto V) { with_bool(pooled, [&](auto P) { with_bool(dwj != nullptr, [&](auto D) {
+        if (bn == 32) BD_GO(32); else if (bn == 64) BD_GO(64); else BD_GO(128);
+    }); }); });
 #undef BD_GO
     return gspn_launch_status();
 }
@@ -4287,11 +4263,7 @@ extern "C" int gspn_mlp_bwd_data_dw(long rows, int cin, int cout, const gspn_dy_
     const int rc = bwd_data_check(rows, cin, cout, a, col0, ncols, ldx);
     if (rc) return rc;
     if (rows <= 0 || !work || !dW || ldx_in < cin || (use_bn && !var)) return GSPN_ERR_ARG;
-    bool use_stream;
-    const WgradPlan p = wgrad_choose(rows, cin, cout, a, X, ldx_in, &use_stream);
-    const char* wb = reinterpret_cast<const char*>(work);
-    const DwJob j = dw_job(rows, cin, cout, p.nslots, reinterpret_cast<const float*>(wb + ws_off_pp(p.nch, cin, cout)), reinterpret_cast<const double*>(wb),
-                           reinterpret_cast<const float*>(wb + ws_off_g3(cout)), var, gamma, eps, use_bn, is_training, dW);
+    const DwJob j = dw_job_from_work(rows, cin, cout, a, X, ldx_in, work, var, gamma, eps, use_bn, is_training, dW);
     return bwd_data_launch(rows, cin, cout, a, W, col0, ncols, dX, ldx, &j, (hipStream_t)stream);
 }
 // gspn_mlp_bwd_data_dw with a second, plain reduction riding along: dW2 (cin2, cout) = the sum of nslots2 partial tiles at part2
@@ -4303,11 +4275,7 @@ extern "C" int gspn_mlp_bwd_data_dw2(long rows, int cin, int cout, const gspn_dy
     if (rc) return rc;
     if (rows <= 0 || !work || !dW || ldx_in < cin || (use_bn && !var)) return GSPN_ERR_ARG;
     if (cin2 < 0 || nslots2 < 0 || (cin2 > 0 && (!part2 || !dW2 || nslots2 <= 0))) return GSPN_ERR_ARG;
-    bool use_stream;
-    const WgradPlan p = wgrad_choose(rows, cin, cout, a, X, ldx_in, &use_stream);
-    const char* wb = reinterpret_cast<const char*>(work);
-    DwJob j = dw_job(rows, cin, cout, p.nslots, reinterpret_cast<const float*>(wb + ws_off_pp(p.nch, cin, cout)), reinterpret_cast<const double*>(wb),
-                     reinterpret_cast<const float*>(wb + ws_off_g3(cout)), var, gamma, eps, use_bn, is_training, dW);
+    DwJob j = dw_job_from_work(rows, cin, cout, a, X, ldx_in, work, var, gamma, eps, use_bn, is_training, dW);
     if (cin2 > 0) {
         j.PP2 = part2; j.dW2 = dW2; j.cin2 = cin2; j.nslots2 = nslots2;
         j.nblk2 = (int)dw_blocks((long)cin2 * cout, nslots2, 256);
@@ -4370,24 +4338,14 @@ extern "C" int gspn_mlp_bwd_data_pooltop(long rows, int cin, int ctop, const gsp
         return GSPN_ERR_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
     const int BNs = cin <= 32 ? 32 : 64;
-    const int QX = cin / 4;
-    const long extra4 = 4L * ctop * BNs + 2L * 4 * ctop * 8, extra2 = 4L * ctop * BNs + 2L * 2 * ctop * 8;
-    const long lds4 = 16L * QX * (BNs + 64 * 4) + 32L * QX + extra4, lds2 = 16L * QX * (BNs + 64 * 2) + 32L * QX + extra2;
-    int trg = 0;
-    if (lds4 <= 53 * 1024 && 4 * ctop <= 512) trg = 4;
-    else if (BNs >= 64 && lds2 <= 80 * 1024 && 2 * ctop <= 512) trg = 2;
-    if (trg && (32 * trg * QX) % 64 != 0) trg = 0;
-    if (trg && 32 * trg * QX / 64 > 32) trg = 0;
+    const StreamPlan sp = stream_plan(BNs, cin / 4, ctop);
+    const int trg = sp.trg;
     if (!trg) return GSPN_ERR_UNSUPPORTED;
     float* M = scratch;
     float* cvec = M + (size_t)cin * cin;
-    bool use_stream;
-    const WgradPlan p = wgrad_choose(rows, cin, ctop, a, X, ldx_in, &use_stream);
-    const char* wb = reinterpret_cast<const char*>(work);
-    const DwJob j = dw_job(rows, cin, ctop, p.nslots, reinterpret_cast<const float*>(wb + ws_off_pp(p.nch, cin, ctop)), reinterpret_cast<const double*>(wb),
-                           reinterpret_cast<const float*>(wb + ws_off_g3(ctop)), var, gamma, eps, use_bn, is_training, dW);
+    const DwJob j = dw_job_from_work(rows, cin, ctop, a, X, ldx_in, work, var, gamma, eps, use_bn, is_training, dW);
     hipLaunchKernelGGL(pooltop_prep_kernel, dim3((unsigned)(cin + j.nblk)), dim3(256), 0, st, cin, ctop, W, bias, a->cB, a->cC, M, cvec, j);
-    const size_t dyn = (size_t)(trg == 4 ? lds4 : lds2);
+    const size_t dyn = sp.dyn;
     const long ntiles = (rows + 32 * trg - 1) / (32 * trg);
     long bpc = (160L * 1024) / (long)(dyn + 2 * trg * BNs * 4 + 512);
     if (bpc > 4) bpc = 4;
@@ -4396,23 +4354,12 @@ extern "C" int gspn_mlp_bwd_data_pooltop(long rows, int cin, int ctop, const gsp
     if (gx > ntiles) gx = ntiles;
     const BwdPool bp{a->pool_arg, a->dPool, pooled, a->cA, W, ctop, mean_p, var_p, eps_p};
 #define BWDP_GO(BN_, TRG_)                                                                                                             \
-    do {                                                                                                                               \
-        static bool attr_done = false;                                                                                                 \
-        if (!attr_done) {                                                                                                              \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_fwd_stream_kernel<BN_, TRG_, false, true>),          \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);                                 \
-            if (e != hipSuccess) return (int)e;                                                                                        \
-            attr_done = true;                                                                                                          \
-        }                                                                                                                              \
-        hipLaunchKernelGGL((mlp_fwd_stream_kernel<BN_, TRG_, false, true>), dim3((unsigned)gx, 1), dim3(256), dyn, st, (int)rows, cin, cin, Yp, ldyp, \
-                           scale_p, shift_p, M, cvec, dX, ldx, part, (int)gx, PoolOut{nullptr, nullptr}, GatherSrc{}, bp);              \
-    } while (0)
-    if (BNs == 32 && trg == 4) BWDP_GO(32, 4);
-    else if (BNs == 64 && trg == 4) BWDP_GO(64, 4);
-    else BWDP_GO(64, 2);
+    stream_launch<BN_, TRG_, false, true>(dim3((unsigned)gx, 1), dyn, st, (int)rows, cin, cin, Yp, ldyp, scale_p, shift_p, M, cvec, dX, ldx, part, (int)gx, \
+                                          PoolOut{nullptr, nullptr}, GatherSrc{}, bp)
+    const int rc = (BNs == 32 && trg == 4) ? BWDP_GO(32, 4) : ((BNs == 64 && trg == 4) ? BWDP_GO(64, 4) : BWDP_GO(64, 2));
 #undef BWDP_GO
     *nparts_out = (int)gx;
-    return gspn_launch_status();
+    return rc;
 }
 // Pass B with both options: the fused dW reduction of gspn_mlp_bwd_data_dw (work != NULL) and the previous layer's BN reductions in the
 // epilogue (part != NULL: Yp (rows, ldyp) = that layer's pre-BN output = this layer's input before activation; scale_p/shift_p its
@@ -4430,11 +4377,7 @@ extern "C" int gspn_mlp_bwd_data_ex(long rows, int cin, int cout, const gspn_dy_
     const DwJob* jp = nullptr;
     if (work) {
         if (!dW || (X && ldx_in < cin) || (use_bn && !var)) return GSPN_ERR_ARG;
-        bool use_stream;
-        const WgradPlan p = wgrad_choose(rows, cin, cout, a, X, ldx_in, &use_stream);
-        const char* wb = reinterpret_cast<const char*>(work);
-        j = dw_job(rows, cin, cout, p.nslots, reinterpret_cast<const float*>(wb + ws_off_pp(p.nch, cin, cout)), reinterpret_cast<const double*>(wb),
-                   reinterpret_cast<const float*>(wb + ws_off_g3(cout)), var, gamma, eps, use_bn, is_training, dW);
+        j = dw_job_from_work(rows, cin, cout, a, X, ldx_in, work, var, gamma, eps, use_bn, is_training, dW);
         jp = &j;
     }
     RsumArgs rs{nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0.f, nullptr};

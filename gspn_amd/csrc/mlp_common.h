@@ -3,6 +3,7 @@
 #include "common.h"
 #include <stdlib.h>
 #include <stdint.h>
+#include <type_traits>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -25,6 +26,10 @@ struct PoolOut { float* vmax; int* amax; };
 
 static inline int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 static inline bool vec_ok(const void* p, int ld) { return (ld % 4 == 0) && (((uintptr_t)p) % 16 == 0); }
+
+// f(std::true_type{}) or f(std::false_type{}): a runtime bool becomes a template argument (decltype(B)::value inside a generic lambda)
+// without an if / else ladder of launches; both branches are instantiated, like the rungs of a ladder
+template <class F> static inline void with_bool(bool c, F&& f) { if (c) f(std::true_type{}); else f(std::false_type{}); }
 
 // rows at or below which the FORWARD of a layer takes the split-K kernel of mlp_short.hip.  Measured (tools/r05_short_ab.sh, graph-timed,
 // us, round-4 kernel -> split-K): 4096 x 256 -> 128 9.9 -> 7.1, 4096 x 128 -> 128 6.0 -> 4.4, 4096 x 384 -> 256 13.4 -> 13.3; at 16384 rows

@@ -217,16 +217,10 @@ static bool fwd_short_launch(dim3 g, hipStream_t st, int rows, int cin, int cout
                              const float* W, const float* bias, float* Y, int ldy, float* stats, PoolOut po) {
     constexpr size_t dyn = sizeof(float) * (4 * MT * NT * 16 * 64 + 32 * MT * (4 * KW + 4) + 2 * 4 * KW);
     if constexpr (dyn > 48 * 1024) {
-        // the attribute belongs to (function, DEVICE): one flag per device, not per process; a failure is reported, not swallowed
-        static bool done[64] = {};
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) dev = -1;
-        if (dev < 0 || dev >= 64 || !done[dev]) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&fwd_short_kernel<KW, MT, NT, ACT, POOL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess) {
-                (void)hipGetLastError();
-                return false;
-            }
-            if (dev >= 0 && dev < 64) done[dev] = true;
+        // (once per device, common.h -- ADVICE r05); a failure is reported, not swallowed
+        if (gspn_dyn_lds_optin<&fwd_short_kernel<KW, MT, NT, ACT, POOL>>((int)dyn) != hipSuccess) {
+            (void)hipGetLastError();
+            return false;
         }
     }
     hipLaunchKernelGGL((fwd_short_kernel<KW, MT, NT, ACT, POOL>), g, dim3(256), dyn, st, rows, cin, cout, X, ldx, in_scale, in_shift, W, bias, Y, ldy, stats, po);
@@ -263,24 +257,22 @@ bool gspn_fwd_short_go(long rows, int cin, int cout, const float* X, int ldx, co
     const dim3 g(nparts, cout / (32 * nt));
     const int irows = (int)rows;
     bool ok = true;
-#define FS_GO(KW_, MT_, NT_, A_, P_) ok = fwd_short_launch<KW_, MT_, NT_, A_, P_>(g, st, irows, cin, cout, X, ldx, in_scale, in_shift, W, bias, Y, ldy, stats, po)
-#define FS_P(KW_, MT_, NT_, A_) do { if (po.vmax) FS_GO(KW_, MT_, NT_, A_, true); else FS_GO(KW_, MT_, NT_, A_, false); } while (0)
-#define FS_A(KW_, MT_, NT_) do { if (in_scale) FS_P(KW_, MT_, NT_, true); else FS_P(KW_, MT_, NT_, false); } while (0)
-#define FS_T2(KW_) do { if (nt == 1) FS_A(KW_, 1, 1); else FS_A(KW_, 1, 2); } while (0)
-#define FS_T4(KW_) do { if (mt == 2 && nt == 2) FS_A(KW_, 2, 2); else if (mt == 2) FS_A(KW_, 2, 1); else FS_T2(KW_); } while (0)
-#define FS_T5(KW_) do { if (nt == 4) FS_A(KW_, 1, 4); else FS_T4(KW_); } while (0)
-    switch (kw) {
-        case 16: FS_T5(16); break;
-        case 32: FS_T5(32); break;
-        case 48: FS_T4(48); break;
-        case 64: FS_T2(64); break;
-        default: FS_T2(96); break;
-    }
+#define FS_GO(KW_, MT_, NT_) ok = fwd_short_launch<KW_, MT_, NT_, decltype(A)::value, decltype(P)::value>(g, st, irows, cin, cout, X, ldx, in_scale, in_shift, W, bias, Y, ldy, stats, po)
+#define FS_T2(KW_) do { if (nt == 1) FS_GO(KW_, 1, 1); else FS_GO(KW_, 1, 2); } while (0)
+#define FS_T4(KW_) do { if (mt == 2 && nt == 2) FS_GO(KW_, 2, 2); else if (mt == 2) FS_GO(KW_, 2, 1); else FS_T2(KW_); } while (0)
+#define FS_T5(KW_) do { if (nt == 4) FS_GO(KW_, 1, 4); else FS_T4(KW_); } while (0)
+    with_bool(in_scale != nullptr, [&](auto A) { with_bool(po.vmax != nullptr, [&](auto P) {
+        switch (kw) {
+            case 16: FS_T5(16); break;
+            case 32: FS_T5(32); break;
+            case 48: FS_T4(48); break;
+            case 64: FS_T2(64); break;
+            default: FS_T2(96); break;
+        }
+    }); });
 #undef FS_T5
 #undef FS_T4
 #undef FS_T2
-#undef FS_A
-#undef FS_P
 #undef FS_GO
     return ok;
 }

@@ -131,6 +131,8 @@ SIGNATURES = {
     "gspn_crop_gather_grad": [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
     "gspn_class_nms3d": [_I, _I, _I, _I, _F, _P, _P, _P, _P, _P],
     "gspn_nearest_in_sets": [_I, _I, _I, _I, _P, _P, _P, _P, _P],
+    "gspn_crop_linear_fwd": [_I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P],
+    "gspn_crop_linear_bwd_side": [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P],
 }
 
 # entry points that do not return an int status: symbol -> (argtypes, restype)
@@ -156,9 +158,10 @@ SPECIAL = {
     "gspn_nmdistance_grad_ws_bytes": ([_I, _I, _I], _L),
     "gspn_deconv_bwd_kernel_work_bytes": ([_I, _I, _I, _I, _I, _I, _I, _I, _I], _L),
     "gspn_crop_gather_grad_part_floats": ([_I, _I, _I], _L),
+    "gspn_crop_linear_part_floats": ([_I, _I, _I, _I], _L),
 }
 
-ABI_VERSION = 14        # == GSPN_ABI_VERSION of include/gspn_hip.h this binding was written against
+ABI_VERSION = 15        # == GSPN_ABI_VERSION of include/gspn_hip.h this binding was written against
 
 _lib = None
 

@@ -227,6 +227,21 @@ class _Lists:
         return self.lists
 
 
+def _crop_gather_grad(lists, grad_out):
+    """grad_out (B, R, P, c) gathered through lists.idx (B, R, P) -> (B, n, c): the sum over the positions that name each point, in the
+    fixed order of gspn_crop_gather_grad"""
+    b, m, ns, c = grad_out.shape
+    grad_out = grad_out.contiguous()
+    order, offsets = lists.get()
+    n, idx = lists.n, lists.idx
+    g = torch.empty((b, n, c), dtype=torch.float32, device=grad_out.device)
+    part = torch.empty(int(L.lib().gspn_crop_gather_grad_part_floats(b, m * ns, c)), dtype=torch.float32, device=grad_out.device)
+    with torch.cuda.device(grad_out.device):
+        L.check(L.lib().gspn_crop_gather_grad(b, n, c, m * ns, L.ptr(idx), L.ptr(order), L.ptr(offsets), L.ptr(grad_out), L.ptr(part), L.ptr(g),
+                                              L.stream()), "points_cropping(grad)")
+    return g
+
+
 class _CropGather(torch.autograd.Function):
     """group_point whose gradient is gspn_crop_gather_grad at EVERY width: a fixed summation order (tf_grouping.group_point takes the atomic
     scatter-add below 16 channels), and the list of point 0 -- which the rows of zeros of negative and padding ROIs all name -- spread
@@ -239,16 +254,7 @@ class _CropGather(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        b, m, ns, c = grad_out.shape
-        grad_out = grad_out.contiguous()
-        order, offsets = ctx.lists.get()
-        n, idx = ctx.lists.n, ctx.lists.idx
-        g = torch.empty((b, n, c), dtype=torch.float32, device=grad_out.device)
-        part = torch.empty(int(L.lib().gspn_crop_gather_grad_part_floats(b, m * ns, c)), dtype=torch.float32, device=grad_out.device)
-        with torch.cuda.device(grad_out.device):
-            L.check(L.lib().gspn_crop_gather_grad(b, n, c, m * ns, L.ptr(idx), L.ptr(order), L.ptr(offsets), L.ptr(grad_out), L.ptr(part), L.ptr(g),
-                                                  L.stream()), "points_cropping(grad)")
-        return g, None, None
+        return _crop_gather_grad(ctx.lists, grad_out), None, None
 
 
 def points_cropping(pc, pc_fea, pc_center, rois, masks_selection_idx, num_rois, num_point_per_roi, normalize_crop_region=True):

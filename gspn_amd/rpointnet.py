@@ -7,13 +7,17 @@ prepared outside, rpointnet + get_loss + backward capture in a graph.CapturedSte
 detection_target_gen (:647), mask_selection_gen (:749), points_cropping (:785), box_refinement (:553), apply_box_delta (:570) -- lives in
 roi.py and is re-exported here under the reference's names, and so is the detection output stage behind the heads -- refine_detections
 (:818), select_segmentation (:986), unmold_segmentation (:1008), with the extensions class_nms_3d and nearest_in_sets -- which lives in
-detect.py.  What needs the detection heads themselves (the FPN layers, classification_head, segmentation_head, their losses, inference)
-is not implemented and raises NotImplementedError."""
+detect.py.  The heads between the two -- the FPN layers (fpn_features, :1100-1104), classification_head (:915), segmentation_head (:946),
+crop_linear (their first layer fused with the crop) and the R-PointNet losses (:1251-1323, get_rpointnet_loss) -- live in heads.py and are
+re-exported here as callable parts.  The two drivers do not call them yet: rpointnet with mode='inference' or 'RPOINTNET' in TRAIN_MODULE,
+and get_loss with 'RPOINTNET' in TRAIN_MODULE, raise NotImplementedError."""
 import torch
 
 from . import _lib as L
 from .detect import (class_nms_3d, nearest_in_sets, refine_detections, refine_detections_batch, select_segmentation,
                      unmold_segmentation)
+from .heads import (classification_head, crop_linear, fpn_features, get_rpointnet_bbox_loss, get_rpointnet_class_loss, get_rpointnet_loss,
+                    get_rpointnet_mask_loss, segmentation_head)
 from .proposal_head import chamfer_recons_loss
 from .roi import (apply_box_delta, box_point_count, box_refinement, detection_target_gen, detection_target_gen_batch, mask_selection_gen,
                   mask_selection_gen_batch, nms_3d, points_cropping, sample_points_in_boxes)
@@ -23,7 +27,9 @@ from .spn_boxes import box_shrink, points_bbox, spn_target_gen_batch
 __all__ = ["Config", "box_shrink", "spn_target_gen", "spn_target_gen_batch", "gather_selection", "smooth_l1_loss", "get_spn_class_loss",
            "seg_label_per_group", "rpointnet", "get_loss", "nms_3d", "box_point_count", "sample_points_in_boxes", "detection_target_gen",
            "detection_target_gen_batch", "mask_selection_gen", "mask_selection_gen_batch", "points_cropping", "box_refinement", "apply_box_delta",
-           "class_nms_3d", "refine_detections", "refine_detections_batch", "select_segmentation", "nearest_in_sets", "unmold_segmentation"]
+           "class_nms_3d", "refine_detections", "refine_detections_batch", "select_segmentation", "nearest_in_sets", "unmold_segmentation",
+           "crop_linear", "classification_head", "segmentation_head", "fpn_features", "get_rpointnet_class_loss", "get_rpointnet_bbox_loss",
+           "get_rpointnet_mask_loss", "get_rpointnet_loss"]
 
 
 class Config(object):
@@ -110,14 +116,16 @@ def rpointnet(pc, color, pc_ins, group_label, group_indicator, seg_label, bbox_i
               geometry=None, noise=None, valid_idx=None):
     """:1051.  pc, color (B, N, 3), pc_ins (B, NUM_GROUP, NUM_POINT_INS, 3), group_label, seg_label (B, N), group_indicator (B, NUM_GROUP),
     bbox_ins (B, NUM_GROUP, 6) -> end_points of shape_proposal_net plus group_label, seg_label, seg_label_per_group, bbox_ins.
-    geometry / noise / valid_idx (extensions) are handed on to shape_proposal_net."""
+    geometry / noise / valid_idx (extensions) are handed on to shape_proposal_net.
+    mode='inference' and 'RPOINTNET' in TRAIN_MODULE raise NotImplementedError: the stages they need (the ROI stage, fpn_features, the two
+    heads, refine_detections) exist as parts of this module, but this driver does not chain them yet."""
     assert mode in ['training', 'inference']
     if mode == 'inference':
-        raise NotImplementedError("rpointnet: mode='inference' needs the FPN layers, classification_head, segmentation_head and "
-                                  "refine_detections, which are not implemented")
+        raise NotImplementedError("rpointnet: mode='inference' is not wired into this driver (fpn_features, classification_head, "
+                                  "segmentation_head and refine_detections are callable on their own)")
     if 'RPOINTNET' in config.TRAIN_MODULE:
-        raise NotImplementedError("rpointnet: 'RPOINTNET' in TRAIN_MODULE needs the FPN layers, classification_head and segmentation_head, "
-                                  "which are not implemented")
+        raise NotImplementedError("rpointnet: 'RPOINTNET' in TRAIN_MODULE is not wired into this driver (fpn_features, classification_head "
+                                  "and segmentation_head are callable on their own)")
     if 'SPN' not in config.TRAIN_MODULE:
         raise NotImplementedError("rpointnet: TRAIN_MODULE must be ['SPN']")
     if not config.USE_COLOR:
@@ -136,9 +144,10 @@ def rpointnet(pc, color, pc_ins, group_label, group_indicator, seg_label, bbox_i
 
 def get_loss(end_points, config, alpha, smpw, mode='training'):
     """:1325, the five SPN terms (:1328-1381, :1395).  smpw (B, N): per-point weights of the semantic loss.  Returns (loss, end_points);
-    end_points gains spn_match, sem_labels, spn_class_loss, recons_loss, shift_loss, sem_loss, kl_loss, loss."""
+    end_points gains spn_match, sem_labels, spn_class_loss, recons_loss, shift_loss, sem_loss, kl_loss, loss.
+    The R-PointNet terms (:1383-1392) are get_rpointnet_loss, which this driver does not add yet: 'RPOINTNET' in TRAIN_MODULE raises."""
     if 'RPOINTNET' in config.TRAIN_MODULE or 'SPN' not in config.TRAIN_MODULE:
-        raise NotImplementedError("get_loss: only TRAIN_MODULE == ['SPN'] is implemented (no R-PointNet class / bbox / mask losses)")
+        raise NotImplementedError("get_loss: only TRAIN_MODULE == ['SPN'] is implemented (the R-PointNet terms are get_rpointnet_loss)")
     nsmp_ins = config.NUM_POINT_INS
     pc_ins_centered_seed = L.need(end_points['pc_ins_centered_seed'], torch.float32, 4, "pc_ins_centered_seed")
     bbox_size = points_bbox(pc_ins_centered_seed)[:, :, 3:].unsqueeze(2)                                  # (B, nsmp, 1, 3)

@@ -41,8 +41,9 @@ extern "C" {
  *  11: gspn_deconv_fwd / gspn_deconv_bwd_input / gspn_deconv_bwd_kernel (+ _work_bytes).
  *  12: gspn_box_shrink / gspn_points_bbox / gspn_spn_target_gen.
  *  13: gspn_nms3d / gspn_box_point_count / gspn_sample_points_in_boxes / gspn_detection_target_select / gspn_crop_gather_grad.
- *  14: gspn_class_nms3d / gspn_nearest_in_sets. */
-#define GSPN_ABI_VERSION 14
+ *  14: gspn_class_nms3d / gspn_nearest_in_sets.
+ *  15: gspn_crop_linear_fwd / gspn_crop_linear_bwd_side (+ _part_floats). */
+#define GSPN_ABI_VERSION 15
 int gspn_dist_policy(void);
 int gspn_abi_version(void);
 
@@ -338,6 +339,30 @@ int gspn_class_nms3d(int b, int n, int max_per_class, int max_output_size, float
  * (dx*dx + dy*dy) + dz*dz, d = query[s,i] - sets[s,k,j], the smallest j among equal distances (tf.argmin).  With boxes, a query that is
  * not inside box k -- q >= c - s/2 && q <= c + s/2 on all axes -- gets -1 and is not searched.  p <= 4096, n <= 32768. */
 int gspn_nearest_in_sets(int b, int r, int n, int p, const float* query, const float* sets, const float* boxes, int* idx, void* stream);
+
+/* ---------------- models/model_rpointnet.py heads: the first layer over the crop (gspn_amd/csrc/heads.hip) ----------------------------
+ * classification_head (:915) and segmentation_head (:946) start with a 1x1 convolution of the crop points_cropping (:785-816) builds,
+ * concat(pc_fea[idx] (C), center_n (3), coord_n (3)) with center_n = (center[idx] - roi centre) / size, coord_n = (pc[idx] - roi centre) /
+ * size.  The layer is linear and per point, so with T (b*n, ldt >= cout) = pc_fea . W[:C] (one gspn_mlp_fwd launch over the b*n points)
+ *     Y[row, :] = T[scene*n + idx[row], :cout] + center_n[row] . Wside[0:3] + coord_n[row] . Wside[3:6] + bias,   row over (b, r, p)
+ * and the (b, r, p, C + 6) crop is never written.  idx (b,r,p) i32 scene-local (a value outside [0, n) is clamped), pc, center (b,n,3),
+ * rois (b,r,6) zero padded, Wside (6,cout) = rows C..C+5 of the layer's weights, bias (cout).  size is 1 when normalize == 0; otherwise
+ * rois[.., 3:6], with 1 added when the row's six values sum to 0 (:812; the centre is read before that, as in the reference).
+ * fp32, no atomics, no host synchronisation.  cout a multiple of 4 and <= 256, ldt a multiple of 4, T / Wside / bias / Y / dY /
+ * dcenter_rows 16-byte aligned: GSPN_ERR_UNSUPPORTED otherwise, before anything is launched. */
+int gspn_crop_linear_fwd(int b, int n, int r, int p, int cout, const float* T, int ldt, const int* idx, const float* pc, const float* center,
+                         const float* rois, int normalize, const float* Wside, const float* bias, float* Y, void* stream);
+
+/* The gradients of the above that are not gathers: dWside (6,cout) = side^T . dY and dbias (cout) = colsum(dY) over the b*r*p rows of dY
+ * (rows, cout), and dcenter_rows (rows, 4) = ((dY[row] . Wside[k]) / size[k], k = 0..2; 0): the gradient of the centre coordinates each row
+ * read.  Every workgroup writes one partial (7, cout) into part (gspn_crop_linear_part_floats floats; 0 for sizes the launcher does not
+ * take) and a second kernel adds the partials in workgroup order in double: a fixed order, the same bits on every call.  The gradients of
+ * the two gathers -- dT from dY at width cout, dcenter from dcenter_rows at width 4 -- are gspn_crop_gather_grad through the inverse
+ * lists of idx.  pc and rois get no gradient. */
+long gspn_crop_linear_part_floats(int b, int r, int p, int cout);
+int gspn_crop_linear_bwd_side(int b, int n, int r, int p, int cout, const float* dY, const int* idx, const float* pc, const float* center,
+                              const float* rois, int normalize, const float* Wside, float* part, float* dWside, float* dbias,
+                              float* dcenter_rows, void* stream);
 
 /* ---------------- utils/pointnet_util.py composition helpers --------------------------- */
 

@@ -17,12 +17,17 @@
             nearest_in_sets with and without the box gate and unmold_segmentation on 100 detections x 1024 crop points, and
             unmold_segmentation as the reference states it -- the broadcast distance tensor, written in torch and chunked over the ROIs so
             that it fits -- alternating in one process; median / min / max, the inside share and the distance evaluations per launch
+  heads     the two heads (gspn_amd/heads.py) with the reference's widths over --crop-channels feature channels, their first layer fused
+            with the crop (crop=, the T GEMM included) against points_cropping + the materialised heads, alternating in one process: both
+            heads forward + backward at the training shape (64 ROIs x 256 points), forward only at the inference shapes (classification
+            head 384 x 1024, segmentation head 100 x 1024); median / min / max and the largest relative difference between the two forms
 
 Prints one JSON line per (shape, measurement): median / min milliseconds over --iters timed runs after --warmup runs.
     python tools/spn_step.py --shapes 2x18000,8x32768
     python tools/spn_step.py --shapes 2x18000 --measures spn
     python tools/spn_step.py --shapes 2x18000 --measures roi
     python tools/spn_step.py --shapes 2x18000 --measures detect
+    python tools/spn_step.py --shapes 2x18000 --measures heads --iters 30
 """
 import argparse
 import json
@@ -265,6 +270,59 @@ def measure_detect(a, shape, b, n, dev):
                       "unmold_chunk": a.unmold_chunk, **res}), flush=True)
 
 
+def measure_heads(a, shape, b, n, dev):
+    from gspn_amd import rpointnet as RP
+    sc = {k: torch.from_numpy(v) for k, v in synth.spn_batch(a.kind, b, n, 100, 512, 19, seed0=7).items()}
+    ext = sc["pc"].amax((0, 1))
+    pc = sc["pc"].to(dev)
+    seed = torch.zeros(1, dtype=torch.int64, device=dev)
+    gen = torch.Generator().manual_seed(64)
+    ncat = RP.Config.NUM_CATEGORY
+    cases = (("training_both_heads_fwd_bwd", True, 64, 256, True, True), ("inference_classification_head_fwd", False, 384, 1024, True, False),
+             ("inference_segmentation_head_fwd", False, 100, 1024, False, True))
+    for name, train, r, p, with_cls, with_seg in cases:
+        cfg = RP.Config(istrain=train)
+        cfg.NUM_POINT_INS_MASK = p
+        boxes = roi_proposals(sc["bbox_ins"], ext, r, gen)[0].to(dev)
+        rois, idx = RP.mask_selection_gen_batch(boxes, pc, r, cfg, False, seed)
+        fea = torch.randn(b, n, a.crop_channels, device=dev).requires_grad_(train)
+        cen = (pc + 0.1 * torch.randn(b, n, 3, device=dev)).requires_grad_(train)
+        store = tf_util.set_variable_store(tf_util.VariableStore(device=dev, seed=1))
+        last = {}
+
+        def run(fused):
+            def fn():
+                fea.grad = cen.grad = None
+                for v in store.parameters():
+                    v.grad = None
+                if fused:
+                    crop, coord, feat = dict(pc=pc, pc_fea=fea, pc_center=cen, rois=rois, idx=idx, normalize=cfg.NORMALIZE_CROP_REGION), None, None
+                else:
+                    f, c, coord, _ = RP.points_cropping(pc, fea, cen, rois, idx, r, p, cfg.NORMALIZE_CROP_REGION)
+                    crop, feat = None, torch.cat((f, c), -1)
+                outs = []
+                if with_cls:
+                    logits, _, deltas = RP.classification_head(coord, feat, ncat, [128, 256, 512], [256, 256], train, 0.5, 'classification_head',
+                                                               crop=crop)
+                    outs += [logits, deltas]
+                if with_seg:
+                    outs.append(RP.segmentation_head(coord, feat, ncat, [64, 64], [64, 128, 512], [256, 256], train, 0.5, 'segmentation_head',
+                                                     crop=crop))
+                if train:
+                    sum(o.square().mean() for o in outs).backward()
+                last[fused] = [o.detach() for o in outs]
+            return fn
+
+        fns = {"materialised": run(False), "fused": run(True)}
+        for fn in fns.values():
+            fn()
+        diff = max(float((x - y).abs().max() / (y.abs().max() + 1e-30)) for x, y in zip(last[True], last[False]))
+        res = timed_alternating(fns, a.warmup, a.iters)
+        print(json.dumps({"shape": shape, "kind": a.kind, "measure": "heads", "config": name, "rois": r, "points_per_roi": p,
+                          "crop_channels": a.crop_channels, "iters": a.iters, "max_relative_difference_fused_vs_materialised": diff, **res}),
+              flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--measures", default="step,full_fwd,nn,spn")
@@ -289,6 +347,8 @@ def main():
             measure_roi(a, shape, b, n, dev)
         if "detect" in measures:
             measure_detect(a, shape, b, n, dev)
+        if "heads" in measures:
+            measure_heads(a, shape, b, n, dev)
         if not set(measures) & {"step", "full_fwd", "nn"}:
             continue
         xyz = torch.from_numpy(synth.batch(a.kind, b, n)).to(dev)

@@ -86,6 +86,10 @@ __device__ __forceinline__ int wave_max_i32(int v) {
     return max(max(a, b), max(c, d));
 }
 __device__ __forceinline__ int lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
+// the number of set bits of a ballot mask below this lane: the slot of a hit among the wave's hits, in lane order
+__device__ __forceinline__ int mbcnt64(unsigned long long mask) {
+    return __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+}
 
 static inline int gspn_launch_status() {
     hipError_t e = hipGetLastError();

@@ -1,12 +1,5 @@
-// detect.hip -- the detection output stage of R-PointNet (models/model_rpointnet.py) behind the two heads, ABI 14.
-//
-//   gspn_class_nms3d       the per-class NMS of refine_detections (:855-901): the reference calls nms_3d once per class through a py_func and
-//                          intersects index sets on the host.  One workgroup per scene and ONE pass over all candidates in score order: the
-//                          sort, the register-resident candidates and the double-buffered live mask of gspn_nms3d (roi.hip); a pick tests only
-//                          the live candidates of its own class, and every live candidate counts the picks of its class, so a class leaves
-//                          after max_per_class picks -- or at once after a pick that survives its own IoU test, which the reference would pick
-//                          again until the class is full and then collapse into one row (:893).  The picks come out in descending score, which
-//                          is the order of the reference's final top_k (:900).
+// detect.hip -- the detection output stage of R-PointNet (models/model_rpointnet.py) behind the two heads, ABI 14, without its per-class NMS
+// (gspn_class_nms3d of nms3d.hip).
 //   gspn_nearest_in_sets   the argmin of unmold_segmentation (:1032-1033) behind the box test of :1042, without the (B, R, N, P) distance
 //                          tensor: a workgroup per (scene, ROI, query tile).  The inside test first; the inside queries are compacted into
 //                          LDS by wave ballot, and a tile without one leaves before anything is staged.  Then the ROI's points are staged as
@@ -16,155 +9,14 @@
 //
 // fp32 throughout, no atomics, no host synchronisation, no allocation.  Compiled with -ffp-contract=off: every bound, volume, IoU and distance
 // below is evaluated exactly as the reference writes it.
-#include <math.h>
+#include "box_common.h"
 
-#include "common.h"
-
-#define CN_THREADS 1024
-#define CN_WAVES (CN_THREADS / GSPN_WAVE)
-#define CN_MAX_N 4096
-#define CN_SLOTS (CN_MAX_N / CN_THREADS)
-#define CN_WORDS (CN_MAX_N / 64)
 #define NN_THREADS 256
 #define NN_WAVES (NN_THREADS / GSPN_WAVE)
 #define NN_MAX_P 4096
 #define NN_MAX_N 32768
 
 namespace {
-
-__device__ __forceinline__ int det_mbcnt64(unsigned long long mask) {
-    return __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
-
-// ---------------------------------------------------------------------------------------------------- per-class nms_3d
-// grid (b), CN_THREADS lanes, p = n rounded up to a power of two (>= 64).  Dynamic LDS: the live mask twice (2 x 64 words), the sorted
-// indices and their classes (2 x p ints), then lo[3], hi[3], volume of the sorted candidates (7 x p floats); the sort's 64-bit keys lie
-// over the last region.
-__global__ __launch_bounds__(CN_THREADS) void class_nms3d_kernel(int n, int p, int per_class, int m, float iou_thr, const float* __restrict__ boxes,
-                                                                 const float* __restrict__ scores, const int* __restrict__ class_ids,
-                                                                 int* __restrict__ out) {
-    extern __shared__ __align__(16) unsigned char cn_smem[];
-    unsigned long long* alive = (unsigned long long*)cn_smem;                      // [2][CN_WORDS]
-    int* sidx = (int*)(cn_smem + 2 * CN_WORDS * 8);                               // [p]
-    int* scls = sidx + p;                                                          // [p]
-    float* cb = (float*)(scls + p);                                                // [7][p]
-    unsigned long long* key = (unsigned long long*)cb;                             // [p], dead before cb is written
-    const int bi = blockIdx.x, tid = threadIdx.x, lane = tid % GSPN_WAVE, wave = tid / GSPN_WAVE;
-    const float* bx = boxes + (long)bi * n * 6;
-    const float* sc = scores + (long)bi * n;
-    const int* ci = class_ids + (long)bi * n;
-    int* o = out + (long)bi * m;
-
-    // ascending 64-bit keys = descending score, lower index first among equal scores (-0 counts as +0); a row of class <= 0 is no candidate
-    for (int k = tid; k < p; k += CN_THREADS) {
-        unsigned long long v = ~0ull;
-        if (k < n && ci[k] > 0) {
-            unsigned u = __float_as_uint(sc[k] + 0.0f);
-            u = (u >> 31) ? ~u : (u | 0x80000000u);
-            v = ((unsigned long long)(~u) << 32) | (unsigned)k;
-        }
-        key[k] = v;
-    }
-    __syncthreads();
-    for (int size = 2; size <= p; size <<= 1) {
-        for (int j = size >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < p / 2; t += CN_THREADS) {
-                const int i = 2 * t - (t & (j - 1)), l = i + j;
-                const unsigned long long a = key[i], c = key[l];
-                if ((a > c) == ((i & size) == 0)) {
-                    key[i] = c;
-                    key[l] = a;
-                }
-            }
-            __syncthreads();
-        }
-    }
-
-    // candidate k = u * CN_THREADS + tid lives in this lane's registers; bit (k % 64) of word (k / 64) says whether it is still live
-    int si[CN_SLOTS];
-#pragma unroll
-    for (int u = 0; u < CN_SLOTS; ++u) {
-        const int k = u * CN_THREADS + tid;
-        si[u] = -1;
-        if (k < p) {
-            const unsigned long long v = key[k];
-            if (v != ~0ull) si[u] = (int)(unsigned)v;
-        }
-    }
-    __syncthreads();                                                 // the keys are dead: cb takes their place
-    float lo[CN_SLOTS][3], hi[CN_SLOTS][3], vol[CN_SLOTS];
-    int cls[CN_SLOTS], seen[CN_SLOTS];                               // seen: the picks of this candidate's class so far
-    bool live[CN_SLOTS];
-#pragma unroll
-    for (int u = 0; u < CN_SLOTS; ++u) {
-        const int k = u * CN_THREADS + tid;
-        live[u] = false;
-        cls[u] = 0;
-        seen[u] = 0;
-        if (k < p) {
-            float q[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-            if (si[u] >= 0) {
-#pragma unroll
-                for (int a = 0; a < 6; ++a) q[a] = bx[(long)si[u] * 6 + a];
-                cls[u] = ci[si[u]];
-                live[u] = true;
-            }
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                lo[u][a] = q[a] - q[3 + a] / 2.0f;
-                hi[u][a] = q[a] + q[3 + a] / 2.0f;
-                cb[a * p + k] = lo[u][a];
-                cb[(3 + a) * p + k] = hi[u][a];
-            }
-            vol[u] = q[3] * q[4] * q[5];
-            cb[6 * p + k] = vol[u];
-            sidx[k] = si[u];
-            scls[k] = cls[u];
-        }
-        const unsigned long long mask = __ballot(live[u]);
-        if (lane == 0) alive[u * CN_WAVES + wave] = mask;
-    }
-    __syncthreads();
-
-    int count = 0;
-    for (; count < m; ++count) {
-        const unsigned long long* cur = alive + (count & 1) * CN_WORDS;
-        unsigned long long* nxt = alive + ((count + 1) & 1) * CN_WORDS;
-        const unsigned long long nz = __ballot(cur[lane] != 0ull);   // lane l looks at word l: CN_WORDS == 64
-        if (nz == 0ull) break;                                       // every wave reads the same words: uniform
-        const int word = __builtin_ctzll(nz);
-        const int k0 = word * 64 + __builtin_ctzll(cur[word]);
-        float plo[3], phi[3], own[3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            plo[a] = cb[a * p + k0];
-            phi[a] = cb[(3 + a) * p + k0];
-            own[a] = fmaxf(phi[a] - plo[a], 0.0f);                   // min(hi, hi) - max(lo, lo)
-        }
-        const float pvol = cb[6 * p + k0];
-        const int pcls = scls[k0];
-        if (tid == 0) o[count] = sidx[k0];
-        // the pick's own test, as its lane evaluates it below: a pick that survives it would be picked until its class is full
-        const float own_inter = own[0] * own[1] * own[2];
-        const bool exhausted = !(own_inter / (((pvol + pvol) - own_inter) + 1e-8f) > iou_thr);
-#pragma unroll
-        for (int u = 0; u < CN_SLOTS; ++u) {
-            if (live[u] && cls[u] == pcls) {
-                float cube[3];
-#pragma unroll
-                for (int a = 0; a < 3; ++a) cube[a] = fmaxf(fminf(phi[a], hi[u][a]) - fmaxf(plo[a], lo[u][a]), 0.0f);
-                const float inter = cube[0] * cube[1] * cube[2];
-                const float iou = inter / (((vol[u] + pvol) - inter) + 1e-8f);
-                ++seen[u];
-                if (iou > iou_thr || exhausted || seen[u] >= per_class) live[u] = false;
-            }
-            const unsigned long long mask = __ballot(live[u]);
-            if (lane == 0) nxt[u * CN_WAVES + wave] = mask;
-        }
-        __syncthreads();
-    }
-    for (int j = count + tid; j < m; j += CN_THREADS) o[j] = -1;
-}
 
 // ---------------------------------------------------------------------------------------------------- nearest point of each set
 // grid (ceil(n / (NN_THREADS * QB)), r, b), NN_THREADS lanes.  Dynamic LDS: the set as three planes of p4 = p rounded up to 4 floats, the
@@ -185,11 +37,7 @@ __global__ __launch_bounds__(NN_THREADS) void nearest_in_sets_kernel(int r, int 
     if (boxes != nullptr) {
         const float* bx = boxes + ((long)bi * r + ri) * 6;           // uniform: scalar loads
         float lo[3], hi[3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            lo[a] = bx[a] - bx[3 + a] / 2.0f;
-            hi[a] = bx[a] + bx[3 + a] / 2.0f;
-        }
+        box_bounds(bx, lo, hi);
         bool in[QB];
         int before[QB];
 #pragma unroll
@@ -197,9 +45,9 @@ __global__ __launch_bounds__(NN_THREADS) void nearest_in_sets_kernel(int r, int 
             const int i = i0 + u * NN_THREADS + tid;
             const float* g = q + 3 * (long)min(i, n - 1);
             const float x = i < n ? g[0] : NAN, y = g[1], z = g[2];  // a slot past n holds NaN, which is inside no box
-            in[u] = x >= lo[0] && x <= hi[0] && y >= lo[1] && y <= hi[1] && z >= lo[2] && z <= hi[2];
+            in[u] = point_in_box(x, y, z, lo, hi);
             const unsigned long long mask = __ballot(in[u]);
-            before[u] = det_mbcnt64(mask);
+            before[u] = mbcnt64(mask);
             if (lane == 0) wcnt[u][wave] = __popcll(mask);
             if (i < n && !in[u]) o[i] = -1;
         }
@@ -302,21 +150,6 @@ __global__ __launch_bounds__(NN_THREADS) void nearest_in_sets_kernel(int r, int 
 }
 
 }  // namespace
-
-extern "C" int gspn_class_nms3d(int b, int n, int max_per_class, int max_output_size, float iou_threshold, const float* boxes, const float* scores,
-                                const int* class_ids, int* selected, void* stream) {
-    if (b <= 0 || n <= 0 || max_per_class <= 0 || max_output_size <= 0) return GSPN_ERR_ARG;
-    if (n > CN_MAX_N) return GSPN_ERR_UNSUPPORTED;
-    int p = 64;
-    while (p < n) p <<= 1;
-    const size_t lds = 2 * CN_WORDS * 8 + (size_t)p * 8 + (size_t)p * 28;
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute((const void*)class_nms3d_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * CN_WORDS * 8 + CN_MAX_N * 36) != hipSuccess)
-        return (int)hipGetLastError();
-    class_nms3d_kernel<<<b, CN_THREADS, lds, (hipStream_t)stream>>>(n, p, max_per_class, max_output_size, iou_threshold, boxes, scores, class_ids,
-                                                                   selected);
-    return gspn_launch_status();
-}
 
 extern "C" int gspn_nearest_in_sets(int b, int r, int n, int p, const float* query, const float* sets, const float* boxes, int* idx, void* stream) {
     if (b <= 0 || r <= 0 || n <= 0 || p <= 0) return GSPN_ERR_ARG;

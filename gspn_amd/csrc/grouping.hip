@@ -65,7 +65,7 @@ __global__ __launch_bounds__(BQ_WAVES * 64) void ball_query_kernel(int b, int n,
             const unsigned long long mask = __ballot(hit);
             if (mask != 0ull && cnt < nsample) {
                 if (cnt == 0) first = base + u * 64 + __builtin_ctzll(mask);
-                const int pos = cnt + __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+                const int pos = cnt + mbcnt64(mask);
                 if (hit && pos < nsample) row[pos] = k;          // :33
                 cnt += __builtin_popcountll(mask);
             }
@@ -174,7 +174,7 @@ __global__ __launch_bounds__(BQM_WAVES * 64) void ball_query_cont_kernel(int b, 
                 const int kb = base + 256 * ch + 4 * lane;
                 int pos = c;
 #pragma unroll
-                for (int u = 0; u < 4; ++u) pos += __builtin_amdgcn_mbcnt_hi((unsigned)(mm[ch][u] >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mm[ch][u], 0u));
+                for (int u = 0; u < 4; ++u) pos += mbcnt64(mm[ch][u]);
 #pragma unroll
                 for (int u = 0; u < 4; ++u)
                     if (h[ch][u]) { if (pos < nsample) row[pos] = kb + u; ++pos; }          // :33, ascending k
@@ -381,7 +381,7 @@ __global__ __launch_bounds__(256) void ball_grid_query_kernel(int b, int n, int 
         }
         const unsigned long long mask = __ballot(hit);
         if (mask != 0ull) {
-            const int pos = cnt + __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+            const int pos = cnt + mbcnt64(mask);
             if (hit && pos < BQG_CAP) hits[pos] = k;
             cnt += __builtin_popcountll(mask);
         }

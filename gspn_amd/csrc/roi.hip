@@ -1,12 +1,7 @@
-// roi.hip -- the ROI stage of R-PointNet (models/model_rpointnet.py) between the shape proposals and the two heads, ABI 13.
-//
-//   gspn_nms3d                    nms_3d (:436-466), a numpy loop per scene on the host in the reference.  One workgroup per scene, the scene
-//                                 resident on chip: a bitonic sort of (score, index) in LDS, then the greedy loop -- the first live candidate in
-//                                 score order is written out, every lane tests its own candidates (bounds and volumes in registers) against it
-//                                 and clears those with iou > threshold.  The live set is a bit mask of 64 words kept twice in LDS, read from one
-//                                 copy and written to the other, so a pick costs one barrier.
-//   gspn_box_point_count          number of points inside each box (the "remove empty proposals" test of :671-678 and :762-770).  The scan of
-//                                 box_shrink_kernel (spn_boxes.hip): boxes in registers, lanes stride over the points, loads issued ahead.
+// roi.hip -- the ROI stage of R-PointNet (models/model_rpointnet.py) between the shape proposals and the two heads, ABI 13, behind its first
+// step, nms_3d (gspn_nms3d of nms3d.hip).
+//   gspn_box_point_count          number of points inside each box (the "remove empty proposals" test of :671-678 and :762-770): the scan of
+//                                 gspn_box_shrink (spn_boxes.hip), same shape (BOX_SCAN_* of box_common.h), with a count for accumulator.
 //   gspn_sample_points_in_boxes   sample_points_within_box (:584-597) without its (boxes, points) mask matrix: a workgroup per box, every wave
 //                                 compacts the inside indices of a contiguous quarter of the points, ascending, into its own LDS region
 //                                 (ballot + mbcnt), then draw j looks up rank (rand32 * count) >> 32 across the four regions.
@@ -21,18 +16,8 @@
 //
 // fp32 throughout, no atomics, no host synchronisation, no allocation.  Compiled with -ffp-contract=off: every bound, volume and IoU below
 // is evaluated exactly as the reference writes it.  The random numbers are gspn_roi_rand32 of include/gspn_hip.h.
-#include <math.h>
+#include "box_common.h"
 
-#include "common.h"
-
-#define NMS_THREADS 1024
-#define NMS_WAVES (NMS_THREADS / GSPN_WAVE)
-#define NMS_MAX_N 4096
-#define NMS_SLOTS (NMS_MAX_N / NMS_THREADS)
-#define NMS_WORDS (NMS_MAX_N / 64)
-#define PC_THREADS 256
-#define PC_WAVES (PC_THREADS / GSPN_WAVE)
-#define PC_UNROLL 4
 #define SM_THREADS 256
 #define SM_WAVES (SM_THREADS / GSPN_WAVE)
 #define SM_UNROLL 4
@@ -59,142 +44,15 @@ __device__ __forceinline__ unsigned roi_rand32(unsigned long long scene_state, u
     return (unsigned)(roi_mix64(scene_state ^ (((unsigned long long)a << 32) | (unsigned long long)b)) >> 32);
 }
 
-__device__ __forceinline__ int mbcnt64(unsigned long long mask) {
-    return __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
-
-// ---------------------------------------------------------------------------------------------------- nms_3d
-// grid (b), NMS_THREADS lanes, p = n rounded up to a power of two (>= 64).  Dynamic LDS: the live mask twice (2 x 64 words), the sorted
-// indices (p ints), then lo[3], hi[3], volume of the sorted candidates (7 x p floats); the sort's 64-bit keys lie over the last region.
-__global__ __launch_bounds__(NMS_THREADS) void nms3d_kernel(int n, int p, int limit, int m, float iou_thr, float score_thr,
-                                                            const float* __restrict__ boxes, const float* __restrict__ scores,
-                                                            int* __restrict__ out) {
-    extern __shared__ __align__(16) unsigned char nms_smem[];
-    unsigned long long* alive = (unsigned long long*)nms_smem;                      // [2][NMS_WORDS]
-    int* sidx = (int*)(nms_smem + 2 * NMS_WORDS * 8);                              // [p]
-    float* cb = (float*)(nms_smem + 2 * NMS_WORDS * 8 + 4 * (size_t)p);            // [7][p]
-    unsigned long long* key = (unsigned long long*)cb;                              // [p], dead before cb is written
-    const int bi = blockIdx.x, tid = threadIdx.x, lane = tid % GSPN_WAVE, wave = tid / GSPN_WAVE;
-    const float* bx = boxes + (long)bi * n * 6;
-    const float* sc = scores + (long)bi * n;
-    int* o = out + (long)bi * m;
-
-    // ascending 64-bit keys = descending score, lower index first among equal scores (-0 counts as +0, as numpy's argsort of -scores has it)
-    for (int k = tid; k < p; k += NMS_THREADS) {
-        unsigned long long v = ~0ull;
-        if (k < n) {
-            unsigned u = __float_as_uint(sc[k] + 0.0f);
-            u = (u >> 31) ? ~u : (u | 0x80000000u);
-            v = ((unsigned long long)(~u) << 32) | (unsigned)k;
-        }
-        key[k] = v;
-    }
-    __syncthreads();
-    for (int size = 2; size <= p; size <<= 1) {
-        for (int j = size >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < p / 2; t += NMS_THREADS) {
-                const int i = 2 * t - (t & (j - 1)), l = i + j;
-                const unsigned long long a = key[i], c = key[l];
-                if ((a > c) == ((i & size) == 0)) {
-                    key[i] = c;
-                    key[l] = a;
-                }
-            }
-            __syncthreads();
-        }
-    }
-
-    // candidate k = u * NMS_THREADS + tid lives in this lane's registers; bit (k % 64) of word (k / 64) says whether it is still live
-    int si[NMS_SLOTS];
-#pragma unroll
-    for (int u = 0; u < NMS_SLOTS; ++u) {
-        const int k = u * NMS_THREADS + tid;
-        si[u] = -1;
-        if (k < p) {
-            const unsigned long long v = key[k];
-            if (v != ~0ull) si[u] = (int)(unsigned)v;
-        }
-    }
-    __syncthreads();                                                 // the keys are dead: cb takes their place
-    float lo[NMS_SLOTS][3], hi[NMS_SLOTS][3], vol[NMS_SLOTS];
-    bool live[NMS_SLOTS];
-#pragma unroll
-    for (int u = 0; u < NMS_SLOTS; ++u) {
-        const int k = u * NMS_THREADS + tid;
-        live[u] = false;
-        if (k < p) {
-            float q[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-            if (si[u] >= 0) {
-#pragma unroll
-                for (int a = 0; a < 6; ++a) q[a] = bx[(long)si[u] * 6 + a];
-                live[u] = k < limit && sc[si[u]] > score_thr;
-            }
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                lo[u][a] = q[a] - q[3 + a] / 2.0f;
-                hi[u][a] = q[a] + q[3 + a] / 2.0f;
-                cb[a * p + k] = lo[u][a];
-                cb[(3 + a) * p + k] = hi[u][a];
-            }
-            vol[u] = q[3] * q[4] * q[5];
-            cb[6 * p + k] = vol[u];
-            sidx[k] = si[u];
-        }
-        const unsigned long long mask = __ballot(live[u]);
-        if (lane == 0) alive[u * NMS_WAVES + wave] = mask;
-    }
-    __syncthreads();
-
-    int count = 0;
-    for (; count < m; ++count) {
-        const unsigned long long* cur = alive + (count & 1) * NMS_WORDS;
-        unsigned long long* nxt = alive + ((count + 1) & 1) * NMS_WORDS;
-        const unsigned long long nz = __ballot(cur[lane] != 0ull);   // lane l looks at word l: NMS_WORDS == 64
-        if (nz == 0ull) break;                                       // every wave reads the same words: uniform
-        const int word = __builtin_ctzll(nz);
-        const int k0 = word * 64 + __builtin_ctzll(cur[word]);
-        float plo[3], phi[3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            plo[a] = cb[a * p + k0];
-            phi[a] = cb[(3 + a) * p + k0];
-        }
-        const float pvol = cb[6 * p + k0];
-        if (tid == 0) o[count] = sidx[k0];
-#pragma unroll
-        for (int u = 0; u < NMS_SLOTS; ++u) {
-            if (live[u]) {
-                float cube[3];
-#pragma unroll
-                for (int a = 0; a < 3; ++a) cube[a] = fmaxf(fminf(phi[a], hi[u][a]) - fmaxf(plo[a], lo[u][a]), 0.0f);
-                const float inter = cube[0] * cube[1] * cube[2];
-                const float iou = inter / (((vol[u] + pvol) - inter) + 1e-8f);
-                if (iou > iou_thr) live[u] = false;                  // the pick itself leaves only by this test (:464-465)
-            }
-            const unsigned long long mask = __ballot(live[u]);
-            if (lane == 0) nxt[u * NMS_WAVES + wave] = mask;
-        }
-        __syncthreads();
-    }
-    for (int j = count + tid; j < m; j += NMS_THREADS) o[j] = -1;
-}
-
 // ---------------------------------------------------------------------------------------------------- points inside boxes
-// a point is inside when  pc >= (c - s/2) - margin  &&  pc <= (c + s/2) + margin  on all axes (:673-674 with margin 0, :764-765 with 1e-3)
-__device__ __forceinline__ void box_bounds(const float* __restrict__ q, float margin, float* lo, float* hi) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float h = q[3 + a] / 2.0f;
-        lo[a] = (q[a] - h) - margin;
-        hi[a] = (q[a] + h) + margin;
-    }
-}
-
+// a point is inside when  pc >= (c - s/2) - margin  &&  pc <= (c + s/2) + margin  on all axes (:673-674 with margin 0, :764-765 with 1e-3).
+// The two kernels below spell the six compares out where they use them: there the compiler keeps the early exits of the && chain, which
+// point_in_box (flattened before it is inlined) does not.
 // grid (ceil(s / NB), b).  Boxes past s in the last chunk are counted on a clamped index and not written.
 template <int NB>
-__global__ __launch_bounds__(PC_THREADS) void box_point_count_kernel(int s, int n, float margin, const float* __restrict__ box,
-                                                                     const float* __restrict__ pc, int* __restrict__ count) {
-    __shared__ int red[PC_WAVES][NB];
+__global__ __launch_bounds__(BOX_SCAN_THREADS) void box_point_count_kernel(int s, int n, float margin, const float* __restrict__ box,
+                                                                           const float* __restrict__ pc, int* __restrict__ count) {
+    __shared__ int red[BOX_SCAN_WAVES][NB];
     const int bi = blockIdx.y, s0 = blockIdx.x * NB, tid = threadIdx.x;
     const float* bx = box + (long)bi * s * 6;
     const float* p = pc + (long)bi * n * 3;
@@ -206,18 +64,18 @@ __global__ __launch_bounds__(PC_THREADS) void box_point_count_kernel(int s, int 
         cnt[k] = 0;
     }
     // a slot past n holds NaN, which is inside no box
-    for (int i0 = tid; i0 < n; i0 += PC_THREADS * PC_UNROLL) {
-        float x[PC_UNROLL], y[PC_UNROLL], z[PC_UNROLL];
+    for (int i0 = tid; i0 < n; i0 += BOX_SCAN_THREADS * BOX_SCAN_UNROLL) {
+        float x[BOX_SCAN_UNROLL], y[BOX_SCAN_UNROLL], z[BOX_SCAN_UNROLL];
 #pragma unroll
-        for (int u = 0; u < PC_UNROLL; ++u) {
-            const int i = i0 + u * PC_THREADS;
+        for (int u = 0; u < BOX_SCAN_UNROLL; ++u) {
+            const int i = i0 + u * BOX_SCAN_THREADS;
             const float* q = p + 3 * (long)min(i, n - 1);
             x[u] = i < n ? q[0] : NAN;
             y[u] = q[1];
             z[u] = q[2];
         }
 #pragma unroll
-        for (int u = 0; u < PC_UNROLL; ++u) {
+        for (int u = 0; u < BOX_SCAN_UNROLL; ++u) {
 #pragma unroll
             for (int k = 0; k < NB; ++k)
                 cnt[k] += (x[u] >= lo[k][0] && x[u] <= hi[k][0] && y[u] >= lo[k][1] && y[u] <= hi[k][1] && z[u] >= lo[k][2] && z[u] <= hi[k][2]) ? 1 : 0;
@@ -235,7 +93,7 @@ __global__ __launch_bounds__(PC_THREADS) void box_point_count_kernel(int s, int 
     if (tid < NB && s0 + tid < s) {
         int v = 0;
 #pragma unroll
-        for (int w = 0; w < PC_WAVES; ++w) v += red[w][tid];
+        for (int w = 0; w < BOX_SCAN_WAVES; ++w) v += red[w][tid];
         count[(long)bi * s + s0 + tid] = v;
     }
 }
@@ -250,7 +108,7 @@ __global__ __launch_bounds__(SM_THREADS) void sample_points_kernel(int r, int n,
     const float* bx = boxes + ((long)bi * r + ri) * 6;
     const float* p = pc + (long)bi * n * 3;
     int* o = idx_out + ((long)bi * r + ri) * nsmp;
-    const bool zero_row = bx[0] == 0.0f && bx[1] == 0.0f && bx[2] == 0.0f && bx[3] == 0.0f && bx[4] == 0.0f && bx[5] == 0.0f;
+    const bool zero_row = zero_row6(bx);
     float lo[3], hi[3];
     box_bounds(bx, margin, lo, hi);
     int cnt = 0;                                                     // uniform across the wave
@@ -304,24 +162,6 @@ __global__ __launch_bounds__(SM_THREADS) void sample_points_kernel(int r, int n,
 }
 
 // ---------------------------------------------------------------------------------------------------- detection targets
-// IoU of a proposal p and a ground-truth box q (:683-689), in the reference's order of operations (box_iou of spn_boxes.hip)
-__device__ __forceinline__ float roi_box_iou(const float* __restrict__ p, const float* __restrict__ q) {
-    const float vp = p[3] * p[4] * p[5], vq = q[3] * q[4] * q[5];
-    float cube[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float va = fmaxf(p[a] - p[3 + a] / 2.0f, q[a] - q[3 + a] / 2.0f);
-        const float vb = fminf(p[a] + p[3 + a] / 2.0f, q[a] + q[3 + a] / 2.0f);
-        cube[a] = fmaxf(vb - va, 0.0f);
-    }
-    const float inter = cube[0] * cube[1] * cube[2];
-    return inter / (vp + vq - inter + 1e-8f);
-}
-
-__device__ __forceinline__ bool zero_row6(const float* __restrict__ q) {
-    return q[0] == 0.0f && q[1] == 0.0f && q[2] == 0.0f && q[3] == 0.0f && q[4] == 0.0f && q[5] == 0.0f;
-}
-
 // grid (b), one lane per proposal (s <= DT_THREADS)
 __global__ __launch_bounds__(DT_THREADS) void detection_target_select_kernel(int s, int g, int rois, int max_positive, float inv_ratio,
                                                                              const long long* __restrict__ seed_dev,
@@ -345,7 +185,7 @@ __global__ __launch_bounds__(DT_THREADS) void detection_target_select_kernel(int
             for (int j = 0; j < g; ++j) {
                 const float* q = gb + (long)j * 6;                   // uniform: scalar loads
                 if (zero_row6(q)) continue;
-                const float v = roi_box_iou(p, q);
+                const float v = box_iou(p, q);
                 if (v > best) { best = v; arg = j; }                 // strict: the lowest index among equal IoUs (tf.argmax)
             }
             mycls = best >= 0.5f ? 1 : (best < 0.5f ? 2 : 0);
@@ -441,30 +281,15 @@ __global__ __launch_bounds__(GSPN_WAVE) void crop_grad_join_kernel(int n, int c,
 
 }  // namespace
 
-extern "C" int gspn_nms3d(int b, int n, int pre_nms_limit, int max_output_size, float iou_threshold, float score_threshold, const float* boxes,
-                          const float* scores, int* selected, void* stream) {
-    if (b <= 0 || n <= 0 || max_output_size <= 0) return GSPN_ERR_ARG;
-    if (n > NMS_MAX_N) return GSPN_ERR_UNSUPPORTED;
-    int p = 64;
-    while (p < n) p <<= 1;
-    const int limit = pre_nms_limit > 0 ? min(pre_nms_limit, n) : n;
-    const size_t lds = 2 * NMS_WORDS * 8 + (size_t)p * 4 + (size_t)p * 28;
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute((const void*)nms3d_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * NMS_WORDS * 8 + NMS_MAX_N * 32) != hipSuccess)
-        return (int)hipGetLastError();
-    nms3d_kernel<<<b, NMS_THREADS, lds, (hipStream_t)stream>>>(n, p, limit, max_output_size, iou_threshold, score_threshold, boxes, scores, selected);
-    return gspn_launch_status();
-}
-
 extern "C" int gspn_box_point_count(int b, int s, int n, float margin, const float* boxes, const float* pc, int* count, void* stream) {
     if (b <= 0 || s <= 0 || n <= 0) return GSPN_ERR_ARG;
     if (b > 65535) return GSPN_ERR_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
     // as gspn_box_shrink: 8 boxes per workgroup once that fills the chip, 4 below
     if ((long)b * ((s + 7) / 8) >= 256)
-        box_point_count_kernel<8><<<dim3((s + 7) / 8, b), PC_THREADS, 0, st>>>(s, n, margin, boxes, pc, count);
+        box_point_count_kernel<8><<<dim3((s + 7) / 8, b), BOX_SCAN_THREADS, 0, st>>>(s, n, margin, boxes, pc, count);
     else
-        box_point_count_kernel<4><<<dim3((s + 3) / 4, b), PC_THREADS, 0, st>>>(s, n, margin, boxes, pc, count);
+        box_point_count_kernel<4><<<dim3((s + 3) / 4, b), BOX_SCAN_THREADS, 0, st>>>(s, n, margin, boxes, pc, count);
     return gspn_launch_status();
 }
 
@@ -474,9 +299,8 @@ extern "C" int gspn_sample_points_in_boxes(int b, int r, int n, int nsmp, float 
     if (n > SM_MAX_N || b > 65535) return GSPN_ERR_UNSUPPORTED;
     const int q = (n + SM_WAVES - 1) / SM_WAVES;
     const size_t lds = (size_t)SM_WAVES * q * sizeof(int);
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute((const void*)sample_points_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SM_MAX_N * (int)sizeof(int)) != hipSuccess)
-        return (int)hipGetLastError();
+    const hipError_t e = lds > 64 * 1024 ? gspn_dyn_lds_optin<&sample_points_kernel>(SM_MAX_N * (int)sizeof(int)) : hipSuccess;
+    if (e != hipSuccess) return (int)e;
     sample_points_kernel<<<dim3(r, b), SM_THREADS, lds, (hipStream_t)stream>>>(r, n, nsmp, q, margin, seed_dev, boxes, pc, idx_out);
     return gspn_launch_status();
 }

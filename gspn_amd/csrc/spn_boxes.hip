@@ -11,13 +11,10 @@
 //
 // fp32 throughout, no atomics, no host synchronisation.  The translation unit is compiled with -ffp-contract=off like the distance kernels
 // (common.h): every bound, sum and product below is evaluated exactly as written, nothing is fused.
-#include <math.h>
-
-#include "common.h"
+#include "box_common.h"
 
 #define BX_THREADS 256
 #define BX_WAVES (BX_THREADS / GSPN_WAVE)
-#define BX_UNROLL 4
 #define TG_THREADS 1024
 #define TG_WAVES (TG_THREADS / GSPN_WAVE)
 
@@ -37,42 +34,39 @@ __device__ __forceinline__ float wave_min_f32(float v) {
 // ---------------------------------------------------------------------------------------------------- box_shrink
 // grid (ceil(s / NB), b).  Boxes past s in the last chunk are computed on a clamped index and not written.
 template <int NB>
-__global__ __launch_bounds__(BX_THREADS) void box_shrink_kernel(int s, int n, const float* __restrict__ box, const float* __restrict__ pc,
-                                                                float* __restrict__ out) {
-    __shared__ float red[BX_WAVES][NB][6];
+__global__ __launch_bounds__(BOX_SCAN_THREADS) void box_shrink_kernel(int s, int n, const float* __restrict__ box, const float* __restrict__ pc,
+                                                                      float* __restrict__ out) {
+    __shared__ float red[BOX_SCAN_WAVES][NB][6];
     const int bi = blockIdx.y, s0 = blockIdx.x * NB, tid = threadIdx.x;
     const float* bx = box + (long)bi * s * 6;
     const float* p = pc + (long)bi * n * 3;
     float lo[NB][3], hi[NB][3], mn[NB][3], mx[NB][3];
 #pragma unroll
     for (int k = 0; k < NB; ++k) {
-        const float* q = bx + (long)min(s0 + k, s - 1) * 6;          // uniform across the workgroup: scalar loads
+        box_bounds(bx + (long)min(s0 + k, s - 1) * 6, lo[k], hi[k]);  // uniform across the workgroup: scalar loads
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
-            const float h = q[3 + a] / 2.0f;
-            lo[k][a] = q[a] - h;
-            hi[k][a] = q[a] + h;
             mn[k][a] = INFINITY;
             mx[k][a] = -INFINITY;
         }
     }
-    // BX_UNROLL points per lane and trip, all their loads issued before the first test: the scan is bound by load latency, not by the
-    // compares.  A slot past n holds NaN, which is inside no box.
-    for (int i0 = tid; i0 < n; i0 += BX_THREADS * BX_UNROLL) {
-        float x[BX_UNROLL], y[BX_UNROLL], z[BX_UNROLL];
+    // BOX_SCAN_UNROLL points per lane and trip, all their loads issued before the first test: the scan is bound by load latency, not by
+    // the compares.  A slot past n holds NaN, which is inside no box.
+    for (int i0 = tid; i0 < n; i0 += BOX_SCAN_THREADS * BOX_SCAN_UNROLL) {
+        float x[BOX_SCAN_UNROLL], y[BOX_SCAN_UNROLL], z[BOX_SCAN_UNROLL];
 #pragma unroll
-        for (int u = 0; u < BX_UNROLL; ++u) {
-            const int i = i0 + u * BX_THREADS;
+        for (int u = 0; u < BOX_SCAN_UNROLL; ++u) {
+            const int i = i0 + u * BOX_SCAN_THREADS;
             const float* q = p + 3 * (long)min(i, n - 1);
             x[u] = i < n ? q[0] : NAN;
             y[u] = q[1];
             z[u] = q[2];
         }
 #pragma unroll
-        for (int u = 0; u < BX_UNROLL; ++u) {
+        for (int u = 0; u < BOX_SCAN_UNROLL; ++u) {
 #pragma unroll
             for (int k = 0; k < NB; ++k) {
-                const bool in = x[u] >= lo[k][0] && x[u] <= hi[k][0] && y[u] >= lo[k][1] && y[u] <= hi[k][1] && z[u] >= lo[k][2] && z[u] <= hi[k][2];
+                const bool in = point_in_box(x[u], y[u], z[u], lo[k], hi[k]);
                 mx[k][0] = fmaxf(mx[k][0], in ? x[u] : -INFINITY);
                 mx[k][1] = fmaxf(mx[k][1], in ? y[u] : -INFINITY);
                 mx[k][2] = fmaxf(mx[k][2], in ? z[u] : -INFINITY);
@@ -102,7 +96,7 @@ __global__ __launch_bounds__(BX_THREADS) void box_shrink_kernel(int s, int n, co
             bmax[a] = red[0][tid][a];
             bmin[a] = red[0][tid][3 + a];
 #pragma unroll
-            for (int w = 1; w < BX_WAVES; ++w) {
+            for (int w = 1; w < BOX_SCAN_WAVES; ++w) {
                 bmax[a] = fmaxf(bmax[a], red[w][tid][a]);
                 bmin[a] = fminf(bmin[a], red[w][tid][3 + a]);
             }
@@ -157,20 +151,6 @@ __global__ __launch_bounds__(BX_THREADS) void points_bbox_kernel(long rows, int 
 }
 
 // ---------------------------------------------------------------------------------------------------- spn_target_gen
-// IoU of two (centre, size) boxes, :617-623, in the reference's order of operations
-__device__ __forceinline__ float box_iou(const float* __restrict__ p, const float* __restrict__ q) {
-    const float vp = p[3] * p[4] * p[5], vq = q[3] * q[4] * q[5];
-    float cube[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float va = fmaxf(p[a] - p[3 + a] / 2.0f, q[a] - q[3 + a] / 2.0f);
-        const float vb = fminf(p[a] + p[3 + a] / 2.0f, q[a] + q[3 + a] / 2.0f);
-        cube[a] = fmaxf(vb - va, 0.0f);
-    }
-    const float inter = cube[0] * cube[1] * cube[2];
-    return inter / (vp + vq - inter + 1e-8f);
-}
-
 // grid (b), one workgroup per scene
 __global__ __launch_bounds__(TG_THREADS) void spn_target_gen_kernel(int s, int g, const float* __restrict__ proposals,
                                                                     const float* __restrict__ seed_cls, const float* __restrict__ gt_cls,
@@ -228,9 +208,9 @@ extern "C" int gspn_box_shrink(int b, int s, int n, const float* box, const floa
     hipStream_t st = (hipStream_t)stream;
     // 8 boxes per workgroup once that fills the chip, 4 below (the training shape, 2 x 256 boxes: 128 workgroups instead of 64)
     if ((long)b * ((s + 7) / 8) >= 256)
-        box_shrink_kernel<8><<<dim3((s + 7) / 8, b), BX_THREADS, 0, st>>>(s, n, box, pc, out);
+        box_shrink_kernel<8><<<dim3((s + 7) / 8, b), BOX_SCAN_THREADS, 0, st>>>(s, n, box, pc, out);
     else
-        box_shrink_kernel<4><<<dim3((s + 3) / 4, b), BX_THREADS, 0, st>>>(s, n, box, pc, out);
+        box_shrink_kernel<4><<<dim3((s + 3) / 4, b), BOX_SCAN_THREADS, 0, st>>>(s, n, box, pc, out);
     return gspn_launch_status();
 }
 

@@ -270,7 +270,7 @@ int gspn_points_bbox(int rows, int m, const float* pts, const float* offset, flo
 int gspn_spn_target_gen(int b, int s, int g, const float* proposals, const float* seed_cls, const float* gt_cls, const float* gt_boxes,
                         int* spn_match, void* stream);
 
-/* ---------------- models/model_rpointnet.py ROI stage: from shape proposals to the inputs of the heads (gspn_amd/csrc/roi.hip) -------
+/* ---------------- models/model_rpointnet.py ROI stage: from shape proposals to the inputs of the heads (gspn_amd/csrc/roi.hip; gspn_nms3d: nms3d.hip) -------
  * Same rules as the box arithmetic above: fp32, no atomics, no workspace, no host synchronisation, nothing contracted.
  *
  * Random numbers.  A stateless counter-based generator; with 64-bit unsigned arithmetic modulo 2^64 and
@@ -320,7 +320,7 @@ long gspn_crop_gather_grad_part_floats(int b, int len, int c);
 int gspn_crop_gather_grad(int b, int n, int c, int len, const int* idx, const int* order, const int* offsets, const float* grad_out,
                           float* part, float* grad_points, void* stream);
 
-/* ---------------- models/model_rpointnet.py detection output stage: behind the two heads (gspn_amd/csrc/detect.hip) -------------------
+/* ---------------- models/model_rpointnet.py detection output stage: behind the two heads (gspn_amd/csrc/detect.hip; gspn_class_nms3d: nms3d.hip) ---
  * Same rules as the ROI stage: fp32, no atomics, no workspace, no host synchronisation, nothing contracted. */
 
 /* The per-class NMS of refine_detections (:855-901) for a whole batch, one workgroup per scene.  boxes (b,n,6), scores (b,n), class_ids

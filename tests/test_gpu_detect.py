@@ -94,6 +94,29 @@ def test_class_nms_3d_ties_zero_volume_and_limits():
         class_nms_3d(torch.zeros(1, 4, 6, device="cuda"), zeros, zeros.int(), 8, 0, 0.1)
 
 
+@pytest.mark.parametrize("b,n,seed,m,thr,filled", [(2, 300, 71, 64, 0.25, False), (1, 1500, 72, 32, 0.1, True)])
+def test_class_nms_3d_of_one_class_is_nms_3d(b, n, seed, m, thr, filled):
+    """Both are instances of one kernel body (csrc/nms3d.hip).  With every row in class 1 and a class cap equal to the output size the
+    per-class form has to pick what the plain one picks -- provided no pick survives its own IoU test, after which the class form lets the
+    class leave at once where the plain form picks the row again.  N = 300: one candidate per lane, a sort of 512 > N keys, fewer picks
+    than m and a -1 tail.  N = 1500: two candidates per lane, the output filled."""
+    from gspn_amd.rpointnet import class_nms_3d, nms_3d
+    boxes, scores = RR.nms_boxes(b, n, seed)
+    for row in scores:
+        assert row.unique().numel() == n
+    vol = boxes[..., 3] * boxes[..., 4] * boxes[..., 5]
+    own = ((boxes[..., :3] + boxes[..., 3:] / 2.0) - (boxes[..., :3] - boxes[..., 3:] / 2.0)).clamp(min=0.0)
+    inter = own[..., 0] * own[..., 1] * own[..., 2]
+    assert bool((inter / (((vol + vol) - inter) + torch.tensor(1e-8)) > torch.tensor(thr)).all())   # a pick's IoU with itself, in fp32
+    want = RR.nms_3d(boxes, scores, -1, m, thr)
+    assert bool((want[:, -1] >= 0).all()) == filled and bool((want[:, -1] == -1).all()) == (not filled)
+    ones = torch.ones(b, n, dtype=torch.int32, device="cuda")
+    per_class = class_nms_3d(boxes.cuda(), scores.cuda(), ones, m, m, thr)
+    plain = nms_3d(boxes.cuda(), scores.cuda(), -1, m, thr)
+    assert torch.equal(per_class, plain)
+    assert torch.equal(plain.cpu(), want) and torch.equal(per_class.cpu(), want)
+
+
 # ---- refine_detections -------------------------------------------------------------------------------------------------------------
 
 def detection_inputs(b, r, c, seed, n=2000):

@@ -133,6 +133,7 @@ SIGNATURES = {
     "gspn_nearest_in_sets": [_I, _I, _I, _I, _P, _P, _P, _P, _P],
     "gspn_crop_linear_fwd": [_I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P],
     "gspn_crop_linear_bwd_side": [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P],
+    "gspn_crop_mean": [_I, _I, _I, _I, _I, _P, _P, _P, _P],
 }
 
 # entry points that do not return an int status: symbol -> (argtypes, restype)
@@ -161,7 +162,7 @@ SPECIAL = {
     "gspn_crop_linear_part_floats": ([_I, _I, _I, _I], _L),
 }
 
-ABI_VERSION = 15        # == GSPN_ABI_VERSION of include/gspn_hip.h this binding was written against
+ABI_VERSION = 16        # == GSPN_ABI_VERSION of include/gspn_hip.h this binding was written against
 
 _lib = None
 

@@ -14,7 +14,7 @@ from . import _lib as L
 from .roi import _constant, _take_rows, apply_box_delta
 from .spn_boxes import box_shrink
 
-__all__ = ["class_nms_3d", "classified_boxes", "refine_detections_batch", "refine_detections", "select_segmentation", "nearest_in_sets",
+__all__ = ["class_nms_3d", "first_max_column", "classified_boxes", "refine_detections_batch", "refine_detections", "select_segmentation", "nearest_in_sets",
            "unmold_segmentation"]
 
 
@@ -40,6 +40,15 @@ def class_nms_3d(boxes, scores, class_ids, max_per_class, max_output_size, iou_t
     return out
 
 
+def first_max_column(values):
+    """values (..., C) -> (...) int64: the FIRST maximal column, as tf.argmax picks it (torch.argmax leaves the choice among equal maxima
+    open).  Shared by classified_boxes (:832) and the inference driver's pick of each ROI's semantic probability (:1159)."""
+    c = values.shape[-1]
+    top = values.max(-1, keepdim=True).values
+    columns = torch.arange(c, device=values.device)
+    return torch.where(values == top, columns, columns.new_full((), c - 1)).min(-1).values      # the lowest column of the maximum
+
+
 def classified_boxes(rois, probs, deltas, pc, config):
     """:832-844 for the whole batch.  rois (B, R, 6), probs (B, R, C), deltas (B, R, C, 6), pc (B, N, 3) -> class_ids (B, R) int32: the
     FIRST maximal column of probs (tf.argmax; torch.argmax leaves the choice among equal maxima open), class_scores (B, R): that
@@ -52,9 +61,7 @@ def classified_boxes(rois, probs, deltas, pc, config):
     if tuple(rois.shape) != (b, r, 6) or tuple(deltas.shape) != (b, r, c, 6) or pc.shape[0] != b or pc.shape[2] != 3:
         raise ValueError("refine_detections: expected rois (B, R, 6), probs (B, R, C), deltas (B, R, C, 6) and pc (B, N, 3), got %s, %s, %s, %s"
                          % (tuple(rois.shape), tuple(probs.shape), tuple(deltas.shape), tuple(pc.shape)))
-    top = probs.max(-1, keepdim=True).values
-    columns = torch.arange(c, device=probs.device)
-    class_ids = torch.where(probs == top, columns, columns.new_full((), c - 1)).min(-1).values      # the lowest column of the maximum
+    class_ids = first_max_column(probs)
     class_scores = torch.gather(probs, 2, class_ids.unsqueeze(-1)).squeeze(-1)
     deltas_specific = torch.gather(deltas, 2, class_ids.reshape(b, r, 1, 1).expand(b, r, 1, 6)).squeeze(2)
     refined = apply_box_delta(rois, deltas_specific * _constant(config.BBOX_STD_DEV, rois.device))

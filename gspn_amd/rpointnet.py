@@ -9,13 +9,15 @@ roi.py and is re-exported here under the reference's names, and so is the detect
 (:818), select_segmentation (:986), unmold_segmentation (:1008), with the extensions class_nms_3d and nearest_in_sets -- which lives in
 detect.py.  The heads between the two -- the FPN layers (fpn_features, :1100-1104), classification_head (:915), segmentation_head (:946),
 crop_linear (their first layer fused with the crop) and the R-PointNet losses (:1251-1323, get_rpointnet_loss) -- live in heads.py and are
-re-exported here as callable parts.  The two drivers do not call them yet: rpointnet with mode='inference' or 'RPOINTNET' in TRAIN_MODULE,
-and get_loss with 'RPOINTNET' in TRAIN_MODULE, raise NotImplementedError."""
+re-exported here as callable parts.  Inference is its own driver, rpointnet_inference (:1064-1221 for mode='inference', with crop_mean for
+the per-ROI probabilities of :1146-1150), which lives in inference.py and is re-exported here.  rpointnet itself does not chain the parts:
+with mode='inference' or 'RPOINTNET' in TRAIN_MODULE, and get_loss with 'RPOINTNET' in TRAIN_MODULE, it raises NotImplementedError."""
 import torch
 
 from . import _lib as L
 from .detect import (class_nms_3d, nearest_in_sets, refine_detections, refine_detections_batch, select_segmentation,
                      unmold_segmentation)
+from .inference import crop_mean, rpointnet_inference
 from .heads import (classification_head, crop_linear, fpn_features, get_rpointnet_bbox_loss, get_rpointnet_class_loss, get_rpointnet_loss,
                     get_rpointnet_mask_loss, segmentation_head)
 from .proposal_head import chamfer_recons_loss
@@ -29,7 +31,7 @@ __all__ = ["Config", "box_shrink", "spn_target_gen", "spn_target_gen_batch", "ga
            "detection_target_gen_batch", "mask_selection_gen", "mask_selection_gen_batch", "points_cropping", "box_refinement", "apply_box_delta",
            "class_nms_3d", "refine_detections", "refine_detections_batch", "select_segmentation", "nearest_in_sets", "unmold_segmentation",
            "crop_linear", "classification_head", "segmentation_head", "fpn_features", "get_rpointnet_class_loss", "get_rpointnet_bbox_loss",
-           "get_rpointnet_mask_loss", "get_rpointnet_loss"]
+           "get_rpointnet_mask_loss", "get_rpointnet_loss", "crop_mean", "rpointnet_inference"]
 
 
 class Config(object):
@@ -117,12 +119,13 @@ def rpointnet(pc, color, pc_ins, group_label, group_indicator, seg_label, bbox_i
     """:1051.  pc, color (B, N, 3), pc_ins (B, NUM_GROUP, NUM_POINT_INS, 3), group_label, seg_label (B, N), group_indicator (B, NUM_GROUP),
     bbox_ins (B, NUM_GROUP, 6) -> end_points of shape_proposal_net plus group_label, seg_label, seg_label_per_group, bbox_ins.
     geometry / noise / valid_idx (extensions) are handed on to shape_proposal_net.
-    mode='inference' and 'RPOINTNET' in TRAIN_MODULE raise NotImplementedError: the stages they need (the ROI stage, fpn_features, the two
-    heads, refine_detections) exist as parts of this module, but this driver does not chain them yet."""
+    mode='inference' and 'RPOINTNET' in TRAIN_MODULE raise NotImplementedError: inference is rpointnet_inference, a function of its own;
+    the stages head training needs (the ROI stage, fpn_features, the two heads) exist as parts of this module, but no driver chains them
+    yet."""
     assert mode in ['training', 'inference']
     if mode == 'inference':
-        raise NotImplementedError("rpointnet: mode='inference' is not wired into this driver (fpn_features, classification_head, "
-                                  "segmentation_head and refine_detections are callable on their own)")
+        raise NotImplementedError("rpointnet: mode='inference' is not wired into this driver: call rpointnet_inference, which chains "
+                                  "fpn_features, classification_head, segmentation_head and refine_detections")
     if 'RPOINTNET' in config.TRAIN_MODULE:
         raise NotImplementedError("rpointnet: 'RPOINTNET' in TRAIN_MODULE is not wired into this driver (fpn_features, classification_head "
                                   "and segmentation_head are callable on their own)")

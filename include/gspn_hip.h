@@ -42,8 +42,9 @@ extern "C" {
  *  12: gspn_box_shrink / gspn_points_bbox / gspn_spn_target_gen.
  *  13: gspn_nms3d / gspn_box_point_count / gspn_sample_points_in_boxes / gspn_detection_target_select / gspn_crop_gather_grad.
  *  14: gspn_class_nms3d / gspn_nearest_in_sets.
- *  15: gspn_crop_linear_fwd / gspn_crop_linear_bwd_side (+ _part_floats). */
-#define GSPN_ABI_VERSION 15
+ *  15: gspn_crop_linear_fwd / gspn_crop_linear_bwd_side (+ _part_floats).
+ *  16: gspn_crop_mean. */
+#define GSPN_ABI_VERSION 16
 int gspn_dist_policy(void);
 int gspn_abi_version(void);
 
@@ -363,6 +364,16 @@ long gspn_crop_linear_part_floats(int b, int r, int p, int cout);
 int gspn_crop_linear_bwd_side(int b, int n, int r, int p, int cout, const float* dY, const int* idx, const float* pc, const float* center,
                               const float* rois, int normalize, const float* Wside, float* part, float* dWside, float* dbias,
                               float* dcenter_rows, void* stream);
+
+/* The per-ROI mean of a few gathered columns (gspn_amd/csrc/crop_mean.hip): what the inference path keeps of the fb_prob and sem_prob
+ * columns it crops with the features (:1144-1150), without widening the crop.  table (b,n,c) f32, idx (b,r,p) i32 scene-local (a value
+ * outside [0, n) is clamped, as in gspn_crop_linear_fwd) -> out (b,r,c) f32:
+ *     out[s, k, :] = (1/p) * sum_j table[s, idx[s, k, j], :]
+ * The all-zero index rows of padding ROIs average point 0 p times, as the reference does: there is no masking.  One workgroup per
+ * (scene, ROI); the sum is taken in double in an order that depends on the shape alone, divided by p in double and rounded to float once
+ * (no atomics: the same bits on every call, and a row that names one point p times returns that point's values exactly).
+ * 1 <= c <= 64 (GSPN_ERR_UNSUPPORTED beyond, before anything is launched), p >= 1, b * r < 2^31; no alignment beyond 4 bytes. */
+int gspn_crop_mean(int b, int n, int r, int p, int c, const float* table, const int* idx, float* out, void* stream);
 
 /* ---------------- utils/pointnet_util.py composition helpers --------------------------- */
 

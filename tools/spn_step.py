@@ -21,6 +21,11 @@
             with the crop (crop=, the T GEMM included) against points_cropping + the materialised heads, alternating in one process: both
             heads forward + backward at the training shape (64 ROIs x 256 points), forward only at the inference shapes (classification
             head 384 x 1024, segmentation head 100 x 1024); median / min / max and the largest relative difference between the two forms
+  infer     rpointnet_inference (gspn_amd/inference.py) with Config(istrain=False) -- 2048 seeds -> 1536 -> 384 ROIs x 1024 points, 100
+            detections -- on freshly initialised variables (DETECTION_MIN_CONFIDENCE 0, which they never reach): the whole call and its
+            stages (the same parts chained by hand with an event between them) with fused_crop off and on, alternating in one process; the
+            detections per scene; and crop_mean against the reference's own form of the per-ROI probabilities (concatenate the 20 columns
+            to the 1024 features, points_cropping at width 1044, split, mean), alternating, with their largest relative difference
 
 Prints one JSON line per (shape, measurement): median / min milliseconds over --iters timed runs after --warmup runs.
     python tools/spn_step.py --shapes 2x18000,8x32768
@@ -28,6 +33,7 @@ Prints one JSON line per (shape, measurement): median / min milliseconds over --
     python tools/spn_step.py --shapes 2x18000 --measures roi
     python tools/spn_step.py --shapes 2x18000 --measures detect
     python tools/spn_step.py --shapes 2x18000 --measures heads --iters 30
+    python tools/spn_step.py --shapes 2x18000 --measures infer --iters 5
 """
 import argparse
 import json
@@ -323,6 +329,103 @@ def measure_heads(a, shape, b, n, dev):
               flush=True)
 
 
+def measure_infer(a, shape, b, n, dev):
+    from gspn_amd import rpointnet as RP
+    from gspn_amd.inference import _point_probabilities
+    from gspn_amd.shape_proposal import valid_instances
+    cfg = RP.Config(istrain=False)
+    cfg.BATCH_SIZE, cfg.NUM_POINT, cfg.DETECTION_MIN_CONFIDENCE = b, n, 0
+    sc = {k: torch.from_numpy(v).to(dev) for k, v in
+          synth.spn_batch(a.kind, b, n, cfg.NUM_GROUP, cfg.NUM_POINT_INS, cfg.NUM_CATEGORY, seed0=7).items()}
+    args = (sc["pc"], sc["color"], sc["pc_ins"], sc["group_label"], sc["group_indicator"], sc["seg_label"], sc["bbox_ins"])
+    pc = sc["pc"]
+    valid = valid_instances(sc["group_indicator"])
+    seed = torch.zeros(1, dtype=torch.int64, device=dev)
+    m, p, d = cfg.SPN_NMS_MAX_SIZE_INFERENCE, cfg.NUM_POINT_INS_MASK, cfg.DETECTION_MAX_INSTANCES
+    tf_util.set_variable_store(tf_util.VariableStore(device=dev, seed=1))
+    whole = lambda fused: (lambda: RP.rpointnet_inference(*args, cfg, valid_idx=valid, seed=seed, fused_crop=fused))
+    ep = whole(False)()
+    found = (ep['detections'].abs().sum(-1) != 0).sum(1).tolist()
+    fused_ep = whole(True)()
+    diff = {k: float((fused_ep[k] - ep[k]).abs().max() / (ep[k].abs().max() + 1e-30)) for k in ('rpointnet_class_logits', 'rpointnet_bbox')}
+    res = timed_alternating({"materialised": whole(False), "fused": whole(True)}, a.warmup, a.iters)
+    print(json.dumps({"shape": shape, "kind": a.kind, "measure": "infer", "what": "rpointnet_inference", "seeds": cfg.NUM_SAMPLE, "rois": m,
+                      "points_per_roi": p, "detections_per_scene": found, "detections_per_scene_fused": (fused_ep['detections'].abs().sum(-1) != 0)
+                      .sum(1).tolist(), "max_relative_difference_fused_vs_materialised": diff, "iters": a.iters, **res}), flush=True)
+
+    def stages(fused, times):
+        """the driver's chain with an event behind every stage"""
+        marks = []
+
+        def mark(name):
+            e = torch.cuda.Event(enable_timing=True)
+            e.record()
+            marks.append((name, e))
+
+        def heads_input(rois, idx, r):
+            if fused:
+                return None, None, dict(pc=pc, pc_fea=fea, pc_center=e_p['center_pos'], rois=rois, idx=idx, normalize=cfg.NORMALIZE_CROP_REGION)
+            f, c, coord, _ = RP.points_cropping(pc, fea, e_p['center_pos'], rois, idx, r, p, cfg.NORMALIZE_CROP_REGION)
+            return coord, torch.cat((f, c), -1), None
+
+        with torch.no_grad():
+            mark("start")
+            e_p = RP.shape_proposal_net(pc, sc["color"], sc["pc_ins"], sc["group_label"], sc["group_indicator"], cfg.NUM_CATEGORY,
+                                        'shape_proposal_net', False, bn_decay=None, nsmp=cfg.NUM_SAMPLE, return_fullfea=True, mode='inference',
+                                        valid_idx=valid)
+            mark("shape_proposal_net")
+            sel = RP.nms_3d(e_p['bbox_ins_pred'], e_p['fb_prob'][:, :, 1], cfg.SPN_PRE_NMS_LIMIT, m, cfg.SPN_IOU_THRESHOLD, cfg.SPN_SCORE_THRESHOLD)
+            rois, idx = RP.mask_selection_gen_batch(RP.gather_selection(e_p['bbox_ins_pred'], sel, m), pc, m, cfg, True, seed)
+            mark("nms_and_mask_selection")
+            fea = RP.fpn_features(e_p, False, None)
+            mark("fpn_features")
+            means = RP.crop_mean(_point_probabilities(pc, e_p), idx)
+            mark("point_probabilities_and_crop_mean")
+            coord, feat, crop = heads_input(rois, idx, m)
+            logits, probs, deltas = RP.classification_head(coord, feat, cfg.NUM_CATEGORY, [128, 256, 512], [256, 256], False, None,
+                                                           'classification_head', crop=crop)
+            del coord, feat
+            mark("crop_and_classification_head")
+            sem = torch.gather(means[:, :, 1:], 2, logits.argmax(-1, keepdim=True)).squeeze(-1)
+            det = RP.refine_detections_batch(rois, probs, deltas, pc, means[:, :, 0].contiguous(), sem, cfg)
+            rois_f, idx_f = RP.mask_selection_gen_batch(det[:, :, :6], pc, d, cfg, False, seed + 1)
+            mark("refine_detections_and_mask_selection")
+            coord, feat, crop = heads_input(rois_f, idx_f, d)
+            mask = RP.segmentation_head(coord, feat, cfg.NUM_CATEGORY, [64, 64], [64, 128, 512], [256, 256], False, None, 'segmentation_head',
+                                        crop=crop)
+            RP.select_segmentation(torch.sigmoid(mask), det[:, :, 6])
+            mark("crop_and_segmentation_head")
+        marks[-1][1].synchronize()
+        for (_, e0), (name, e1) in zip(marks, marks[1:]):
+            times.setdefault(name, []).append(e0.elapsed_time(e1))
+
+    per_stage = {}
+    for fused in (False, True):
+        times = {}
+        for i in range(a.warmup + a.iters):
+            stages(fused, times if i >= a.warmup else {})
+        per_stage["fused" if fused else "materialised"] = {k: {"median_ms": round(sorted(v)[len(v) // 2], 4), "min_ms": round(min(v), 4),
+                                                                "max_ms": round(max(v), 4)} for k, v in times.items()}
+    print(json.dumps({"shape": shape, "kind": a.kind, "measure": "infer", "what": "stages", "iters": a.iters, **per_stage}), flush=True)
+
+    # crop_mean on the 1024-wide path against the reference's form at width 1044
+    with torch.no_grad():
+        fea = RP.fpn_features(ep, False, None)
+    table = _point_probabilities(pc, ep)
+    rois, idx = ep['rois'], ep['mask_selection_idx']
+
+    def reference_form():
+        wide = torch.cat((fea, table), -1)
+        cropped = RP.points_cropping(pc, wide, ep['center_pos'], rois, idx, m, p, cfg.NORMALIZE_CROP_REGION)[0]
+        return cropped[..., fea.shape[2]:].mean(2)
+
+    ours, theirs = RP.crop_mean(table, idx), reference_form()
+    res = timed_alternating({"crop_mean": lambda: RP.crop_mean(table, idx), "concat_crop_split_mean": reference_form}, a.warmup, a.iters)
+    print(json.dumps({"shape": shape, "kind": a.kind, "measure": "infer", "what": "crop_mean", "table": list(table.shape), "idx": list(idx.shape),
+                      "feature_channels": fea.shape[2], "iters": a.iters,
+                      "max_relative_difference": float((ours - theirs).abs().max() / (theirs.abs().max() + 1e-30)), **res}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--measures", default="step,full_fwd,nn,spn")
@@ -349,6 +452,8 @@ def main():
             measure_detect(a, shape, b, n, dev)
         if "heads" in measures:
             measure_heads(a, shape, b, n, dev)
+        if "infer" in measures:
+            measure_infer(a, shape, b, n, dev)
         if not set(measures) & {"step", "full_fwd", "nn"}:
             continue
         xyz = torch.from_numpy(synth.batch(a.kind, b, n)).to(dev)

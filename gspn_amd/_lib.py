@@ -134,6 +134,8 @@ SIGNATURES = {
     "gspn_crop_linear_fwd": [_I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P],
     "gspn_crop_linear_bwd_side": [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P],
     "gspn_crop_mean": [_I, _I, _I, _I, _I, _P, _P, _P, _P],
+    "gspn_tile_add": [_L, _I, _I, _P, _P, _P, _P],
+    "gspn_tile_sum": [_L, _I, _I, _P, _P, _P, _P],
 }
 
 # entry points that do not return an int status: symbol -> (argtypes, restype)
@@ -160,9 +162,10 @@ SPECIAL = {
     "gspn_deconv_bwd_kernel_work_bytes": ([_I, _I, _I, _I, _I, _I, _I, _I, _I], _L),
     "gspn_crop_gather_grad_part_floats": ([_I, _I, _I], _L),
     "gspn_crop_linear_part_floats": ([_I, _I, _I, _I], _L),
+    "gspn_tile_sum_part_floats": ([_L, _I, _I], _L),
 }
 
-ABI_VERSION = 16        # == GSPN_ABI_VERSION of include/gspn_hip.h this binding was written against
+ABI_VERSION = 17        # == GSPN_ABI_VERSION of include/gspn_hip.h this binding was written against
 
 _lib = None
 

@@ -8,6 +8,12 @@ layer is linear and per point, so it commutes with the gather (crop_linear, on c
 T is one GEMM over the B*N points instead of the B*R*P crop rows, the gathered rows are cout floats wide and the (B, R, P, C + 6) tensor
 is never written.  A head given crop=dict(...) runs its first layer that way, on the same variables as the materialised form.
 
+Two more opt-in forms, both on the variables of the plain ones.  The segmentation head's conv_post_0 reads concat(tile(global), local); it
+is linear, so tile_linear runs it as a product over the B*R*P local rows, a product over the B*R global rows and a broadcast add
+(gspn_tile_add / gspn_tile_sum of csrc/tile_linear.hip): segmentation_head(split_post=True) never builds the concatenation.  And both
+heads read the same crop, so shared_first_layers runs their two conv_prev_0 layers as ONE crop_linear on the weights concatenated along
+the output axis -- one T, one gather, one set of inverse lists -- and a head given crop=dict(..., first=rows) starts behind it.
+
 Static shapes, nothing reads a value back to the host: heads + get_rpointnet_loss + backward capture in a graph.CapturedStep.  No CPU
 fallback."""
 import torch
@@ -18,8 +24,8 @@ from .mlp import LayerParams, mlp_linear, mlp_stack
 from .pointnet_util import _mlp_layers
 from .roi import _crop_gather_grad, _Lists, points_cropping
 
-__all__ = ["crop_linear", "classification_head", "segmentation_head", "fpn_features", "get_rpointnet_class_loss", "get_rpointnet_bbox_loss",
-           "get_rpointnet_mask_loss", "get_rpointnet_loss"]
+__all__ = ["crop_linear", "tile_linear", "shared_first_layers", "declare_classification_head", "classification_head", "segmentation_head",
+           "fpn_features", "get_rpointnet_class_loss", "get_rpointnet_bbox_loss", "get_rpointnet_mask_loss", "get_rpointnet_loss"]
 
 CROP_LINEAR_MAX_COUT = 256          # CL_MAX_COUT of csrc/heads.hip: one float4 of the output row per lane, at most a wave per row
 
@@ -99,6 +105,66 @@ def crop_linear(pc, pc_fea, pc_center, rois, masks_selection_idx, lp, normalize_
     return _CropLinearSide.apply(T, pc_center, w_side, lp.biases, pc, rois, idx, bool(normalize_crop_region), _Lists(idx, n))
 
 
+# --------------------------------------------------------------------------- the layer behind concat(tile(global), local), split
+class _TileAdd(torch.autograd.Function):
+    """a (G*P, c), g (G, c) -> a[k*P + j] + g[k] (gspn_tile_add).  Backward: da = dy itself, dg = the per-group sum of dy in a fixed order
+    (gspn_tile_sum)."""
+
+    @staticmethod
+    def forward(ctx, a, g, p):
+        groups, c = g.shape
+        y = torch.empty_like(a)
+        with torch.cuda.device(a.device):
+            L.check(L.lib().gspn_tile_add(groups, p, c, L.ptr(a), L.ptr(g), L.ptr(y), L.stream()), "tile_add")
+        ctx.p = p
+        ctx.groups = groups
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        dy = dy.contiguous()
+        groups, p, c = ctx.groups, ctx.p, dy.shape[1]
+        dg = None
+        if ctx.needs_input_grad[1]:
+            lib = L.lib()
+            dg = torch.empty((groups, c), dtype=torch.float32, device=dy.device)
+            nfloats = int(lib.gspn_tile_sum_part_floats(groups, p, c))
+            part = torch.empty(nfloats, dtype=torch.float32, device=dy.device) if nfloats else None
+            with torch.cuda.device(dy.device):
+                L.check(lib.gspn_tile_sum(groups, p, c, L.ptr(dy), L.ptr(part), L.ptr(dg), L.stream()), "tile_sum")
+        return dy, dg, None
+
+
+def tile_linear(local_rows, global_rows, lp, p):
+    """The linear layer over concat(tile(global, p), local) without the concatenation.  local_rows (G*P, cl), global_rows (G, cg), lp: the
+    layer's LayerParams with weights (cg + cl, cout) in the reference's [global, local] order -> (G*P, cout), before batch norm and
+    activation:  y[g*P + j] = local[g*P + j] . W[cg:] + (global[g] . W[:cg] + bias).
+    Two mlp_linear products -- over the rows with zero bias, over the groups with the bias -- and gspn_tile_add; backward hands dY to the
+    local product as it is, its per-group sum (gspn_tile_sum, fixed order) to the global one, and mlp_linear's backward does the rest.
+    Raises NotImplementedError, before anything has run, for cout not a multiple of 4, cg, cl or cout > 1024, G*P >= 2^31 or weights that
+    are not contiguous and 16-byte aligned."""
+    local_rows = L.need(local_rows, torch.float32, 2, "local_rows")
+    global_rows = L.need(global_rows, torch.float32, 2, "global_rows")
+    p = int(p)
+    groups, cg = global_rows.shape
+    rows, cl = local_rows.shape
+    if p <= 0 or groups <= 0 or rows != groups * p:
+        raise ValueError("tile_linear: local_rows (G*P, cl) and global_rows (G, cg) with P = %d, got %s and %s"
+                         % (p, tuple(local_rows.shape), tuple(global_rows.shape)))
+    if lp.weights.dim() != 2 or lp.weights.shape[0] != cg + cl:
+        raise ValueError("tile_linear: the layer's weights must be (cg + cl, cout) = (%d, cout), got %s" % (cg + cl, tuple(lp.weights.shape)))
+    cout = lp.weights.shape[1]
+    most = tf_util._MLP_MAX_CHANNELS
+    if cout % 4 or cout > most or cg > most or cl > most or rows >= 2 ** 31:
+        raise NotImplementedError("tile_linear: cout a multiple of 4, cg, cl, cout <= %d, G*P < 2^31 (got cg %d, cl %d, cout %d, G*P %d)"
+                                  % (most, cg, cl, cout, rows))
+    if not (lp.weights.is_contiguous() and _aligned16(lp.weights) and _aligned16(lp.biases)):
+        raise NotImplementedError("tile_linear: the weights and the biases must be contiguous and 16-byte aligned")
+    y_local = mlp_linear(local_rows, cl, LayerParams(lp.weights[cg:], torch.zeros_like(lp.biases), False))
+    y_global = mlp_linear(global_rows, cg, LayerParams(lp.weights[:cg], lp.biases, False))
+    return _TileAdd.apply(y_local, y_global, p)
+
+
 # --------------------------------------------------------------------------- the heads
 def _pad4(rows):
     """(rows, c) with the row pitch the MLP kernels stage 16 bytes at a time (pad columns zero)"""
@@ -136,7 +202,12 @@ def _first_layers(pc, pc_fea, mlp_list, is_training, bn_decay, bn, crop, pool_ns
         cin = L.need(pc_fea, torch.float32, 4, "pc_fea").shape[3] + 3
     layers = _mlp_layers(mlp_list, cin, 'conv_prev_', bn)
     rows = None
-    if crop is not None:
+    if crop is not None and crop.get("first") is not None:          # conv_prev_0 has run outside (shared_first_layers), on these variables
+        rows = L.need(crop["first"], torch.float32, 2, "crop['first']")
+        if tuple(rows.shape) != (b * r * p, mlp_list[0]):
+            raise ValueError("crop['first'] must be (B*R*P, %d) = (%d, %d), got %s" % (mlp_list[0], b * r * p, mlp_list[0], tuple(rows.shape)))
+        layers, cin = layers[1:], rows.shape[1]
+    elif crop is not None:
         normalize = crop.get("normalize", True)
         try:
             y = crop_linear(crop["pc"], crop["pc_fea"], crop["pc_center"], crop["rois"], crop["idx"], layers[0], normalize)
@@ -164,13 +235,49 @@ def _conv1d_bn_relu(inputs, num_outputs, scope, is_training, bn_decay, bn):
     return torch.relu(y)
 
 
+def declare_classification_head(cin, num_category, mlp_list, mlp_list2, scope, bn=True):
+    """Creates (or finds) every variable of classification_head in the reference's order without running it and returns conv_prev_0's
+    LayerParams.  cin = C + 6, the width of the head's input rows.  What shared_first_layers needs of the segmentation head --
+    segmentation_head/conv_prev_0 -- can then be created before the classification head has run and still comes behind all of its
+    variables."""
+    with tf_util.variable_scope(scope):
+        first = _mlp_layers(mlp_list, cin, 'conv_prev_', bn)[0]
+        c = mlp_list[-1]
+        for i, num_out_channel in enumerate(mlp_list2):
+            tf_util._layer_params('conv_post_%d' % i, c, num_out_channel, [1, c, num_out_channel], True, 1e-3, None, False)
+            if bn:
+                with tf_util.variable_scope('conv_post_%d' % i), tf_util.variable_scope('bn'):
+                    tf_util._bn_variables(num_out_channel)
+            c = num_out_channel
+        tf_util._layer_params('conv_classify', c, num_category, [1, c, num_category], True, 1e-3, None, False)
+        tf_util._layer_params('conv_bbox_regress', c, num_category * 6, [1, c, num_category * 6], True, 1e-3, None, False)
+    return first
+
+
+def shared_first_layers(crop, cls_layer, seg_layer, is_training, bn_decay):
+    """conv_prev_0 of both heads over one crop as ONE crop_linear: the two layers' weights (C + 6, 128) and (C + 6, 64) and their biases are
+    concatenated along the output axis for the call (the variables stay two and get their gradients through the concatenation), the
+    (B, R, P, 192) result is split and each part goes through its own layer's batch norm and ReLU.  One T product, one gather, one side
+    backward and one set of inverse lists instead of two of each.  crop: the dict the heads take; cls_layer, seg_layer: the LayerParams of
+    classification_head/conv_prev_0 and segmentation_head/conv_prev_0 -> (cls_rows (B*R*P, 128), seg_rows (B*R*P, 64)), what
+    crop=dict(..., first=rows) takes.  Raises NotImplementedError, before anything has run, where crop_linear does."""
+    c_cls = cls_layer.weights.shape[1]
+    both = LayerParams(torch.cat((cls_layer.weights, seg_layer.weights), 1), torch.cat((cls_layer.biases, seg_layer.biases)), False)
+    y = crop_linear(crop["pc"], crop["pc_fea"], crop["pc_center"], crop["rois"], crop["idx"], both, crop.get("normalize", True))
+    y = y.reshape(-1, y.shape[3])
+    return (_bn_relu_rows(y[:, :c_cls].contiguous(), cls_layer, is_training, bn_decay),
+            _bn_relu_rows(y[:, c_cls:].contiguous(), seg_layer, is_training, bn_decay))
+
+
 def classification_head(pc, pc_fea, num_category, mlp_list, mlp_list2, is_training, bn_decay, scope, bn=True, crop=None):
     """:915-944.  pc (B, R, P, 3) = pc_coord_cropped, pc_fea (B, R, P, NFEA) = concat(pc_fea_cropped, pc_center_cropped) ->
     logits (B, R, num_category), probs (B, R, num_category), bbox_deltas (B, R, num_category, 6).
     Variables in the reference's order: conv_prev_%d, conv_post_%d, conv_classify, conv_bbox_regress.
     crop (extension) = dict(pc=(B, N, 3), pc_fea=(B, N, C), pc_center=(B, N, 3), rois=(B, R, 6), idx=(B, R, P) int32, normalize=bool): the
     inputs of points_cropping instead of its outputs; the first layer then runs as crop_linear -> stand-alone batch norm -> ReLU on the
-    same variables and pc / pc_fea may be None.  A shape crop_linear declines is cropped and takes the materialised path."""
+    same variables and pc / pc_fea may be None.  A shape crop_linear declines is cropped and takes the materialised path.
+    With crop['first'] = rows (B*R*P, mlp_list[0]) -- shared_first_layers' -- conv_prev_0 has run outside: its variables are still created
+    here, in their place, and the head starts at conv_prev_1."""
     with tf_util.variable_scope(scope):
         new_points, b, r, _ = _first_layers(pc, pc_fea, mlp_list, is_training, bn_decay, bn, crop, True)          # + reduce_max (:933)
         new_points = new_points.view(b, r, -1)
@@ -182,19 +289,31 @@ def classification_head(pc, pc_fea, num_category, mlp_list, mlp_list2, is_traini
         return logits, probs, bbox_deltas.reshape(-1, r, num_category, 6)
 
 
-def segmentation_head(pc, pc_fea, num_category, mlp_list, mlp_list2, mlp_list3, is_training, bn_decay, scope, bn=True, crop=None):
+def segmentation_head(pc, pc_fea, num_category, mlp_list, mlp_list2, mlp_list3, is_training, bn_decay, scope, bn=True, crop=None,
+                      split_post=False):
     """:946-978.  pc (B, R, P, 3), pc_fea (B, R, P, NFEA) -> masks (B, R, P, num_category).
     Variables in the reference's order: conv_prev_%d, conv_%d, conv_post_%d, conv_seg.  crop: as in classification_head.
-    The layer behind concat(tile(global), local) reads that concatenation materialised."""
+    The layer behind concat(tile(global), local), conv_post_0, reads that concatenation materialised; with split_post=True (extension) it
+    runs as tile_linear -> stand-alone batch norm -> ReLU on the same variables and the concatenation is never built.  A shape tile_linear
+    declines takes the materialised path."""
     with tf_util.variable_scope(scope):
         local_feat, b, r, p = _first_layers(pc, pc_fea, mlp_list, is_training, bn_decay, bn, crop, False)         # (B*R*P, mlp_list[-1])
         c_local = local_feat.shape[1]
         layers = _mlp_layers(mlp_list2, c_local, 'conv_', bn)
         global_feat = _stack(local_feat, c_local, layers, is_training, bn_decay, p)                               # (B*R, mlp_list2[-1])
         c_global = global_feat.shape[1]
-        new_points = torch.cat((global_feat.view(b * r, 1, c_global).expand(-1, p, -1), local_feat.view(b * r, p, c_local)), -1)
         layers = _mlp_layers(mlp_list3, c_global + c_local, 'conv_post_', bn)
-        new_points = _stack(new_points.reshape(b * r * p, c_global + c_local), c_global + c_local, layers, is_training, bn_decay)
+        new_points = None
+        if split_post and layers:
+            try:
+                y = tile_linear(local_feat, global_feat, layers[0], p)
+            except NotImplementedError:                  # a shape the kernels decline: the materialised concatenation, same variables
+                pass
+            else:
+                new_points = _stack(_bn_relu_rows(y, layers[0], is_training, bn_decay), y.shape[1], layers[1:], is_training, bn_decay)
+        if new_points is None:
+            new_points = torch.cat((global_feat.view(b * r, 1, c_global).expand(-1, p, -1), local_feat.view(b * r, p, c_local)), -1)
+            new_points = _stack(new_points.reshape(b * r * p, c_global + c_local), c_global + c_local, layers, is_training, bn_decay)
         new_points = new_points.view(b, r, p, -1)
         return tf_util.conv2d(new_points, num_category, [1, 1], padding='VALID', stride=[1, 1], scope='conv_seg', activation_fn=None)
 

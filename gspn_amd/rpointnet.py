@@ -10,8 +10,11 @@ roi.py and is re-exported here under the reference's names, and so is the detect
 detect.py.  The heads between the two -- the FPN layers (fpn_features, :1100-1104), classification_head (:915), segmentation_head (:946),
 crop_linear (their first layer fused with the crop) and the R-PointNet losses (:1251-1323, get_rpointnet_loss) -- live in heads.py and are
 re-exported here as callable parts.  Inference is its own driver, rpointnet_inference (:1064-1221 for mode='inference', with crop_mean for
-the per-ROI probabilities of :1146-1150), which lives in inference.py and is re-exported here.  rpointnet itself does not chain the parts:
-with mode='inference' or 'RPOINTNET' in TRAIN_MODULE, and get_loss with 'RPOINTNET' in TRAIN_MODULE, it raises NotImplementedError."""
+the per-ROI probabilities of :1146-1150), which lives in inference.py and is re-exported here.  Head training is its own driver too:
+rpointnet_head_training / rpointnet_heads_from_proposals (:1070-1115, :1198-1209 for TRAIN_MODULE == ['RPOINTNET']) and
+get_head_training_loss (:1325-1416 for it), which live in training.py and are re-exported here.  rpointnet itself does not chain the
+parts: with mode='inference' or 'RPOINTNET' in TRAIN_MODULE, and get_loss with 'RPOINTNET' in TRAIN_MODULE, it raises NotImplementedError
+and names the function to call."""
 import torch
 
 from . import _lib as L
@@ -19,19 +22,21 @@ from .detect import (class_nms_3d, nearest_in_sets, refine_detections, refine_de
                      unmold_segmentation)
 from .inference import crop_mean, rpointnet_inference
 from .heads import (classification_head, crop_linear, fpn_features, get_rpointnet_bbox_loss, get_rpointnet_class_loss, get_rpointnet_loss,
-                    get_rpointnet_mask_loss, segmentation_head)
+                    get_rpointnet_mask_loss, segmentation_head, shared_first_layers, tile_linear)
 from .proposal_head import chamfer_recons_loss
 from .roi import (apply_box_delta, box_point_count, box_refinement, detection_target_gen, detection_target_gen_batch, mask_selection_gen,
                   mask_selection_gen_batch, nms_3d, points_cropping, sample_points_in_boxes)
 from .shape_proposal import shape_proposal_net
 from .spn_boxes import box_shrink, points_bbox, spn_target_gen_batch
+from .training import get_head_training_loss, rpointnet_head_training, rpointnet_heads_from_proposals
 
 __all__ = ["Config", "box_shrink", "spn_target_gen", "spn_target_gen_batch", "gather_selection", "smooth_l1_loss", "get_spn_class_loss",
            "seg_label_per_group", "rpointnet", "get_loss", "nms_3d", "box_point_count", "sample_points_in_boxes", "detection_target_gen",
            "detection_target_gen_batch", "mask_selection_gen", "mask_selection_gen_batch", "points_cropping", "box_refinement", "apply_box_delta",
            "class_nms_3d", "refine_detections", "refine_detections_batch", "select_segmentation", "nearest_in_sets", "unmold_segmentation",
            "crop_linear", "classification_head", "segmentation_head", "fpn_features", "get_rpointnet_class_loss", "get_rpointnet_bbox_loss",
-           "get_rpointnet_mask_loss", "get_rpointnet_loss", "crop_mean", "rpointnet_inference"]
+           "get_rpointnet_mask_loss", "get_rpointnet_loss", "crop_mean", "rpointnet_inference", "tile_linear", "shared_first_layers",
+           "rpointnet_heads_from_proposals", "rpointnet_head_training", "get_head_training_loss"]
 
 
 class Config(object):
@@ -119,16 +124,15 @@ def rpointnet(pc, color, pc_ins, group_label, group_indicator, seg_label, bbox_i
     """:1051.  pc, color (B, N, 3), pc_ins (B, NUM_GROUP, NUM_POINT_INS, 3), group_label, seg_label (B, N), group_indicator (B, NUM_GROUP),
     bbox_ins (B, NUM_GROUP, 6) -> end_points of shape_proposal_net plus group_label, seg_label, seg_label_per_group, bbox_ins.
     geometry / noise / valid_idx (extensions) are handed on to shape_proposal_net.
-    mode='inference' and 'RPOINTNET' in TRAIN_MODULE raise NotImplementedError: inference is rpointnet_inference, a function of its own;
-    the stages head training needs (the ROI stage, fpn_features, the two heads) exist as parts of this module, but no driver chains them
-    yet."""
+    mode='inference' and 'RPOINTNET' in TRAIN_MODULE raise NotImplementedError: inference is rpointnet_inference and head training is
+    rpointnet_head_training, functions of their own."""
     assert mode in ['training', 'inference']
     if mode == 'inference':
         raise NotImplementedError("rpointnet: mode='inference' is not wired into this driver: call rpointnet_inference, which chains "
                                   "fpn_features, classification_head, segmentation_head and refine_detections")
     if 'RPOINTNET' in config.TRAIN_MODULE:
-        raise NotImplementedError("rpointnet: 'RPOINTNET' in TRAIN_MODULE is not wired into this driver (fpn_features, classification_head "
-                                  "and segmentation_head are callable on their own)")
+        raise NotImplementedError("rpointnet: 'RPOINTNET' in TRAIN_MODULE is not wired into this driver: call rpointnet_head_training (or "
+                                  "rpointnet_heads_from_proposals) with TRAIN_MODULE == ['RPOINTNET'], and get_head_training_loss")
     if 'SPN' not in config.TRAIN_MODULE:
         raise NotImplementedError("rpointnet: TRAIN_MODULE must be ['SPN']")
     if not config.USE_COLOR:
@@ -148,9 +152,16 @@ def rpointnet(pc, color, pc_ins, group_label, group_indicator, seg_label, bbox_i
 def get_loss(end_points, config, alpha, smpw, mode='training'):
     """:1325, the five SPN terms (:1328-1381, :1395).  smpw (B, N): per-point weights of the semantic loss.  Returns (loss, end_points);
     end_points gains spn_match, sem_labels, spn_class_loss, recons_loss, shift_loss, sem_loss, kl_loss, loss.
-    The R-PointNet terms (:1383-1392) are get_rpointnet_loss, which this driver does not add yet: 'RPOINTNET' in TRAIN_MODULE raises."""
+    The R-PointNet terms (:1383-1392) are get_rpointnet_loss, which get_head_training_loss adds for TRAIN_MODULE == ['RPOINTNET']; here
+    'RPOINTNET' in TRAIN_MODULE raises."""
     if 'RPOINTNET' in config.TRAIN_MODULE or 'SPN' not in config.TRAIN_MODULE:
-        raise NotImplementedError("get_loss: only TRAIN_MODULE == ['SPN'] is implemented (the R-PointNet terms are get_rpointnet_loss)")
+        raise NotImplementedError("get_loss: only TRAIN_MODULE == ['SPN'] is implemented (for ['RPOINTNET'] call get_head_training_loss, "
+                                  "which adds the R-PointNet terms of get_rpointnet_loss)")
+    return _spn_loss_terms(end_points, config, alpha, smpw)
+
+
+def _spn_loss_terms(end_points, config, alpha, smpw):
+    """the body get_loss and get_head_training_loss share: the five SPN terms (:1328-1381), their sum (:1395) and the keys of :1405-1414"""
     nsmp_ins = config.NUM_POINT_INS
     pc_ins_centered_seed = L.need(end_points['pc_ins_centered_seed'], torch.float32, 4, "pc_ins_centered_seed")
     bbox_size = points_bbox(pc_ins_centered_seed)[:, :, 3:].unsqueeze(2)                                  # (B, nsmp, 1, 3)

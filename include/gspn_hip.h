@@ -43,8 +43,9 @@ extern "C" {
  *  13: gspn_nms3d / gspn_box_point_count / gspn_sample_points_in_boxes / gspn_detection_target_select / gspn_crop_gather_grad.
  *  14: gspn_class_nms3d / gspn_nearest_in_sets.
  *  15: gspn_crop_linear_fwd / gspn_crop_linear_bwd_side (+ _part_floats).
- *  16: gspn_crop_mean. */
-#define GSPN_ABI_VERSION 16
+ *  16: gspn_crop_mean.
+ *  17: gspn_tile_add / gspn_tile_sum (+ _part_floats). */
+#define GSPN_ABI_VERSION 17
 int gspn_dist_policy(void);
 int gspn_abi_version(void);
 
@@ -374,6 +375,24 @@ int gspn_crop_linear_bwd_side(int b, int n, int r, int p, int cout, const float*
  * (no atomics: the same bits on every call, and a row that names one point p times returns that point's values exactly).
  * 1 <= c <= 64 (GSPN_ERR_UNSUPPORTED beyond, before anything is launched), p >= 1, b * r < 2^31; no alignment beyond 4 bytes. */
 int gspn_crop_mean(int b, int n, int r, int p, int c, const float* table, const int* idx, float* out, void* stream);
+
+/* ---------------- a linear layer over concat(tile(global), local), split (gspn_amd/csrc/tile_linear.hip) -------------------------------
+ * segmentation_head's conv_post_0 (:966-970) reads concat(tile(global (groups, cg), p), local (groups*p, cl)).  It is linear, so
+ *     y[g*p + j, :] = local[g*p + j, :] . W[cg:]  +  (global[g, :] . W[:cg] + bias)
+ * two gspn_mlp_fwd launches and the broadcast add below; the concatenation is never written, and the gradient of the global product is the
+ * per-group sum of dY.  A, Y, dY (groups*p, c), G, dG (groups, c), all contiguous with row pitch c.
+ * c a multiple of 4 and <= GSPN_MLP_MAX_CHANNELS, groups * p < 2^31, every pointer 16-byte aligned: GSPN_ERR_UNSUPPORTED otherwise, before
+ * anything is launched.  fp32, no atomics, no host synchronisation. */
+
+/* Y[g*p + j, :] = A[g*p + j, :] + G[g, :]: one fp32 add per element, the bits of the broadcast add.  Y == A is allowed. */
+int gspn_tile_add(long groups, int p, int c, const float* A, const float* G, float* Y, void* stream);
+
+/* dG[g, :] = sum_j dY[g*p + j, :], summed in double in an order that depends on the shape alone and rounded to float once: the same bits on
+ * every call, and p equal rows return p * row exactly when p is a power of two.  With few groups the rows of a group are spread over
+ * several workgroups, which write double partials into part (gspn_tile_sum_part_floats floats, 16-byte aligned; 0 -- part may then be
+ * NULL -- when the shape needs none or is not taken); a second kernel adds them in workgroup order in double. */
+long gspn_tile_sum_part_floats(long groups, int p, int c);
+int gspn_tile_sum(long groups, int p, int c, const float* dY, float* part, float* dG, void* stream);
 
 /* ---------------- utils/pointnet_util.py composition helpers --------------------------- */
 

@@ -34,6 +34,7 @@ Prints one JSON line per (shape, measurement): median / min milliseconds over --
     python tools/spn_step.py --shapes 2x18000 --measures detect
     python tools/spn_step.py --shapes 2x18000 --measures heads --iters 30
     python tools/spn_step.py --shapes 2x18000 --measures infer --iters 5
+    python tools/spn_step.py --shapes 2x18000 --measures train_heads --iters 10
 """
 import argparse
 import json
@@ -426,6 +427,102 @@ def measure_infer(a, shape, b, n, dev):
                       "max_relative_difference": float((ours - theirs).abs().max() / (theirs.abs().max() + 1e-30)), **res}), flush=True)
 
 
+def measure_train_heads(a, shape, b, n, dev):
+    """one head-training step -- the frozen proposal net, rpointnet_heads_from_proposals, get_head_training_loss, backward -- in the four
+    forms, alternating; and segmentation_head's forward alone at the inference shape with and without split_post.  A freshly initialised
+    proposal net matches no ground truth and the step would train on padding alone, so the proposals are planted as in
+    tests/test_gpu_head_training.py: the first NUM_GROUP seeds carry the foreground ground-truth boxes of non-zero size, the others small cubes about points
+    of the scene (a few device operations inside the timed step, the same for every form)."""
+    from gspn_amd import rpointnet as RP
+    from gspn_amd.shape_proposal import valid_instances
+    cfg = RP.Config()
+    cfg.BATCH_SIZE, cfg.NUM_POINT, cfg.TRAIN_MODULE = b, n, ['RPOINTNET']
+    sc = {k: torch.from_numpy(v).to(dev) for k, v in
+          synth.spn_batch(a.kind, b, n, cfg.NUM_GROUP, cfg.NUM_POINT_INS, cfg.NUM_CATEGORY, seed0=7).items()}
+    pc = sc["pc"]
+    valid = valid_instances(sc["group_indicator"])
+    noise = torch.randn(b, cfg.NUM_SAMPLE, 256, device=dev)
+    seed = torch.zeros(1, dtype=torch.int64, device=dev)
+    store = tf_util.set_variable_store(tf_util.VariableStore(device=dev, seed=1))
+    heads_of = ("fpn", "classification_head/", "segmentation_head/")
+    per_group = RP.seg_label_per_group(sc["seg_label"], sc["group_label"], cfg.NUM_GROUP)
+    # (a group of one point has a box of size 0: as an ROI it would divide its crop by 0, here as in the reference -- not planted)
+    fg = ((per_group > 0) & (sc["bbox_ins"][:, :, 3:].amin(-1) > 0)).unsqueeze(-1)
+    at = (torch.arange(cfg.NUM_SAMPLE, device=dev) * 61 + 7) % n
+    score = torch.linspace(0.99, 0.01, cfg.NUM_SAMPLE, device=dev).expand(b, -1)
+    last = {}
+
+    def run(name, **switches):
+        def fn():
+            for v in store.parameters():
+                v.grad = None
+            with torch.no_grad():
+                ep = RP.shape_proposal_net(pc, sc["color"], sc["pc_ins"], sc["group_label"], sc["group_indicator"], cfg.NUM_CATEGORY,
+                                           'shape_proposal_net', False, bn_decay=None, nsmp=cfg.NUM_SAMPLE, return_fullfea=True, mode='training',
+                                           noise=noise, valid_idx=valid)
+            cubes = torch.cat((pc[:, at], torch.full((b, cfg.NUM_SAMPLE, 3), 0.3, device=dev)), -1)
+            ep['bbox_ins_pred'] = torch.cat((torch.where(fg, sc["bbox_ins"], cubes[:, :cfg.NUM_GROUP]), cubes[:, cfg.NUM_GROUP:]), 1)
+            ep['fb_prob'] = torch.stack((1 - score, score), -1)
+            ep = RP.rpointnet_heads_from_proposals(ep, pc, sc["group_label"], sc["seg_label"], sc["bbox_ins"], cfg, True, 0.5, seed=seed,
+                                                   **switches)
+            loss, ep = RP.get_head_training_loss(ep, cfg, 1.0, sc["smpw"])
+            loss.backward()
+            last[name] = (loss.detach(), {k: v.grad for k, v in store.named_parameters() if k.startswith(heads_of)}, ep)
+        return fn
+
+    fns = {"materialised": run("materialised"), "fused_crop": run("fused_crop", fused_crop=True),
+           "shared_first": run("shared_first", fused_crop=True, shared_first=True),
+           "split_post": run("split_post", fused_crop=True, shared_first=True, split_post=True)}
+    for fn in fns.values():
+        fn()
+    loss0, grads0, ep0 = last["materialised"]
+    for name, (loss, grads, _) in last.items():              # a difference of NaNs would read as 0
+        if not (bool(torch.isfinite(loss)) and all(bool(torch.isfinite(g).all()) for g in grads.values())):
+            raise RuntimeError("train_heads: the %s form returned a loss or a gradient that is not finite" % name)
+    valid_rois = ep0['rois'].abs().sum(-1) != 0
+    diffs = {}
+    for name in list(fns)[1:]:
+        loss, grads, _ = last[name]
+        worst = 0.0
+        for k, g0 in grads0.items():
+            beta = k.rsplit("/", 1)[0] + "/bn/beta"              # biases in front of a batch norm: true gradient 0, judged on beta's scale
+            scale = grads0[beta] if k.endswith("/biases") and beta in grads0 else g0
+            worst = max(worst, float((grads[k] - g0).abs().max() / (scale.abs().max() + 1e-30)))
+        diffs[name] = {"loss": float((loss - loss0).abs() / loss0.abs()), "parameter_gradients": worst}
+    res = timed_alternating(fns, a.warmup, a.iters)
+    print(json.dumps({"shape": shape, "kind": a.kind, "measure": "train_heads", "what": "step: proposal net (frozen) + heads + loss + backward",
+                      "seeds": cfg.NUM_SAMPLE, "rois": cfg.TRAIN_ROIS_PER_IMAGE, "points_per_roi": cfg.NUM_POINT_INS_MASK,
+                      "positive_rois_per_scene": (valid_rois & (ep0['target_class_ids'] > 0)).sum(1).tolist(),
+                      "negative_rois_per_scene": (valid_rois & (ep0['target_class_ids'] == 0)).sum(1).tolist(), "loss": float(loss0),
+                      "max_relative_difference_vs_materialised": diffs, "iters": a.iters, **res}), flush=True)
+    del last, fns
+    for v in store.parameters():
+        v.grad = None
+
+    # segmentation_head forward alone at the inference shape, on materialised inputs built outside the timed region
+    r, p, c = 100, 1024, a.crop_channels
+    gen = torch.Generator().manual_seed(65)
+    coord = (torch.rand(b, r, p, 3, generator=gen) - 0.5).to(dev)
+    feat = torch.randn(b, r, p, c + 3, generator=gen).to(dev)
+    tf_util.set_variable_store(tf_util.VariableStore(device=dev, seed=1))
+    out = {}
+
+    def seg(split):
+        def fn():
+            with torch.no_grad():
+                out[split] = RP.segmentation_head(coord, feat, cfg.NUM_CATEGORY, [64, 64], [64, 128, 512], [256, 256], False, None,
+                                                  'segmentation_head', split_post=split)
+        return fn
+
+    fns = {"materialised_concat": seg(False), "split_post": seg(True)}
+    for fn in fns.values():
+        fn()
+    diff = float((out[True] - out[False]).abs().max() / (out[False].abs().max() + 1e-30))
+    res = timed_alternating(fns, a.warmup, a.iters)
+    print(json.dumps({"shape": shape, "kind": a.kind, "measure": "train_heads", "what": "segmentation_head forward alone", "rois": r,
+                      "points_per_roi": p, "input_channels": c + 6, "max_relative_difference": diff, "iters": a.iters, **res}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--measures", default="step,full_fwd,nn,spn")
@@ -454,6 +551,8 @@ def main():
             measure_heads(a, shape, b, n, dev)
         if "infer" in measures:
             measure_infer(a, shape, b, n, dev)
+        if "train_heads" in measures:
+            measure_train_heads(a, shape, b, n, dev)
         if not set(measures) & {"step", "full_fwd", "nn"}:
             continue
         xyz = torch.from_numpy(synth.batch(a.kind, b, n)).to(dev)

@@ -22,14 +22,14 @@ FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=
          "-Wall", "-Wno-unused-function"]
 
 
-def _hipcc():
+def hipcc_path():
     for c in (os.environ.get("HIPCC"), "/opt/rocm/bin/hipcc", "hipcc"):
         if c and (os.path.isabs(c) and os.path.exists(c) or not os.path.isabs(c)):
             return c
     return "hipcc"
 
 
-def _newer(target, deps):
+def newer(target, deps):
     if not os.path.exists(target):
         return True
     t = os.path.getmtime(target)
@@ -62,13 +62,13 @@ def build(force=False, verbose=False, policy=None, variant=None, extra_flags=())
         flags += list(extra_flags)
         obj_dir, lib_path = os.path.join(OBJ, "v_" + variant), os.path.join(LIBDIR, "libgspn_hip_%s.so" % variant)
     os.makedirs(obj_dir, exist_ok=True)
-    hipcc = _hipcc()
+    hipcc = hipcc_path()
     jobs = []
     objs = []
     for s in srcs:
         o = os.path.join(obj_dir, os.path.basename(s)[:-4] + ".o")
         objs.append(o)
-        if force or _newer(o, [s] + hdrs):
+        if force or newer(o, [s] + hdrs):
             jobs.append([hipcc] + flags + ["-c", s, "-o", o])
 
     def run(cmd):
@@ -82,7 +82,7 @@ def build(force=False, verbose=False, policy=None, variant=None, extra_flags=())
 
     with ThreadPoolExecutor(max_workers=min(8, max(1, len(jobs)))) as ex:
         list(ex.map(run, jobs))
-    if force or jobs or _newer(lib_path, objs):
+    if force or jobs or newer(lib_path, objs):
         run([hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", lib_path] + objs)
     return lib_path
 

@@ -104,6 +104,7 @@ __global__ __launch_bounds__(256) void fwd_short_kernel(int rows, int cin, int c
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) { bv[nt] = bias ? bias[n0 + NT * l31 + nt] : 0.f; csum[nt] = csq[nt] = 0.f; }
     __syncthreads();
+    // (one trip at most as shipped: gspn_fwd_short_go launches rows / 32 >= ntiles workgroups, so the step, the prefetch of a next tile and the trailing barrier never run)
     for (int tile = (int)blockIdx.x; tile < ntiles; tile += (int)gridDim.x) {
         const int m0 = tile * 32 * MT;
 #pragma unroll

@@ -19,49 +19,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
                                                     (8192, 64, 64, True, True), (2048, 192, 96, True, True), (1024, 128, 256, True, False),
                                                     (64, 64, 32, False, True), (4032, 256, 64, True, False)])
 def test_short_forward_against_fp64(rows, cin, cout, act, pool):
-    from gspn_amd import _lib as L
-    lib = L.lib()
-    dev = torch.device("cuda", 0)
-    gen = torch.Generator(device=dev).manual_seed(rows + cin)
-    X = torch.randn(rows, cin + 4, device=dev, generator=gen)                 # padded pitch: ldx > cin
-    W = torch.randn(cin, cout, device=dev, generator=gen) / cin ** 0.5
-    bias = torch.randn(cout, device=dev, generator=gen) * 0.1
-    sc = (torch.rand(cin, device=dev, generator=gen) + 0.5) if act else None
-    sh = (torch.randn(cin, device=dev, generator=gen) * 0.3) if act else None
-    if act:
-        sc[::7] = -sc[::7]                                                    # negative scales are legal (gamma < 0)
-    Y = torch.full((rows, cout + 4), float("nan"), device=dev)               # ldy > cout: the pad columns must stay untouched
-    nst = int(lib.gspn_mlp_fwd_stats_bytes(rows, cout)) // 4
-    stats = torch.full((nst,), float("nan"), device=dev)
-    if pool:
-        Xq = torch.round(X * 2) / 2                                           # quantised inputs and weights: tied maxima inside a pool group occur
-        X = Xq.contiguous()
-        W = (torch.round(W * 8) / 8).contiguous()
-    vmax = torch.full((rows // 32, cout), float("nan"), device=dev) if pool else None
-    amax = torch.full((rows // 32, cout), -1, dtype=torch.int32, device=dev) if pool else None
-    st = L.stream()
-    if pool:
-        L.check(lib.gspn_mlp_fwd_pool32(rows, cin, cout, L.ptr(X), cin + 4, L.ptr(sc), L.ptr(sh), L.ptr(W), L.ptr(bias), L.ptr(Y), cout + 4, L.ptr(stats),
-                                        L.ptr(vmax), L.ptr(amax), st), "fwd")
-    else:
-        L.check(lib.gspn_mlp_fwd(rows, cin, cout, L.ptr(X), cin + 4, L.ptr(sc), L.ptr(sh), L.ptr(W), L.ptr(bias), L.ptr(Y), cout + 4, L.ptr(stats), st), "fwd")
-    torch.cuda.synchronize()
-    A = X[:, :cin]
-    A = torch.relu((A * sc + sh).double()) if act else A.double()            # two fp32 roundings, as tf.nn.batch_normalization's x*scale + shift
-    ref = A @ W.double() + bias.double()
-    got = Y[:, :cout]
-    assert bool(torch.isnan(Y[:, cout:]).all())
-    assert float((got.double() - ref).abs().max()) <= 1e-5 * float(ref.abs().max())
-    parts = stats.view(-1, 2, cout).double()
-    assert bool(torch.isfinite(parts).all())
-    tot = parts.sum(0)
-    assert float((tot[0] - ref.sum(0)).abs().max()) <= 1e-5 * float(ref.abs().sum(0).max())
-    assert float((tot[1] - (ref * ref).sum(0)).abs().max()) <= 1e-5 * float((ref * ref).sum(0).max())
-    if pool:
-        g = got.reshape(rows // 32, 32, cout)
-        mx = g.max(1).values
-        first = (g == mx.unsqueeze(1)).float().argmax(1).int()                # the FIRST row that reaches the maximum (the reference's strict '>')
-        assert torch.equal(vmax, mx) and torch.equal(amax, first)
+    from tests.test_gpu_mlp_instances import check_forward        # this test's former body, with the shape's alignment and pitches as parameters
+    check_forward(rows, cin, cout, act, pool)
 
 
 def test_short_forward_is_deterministic():

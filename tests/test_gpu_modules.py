@@ -121,7 +121,8 @@ def test_fp_module_matches_oracle(b, n1, n2, c1, c2, mlp):
         assert rel_err(t1.grad, p1r.grad) < 1e-4
 
 
-@pytest.mark.parametrize("b,n1,n2,c1,c2,mlp", [(2, 4096, 512, 3, 64, [64, 64, 64]), (1, 1500, 200, 0, 32, [32, 16]), (2, 900, 128, 4, 128, [64, 32])])
+@pytest.mark.parametrize("b,n1,n2,c1,c2,mlp", [(2, 4096, 512, 3, 64, [64, 64, 64]), (1, 1500, 200, 0, 32, [32, 16]), (2, 900, 128, 4, 128, [64, 32]),
+                                                   (2, 1024, 256, 0, 16, [256, 128])])       # 256 columns: preagg_fwd16_kernel<3, 4>
 def test_fp_module_preaggregated_first_layer(b, n1, n2, c1, c2, mlp, monkeypatch):
     """FP module whose skip link carries no gradient and has <= 4 columns (the last FP level: raw colours): the first layer's
     interpolated part is multiplied on the n2 sparse points (mlp.PREAGG).  Against the float64 composition and against the path that

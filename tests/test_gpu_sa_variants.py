@@ -216,6 +216,8 @@ def test_three_nn_metre_scale_rooms(n, m, offset):
     ("U", 3, 1500, 8, 100, 0.3, 16, [32, 48], True),
     ("U", 2, 1024, 20, 64, 0.3, 32, [64, 32], True),
     ("U", 2, 512, 128, 64, 0.8, 32, [128, 128, 256], False),     # SA3-shaped: 132 input columns do not fit the streaming forward -> materialised rows
+    ("U", 2, 1024, 3, 256, 0.3, 16, [128, 64], True),            # a first layer wider than 64 columns: mlp_fwd_stream_kernel<128, 4, true, false>
+    ("U", 2, 1024, 64, 128, 0.4, 16, [128, 64], True),           # ... and with 68 gathered columns <128, 2, true, false>
 ])
 def test_fused_sa_front_end_equals_the_materialised_path(kind, b, n, c, npoint, radius, ns, mlp, expect_gather, monkeypatch):
     """the first conv2d gathers its rows from (b,n,c) features + 20 bytes per grouped row (gspn_sa_rel) instead of reading

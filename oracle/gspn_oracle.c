@@ -362,6 +362,7 @@ void oracle_three_interpolate_grad(int b, int n, int c, int m, const float *grad
  *   CPU twin  tf_nndistance.cpp:21-43 (nnsearch): same rule, unfused arithmetic.
  * ---------------------------------------------------------------------------------------- */
 static void nn_dir(int b, int n, int m, const float *xyz1, const float *xyz2, float *dist, int *idx, int cuda) {
+#pragma omp parallel for collapse(2) schedule(static) if (g_mt)
     for (int i = 0; i < b; i++)
         for (int j = 0; j < n; j++) {
             float x1 = xyz1[((size_t)i * n + j) * 3 + 0], y1 = xyz1[((size_t)i * n + j) * 3 + 1], z1 = xyz1[((size_t)i * n + j) * 3 + 2];

@@ -46,3 +46,26 @@ def test_executed_reads_every_process_s_trace_and_expect_gates(tmp_path, monkeyp
     rec.write_text("[executed after]\nk<1, false>\nk<1, true>\n")
     assert K.main(["executed", str(tmp_path / "trace"), "--expect", str(rec)]) == 1
     assert "k<1, true>" in capsys.readouterr().out.split("in no trace")[1]
+
+
+def test_the_two_records_partition_the_compiled_list():
+    """profiles/kernel_coverage_geometry.txt covers exactly what profiles/kernel_coverage_mlp.txt compiles and does not account for; every
+    instantiation is in one of [executed after] and [not executed], what ran before still runs, and each [not executed] line has its reason"""
+    K = _tool()
+    mlp = os.path.join(ROOT, "profiles", "kernel_coverage_mlp.txt")
+    geo = os.path.join(ROOT, "profiles", "kernel_coverage_geometry.txt")
+    compiled = K.read_section(mlp, "compiled")
+    theirs = K.read_section(mlp, "executed after") + K.read_section(mlp, "not executed")
+    before, after, never = (K.read_section(geo, s) for s in ("executed before", "executed after", "not executed"))
+    assert len(set(after + never)) == len(after) + len(never)
+    assert sorted(theirs + after + never) == sorted(compiled)
+    assert set(before) <= set(after)
+    for want in ["crop_linear_fwd_kernel<%d>" % l for l in (2, 4, 8, 64)] + ["crop_linear_bwd_side_kernel<%d>" % l for l in (2, 4, 8, 64)]:
+        assert "(anonymous namespace)::" + want in after
+    for want in ["three_nn_nested_kernel<%d>" % l for l in (1, 2, 4)] + ["three_nn_grid_kernel<32>", "nm_distance_kernel<2>"]:
+        assert want in after
+    assert "(anonymous namespace)::box_point_count_kernel<8>" in after
+    with open(geo) as fh:
+        body = fh.read().split("\n[not executed]\n")[1]
+    lines = [l for l in body.splitlines() if l.strip()]
+    assert len(lines) == len(never) and all(len(l.split("#", 1)[1].strip()) > 20 for l in lines)

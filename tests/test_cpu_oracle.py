@@ -295,7 +295,8 @@ def test_openmp_mode_does_not_change_results():
             w = np.full(d.shape, 1 / 3, np.float32)
             ip = O.three_interpolate(pts[:, :90].copy(), i3, w)
             ig = O.three_interpolate_grad(pts[:, :90].copy(), i3, w, ip)
-            res.append((idx, cnt, d, i3, gp, gg, ip, ig))
+            nn = O.nn_distance(xyz, q) + O.nn_distance(xyz, q, cpu_twin=True)
+            res.append((idx, cnt, d, i3, gp, gg, ip, ig) + nn)
         finally:
             O.set_mt(False)
     for a, b_ in zip(*res):

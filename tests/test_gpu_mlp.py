@@ -21,9 +21,12 @@ def rel_err(a, b):
 
 
 def make_params(chans, cin, seed, bn=True):
+    """bn: one bool for the whole stack, or one per layer.  Draw order per layer: w, b, then gamma, beta of a batch-normalised layer only"""
+    bns = [bool(bn)] * len(chans) if isinstance(bn, bool) else [bool(v) for v in bn]
+    assert len(bns) == len(chans)
     g = torch.Generator().manual_seed(seed)
     ps = []
-    for c in chans:
+    for c, bn in zip(chans, bns):
         lim = (6.0 / (cin + c)) ** 0.5
         p = {"w": (torch.rand(cin, c, generator=g, dtype=torch.float64) * 2 - 1) * lim,
              "b": (torch.rand(c, generator=g, dtype=torch.float64) - 0.5) * 0.2, "bn": bn}
@@ -120,32 +123,50 @@ def fragile_entries(zs, ns):
     return near | frag_rows[win_row] | win_small, frag_rows
 
 
-def check_stack(rows, ld, cin, chans, ns, training, ref_device="cpu", neg_gamma=False, max_fragile=0.02, place=None, results=None):
+def _leaves(ps, ref_device):
+    """the float64 parameters on `ref_device`, the differentiable ones (gamma / beta: batch-normalised layers only) as leaves"""
+    for p in ps:
+        for k in p:
+            if torch.is_tensor(p[k]):
+                p[k] = p[k].to(ref_device)
+        for k in ("w", "b", "gamma", "beta"):
+            if k in p:
+                p[k] = p[k].clone().requires_grad_(True)
+
+
+def bias_err(lp, p):
+    """error of a layer's bias gradient as a fraction of its scale.  A bias in front of a batch norm has a true gradient of 0 up to rounding: it is
+    held to the weight gradient's scale.  Without batch norm it is a gradient like any other: relative to its own largest element."""
+    diff = float((lp.biases.grad.double().cpu() - p["b"].grad.cpu()).abs().max())
+    if not p["bn"]:
+        return diff / (float(p["b"].grad.abs().max()) + 1e-30)
+    scale = max(float(p["w"].grad.abs().max()), 1e-6)
+    return diff / max(scale, float(p["b"].grad.abs().max()))
+
+
+def check_stack(rows, ld, cin, chans, ns, training, ref_device="cpu", neg_gamma=False, max_fragile=0.02, place=None, results=None, bn=True):
     """mlp_stack forward + backward against oracle/mlp_ref.py evaluated in float64 on `ref_device`.
+    bn: one bool, or one per layer (make_params): gamma / beta gradients and moving statistics are those of the batch-normalised layers.
     place (one of PLACES): the operands handed to the stack through misaligned() -- same values, 4-byte aligned only; the float64 side is the same.
     results (a dict): receives the GPU's output, dX and parameter gradients, for a caller that compares two runs of one case."""
     from gspn_amd.mlp import mlp_stack
     g = torch.Generator().manual_seed(rows + cin)
     x64 = torch.randn(rows, ld, generator=g, dtype=torch.float64)
     x64[:, cin:] = 0
-    ps = make_params(chans, cin, seed=cin)
+    ps = make_params(chans, cin, seed=cin, bn=bn)
     if neg_gamma:
         ps[-1]["gamma"][::3] *= -1.0             # every third channel of the last layer: negative BN scale (the pool then takes the group minimum of y)
     if not training:
-        for p in ps:
+        for p in (p for p in ps if p["bn"]):
             p["moving_mean"] = torch.randn(p["w"].shape[1], generator=g, dtype=torch.float64) * 0.1
             p["moving_var"] = torch.rand(p["w"].shape[1], generator=g, dtype=torch.float64) + 0.5
     layers = to_layers(ps, place)
+    moving0 = [(lp.moving_mean.clone(), lp.moving_variance.clone()) if lp.bn else None for lp in layers]
     x = place_x(x64.float().cuda(), place)
     out = mlp_stack(x, cin, layers, training, 0.7, pool_ns=ns)
 
     xr = x64[:, :cin].to(ref_device).clone().requires_grad_(True)
-    for p in ps:
-        for k in p:
-            if torch.is_tensor(p[k]):
-                p[k] = p[k].to(ref_device)
-        for k in ("w", "b", "gamma", "beta"):
-            p[k] = p[k].clone().requires_grad_(True)
+    _leaves(ps, ref_device)
     # float64 restatement, layer by layer (oracle/mlp_ref.py), keeping the pre-activations.  An element whose BN output lies within
     # fp32 rounding of the ReLU kink -- or a pool group whose two largest activations agree to fp32 rounding -- may fall on the other
     # side in float32.  One such flip moves dW by a single row's contribution, which at 1e5 rows is already 1e-3 of |dW| (the sum over
@@ -181,7 +202,8 @@ def check_stack(rows, ld, cin, chans, ns, training, ref_device="cpu", neg_gamma=
     assert rel_err(out, ref) < 1e-5
     if training:
         for lp, (mm, mv) in zip(layers, moving):
-            assert rel_err(lp.moving_mean, mm) < 1e-5 and rel_err(lp.moving_variance, mv) < 1e-5
+            if lp.bn:
+                assert rel_err(lp.moving_mean, mm) < 1e-5 and rel_err(lp.moving_variance, mv) < 1e-5
 
     go = torch.randn(ref.shape, generator=g, dtype=torch.float64).to(ref_device)
     go[fragile] = 0
@@ -192,16 +214,18 @@ def check_stack(rows, ld, cin, chans, ns, training, ref_device="cpu", neg_gamma=
     tol = 1e-4
     keep = ~frag_rows
     assert rel_err(x.grad[:, :cin][keep.to(x.device)], xr.grad[keep]) < tol
-    for lp, p in zip(layers, ps):
+    for lp, p, m0 in zip(layers, ps, moving0):
         assert rel_err(lp.weights.grad, p["w"].grad) < tol
-        assert rel_err(lp.gamma.grad, p["gamma"].grad) < tol
-        assert rel_err(lp.beta.grad, p["beta"].grad) < tol
-        # bias feeds a batch-normalised layer: its true gradient is ~0 in training mode
-        scale = max(float(p["w"].grad.abs().max()), 1e-6)
-        assert float((lp.biases.grad.double().cpu() - p["b"].grad.cpu()).abs().max()) < tol * max(scale, float(p["b"].grad.abs().max()))
+        if lp.bn:
+            assert rel_err(lp.gamma.grad, p["gamma"].grad) < tol
+            assert rel_err(lp.beta.grad, p["beta"].grad) < tol
+            if not training:                     # neither pass of an evaluation-mode stack touches the moving statistics
+                assert torch.equal(lp.moving_mean, m0[0]) and torch.equal(lp.moving_variance, m0[1])
+        # a bias in front of a batch norm: its true gradient is ~0 in training mode; without one it is held to tol like the others
+        assert bias_err(lp, p) < tol
 
 
-def check_stack_routed(rows, ld, cin, chans, ns, ref_device="cuda", tol=1e-5, place=None, results=None):
+def check_stack_routed(rows, ld, cin, chans, ns, ref_device="cuda", tol=1e-5, place=None, results=None, bn=True):
     """Gradients at north_star's 1e-5, NOTHING silenced.  check_stack above compares against a float64 evaluation that makes its
     own ReLU / arg-max decisions and therefore has to zero the upstream gradient wherever float32 might decide differently.  Here the float64
     backward is ROUTED by the decisions the GPU forward actually took: layer l's ReLU mask is sign(fma(y, scale, shift)) of the GPU's own float32
@@ -209,13 +233,15 @@ def check_stack_routed(rows, ld, cin, chans, ns, ref_device="cuda", tol=1e-5, pl
     every remaining difference is float32 arithmetic, and all of dX (every row), dW, dgamma, dbeta, dbias are held to `tol` of their largest element.
     (That the decisions themselves are right is what the forward comparison at 1e-5 and check_stack establish: a wrong mask away from the kink would show
     there.)
+    bn: one bool, or one per layer (make_params).  A layer without batch norm saves scale 1 and shift 0, so its mask is sign(y); it has no
+    gamma / beta, and its bias gradient is held to `tol` of its own largest element.
     place (one of PLACES): the operands handed to the stack through misaligned(); the float64 side does not change.  results (a dict): receives the
     GPU's output, dX and parameter gradients, for a caller that compares two runs of one case."""
     from gspn_amd.mlp import mlp_stack
     g = torch.Generator().manual_seed(rows + cin + 1)
     x64 = torch.randn(rows, ld, generator=g, dtype=torch.float64)
     x64[:, cin:] = 0
-    ps = make_params(chans, cin, seed=cin + 1)
+    ps = make_params(chans, cin, seed=cin + 1, bn=bn)
     layers = to_layers(ps, place)
     x = place_x(x64.float().cuda(), place)
     out = mlp_stack(x, cin, layers, True, 0.7, pool_ns=ns)
@@ -225,16 +251,13 @@ def check_stack_routed(rows, ld, cin, chans, ns, ref_device="cuda", tol=1e-5, pl
         masks.append(((y.double() * scale.double() + shift.double()) > 0).to(ref_device))      # y*scale exact in float64: the sign of the fma
     arg = node.arg.long().to(ref_device) if ns else None
     xr = x64[:, :cin].to(ref_device).clone().requires_grad_(True)
-    for p in ps:
-        for k in p:
-            if torch.is_tensor(p[k]):
-                p[k] = p[k].to(ref_device)
-        for k in ("w", "b", "gamma", "beta"):
-            p[k] = p[k].clone().requires_grad_(True)
+    _leaves(ps, ref_device)
     h = xr
     flips = 0
+    moving = []
     for p, mk in zip(ps, masks):
-        z, _, _ = R.layer(h, p["w"], p["b"], p["gamma"], p["beta"], p["moving_mean"], p["moving_var"], True, 0.7, True, relu=False)
+        z, mm, mv = R.layer(h, p["w"], p["b"], p.get("gamma"), p.get("beta"), p.get("moving_mean"), p.get("moving_var"), True, 0.7, p["bn"], relu=False)
+        moving.append((mm, mv))
         flips += int(((z.detach() > 0) != mk).sum())
         h = z * mk
     ref = h
@@ -243,6 +266,9 @@ def check_stack_routed(rows, ld, cin, chans, ns, ref_device="cuda", tol=1e-5, pl
         assert int(arg.min()) >= 0 and int(arg.max()) < ns
         ref = ref.view(groups, ns, -1).gather(1, arg[:, None, :]).squeeze(1)
     assert rel_err(out, ref) < 1e-5
+    for lp, (mm, mv) in zip(layers, moving):
+        if lp.bn:
+            assert rel_err(lp.moving_mean, mm) < 1e-5 and rel_err(lp.moving_variance, mv) < 1e-5
     go = torch.randn(ref.shape, generator=g, dtype=torch.float64).to(ref_device)
     ref.backward(go)
     out.backward(place_grad(go.float().cuda(), place))
@@ -252,11 +278,11 @@ def check_stack_routed(rows, ld, cin, chans, ns, ref_device="cuda", tol=1e-5, pl
     errs = {"dX": rel_err(x.grad[:, :cin], xr.grad)}
     for li, (lp, p) in enumerate(zip(layers, ps)):
         errs["dW%d" % li] = rel_err(lp.weights.grad, p["w"].grad)
-        errs["dgamma%d" % li] = rel_err(lp.gamma.grad, p["gamma"].grad)
-        errs["dbeta%d" % li] = rel_err(lp.beta.grad, p["beta"].grad)
-        # the bias feeds a batch-normalised layer: its true gradient is 0 up to rounding; hold it to tol of the weight gradient's scale
-        scale = max(float(p["w"].grad.abs().max()), 1e-6)
-        errs["dbias%d" % li] = float((lp.biases.grad.double().cpu() - p["b"].grad.cpu()).abs().max()) / max(scale, float(p["b"].grad.abs().max()))
+        if lp.bn:
+            errs["dgamma%d" % li] = rel_err(lp.gamma.grad, p["gamma"].grad)
+            errs["dbeta%d" % li] = rel_err(lp.beta.grad, p["beta"].grad)
+        # a bias that feeds a batch-normalised layer: its true gradient is 0 up to rounding; hold it to tol of the weight gradient's scale
+        errs["dbias%d" % li] = bias_err(lp, p)
     print("check_stack_routed rows=%d cin=%d chans=%s ns=%s: %d decisions where float64 alone would have differed; worst %s"
           % (rows, cin, chans, ns, flips, max(errs.items(), key=lambda kv: kv[1])))
     bad = {k: v for k, v in errs.items() if not v < tol}
@@ -620,11 +646,18 @@ def test_pad_rows():
     assert torch.equal(out[:, :3], x) and (out[:, 3] == 0).all()
 
 
-@pytest.mark.parametrize("cin,cout,pooled", [(64, 64, False), (32, 32, False), (32, 64, True), (64, 128, False), (64, 32, True), (32, 128, True)])
-def test_fused_backward_entry_point_with_padded_pitches(cin, cout, pooled):
+FUSED_WITH_PART = [(64, 64, False), (32, 32, False), (32, 64, True), (64, 128, False), (64, 32, True), (32, 128, True)]
+FUSED_NO_PART = [(ci, co, p) for ci in (32, 64) for co in (32, 64, 128) for p in (False, True)]
+
+
+@pytest.mark.parametrize("cin,cout,pooled,with_part", [c + (True,) for c in FUSED_WITH_PART] + [c + (False,) for c in FUSED_NO_PART],
+                         ids=["%d-%d-%s" % c for c in FUSED_WITH_PART] + ["%d-%d-%s-no_part" % c for c in FUSED_NO_PART])
+def test_fused_backward_entry_point_with_padded_pitches(cin, cout, pooled, with_part):
     """gspn_mlp_bwd_fused through the C ABI alone, every pitch LARGER than its channel count (the Python host only ever passes tight
     tensors): dX, dW and the BN-reduction rows against a float64 evaluation of the same formulas on the device --
-    dY = cA*[relu open]*dz + cB*y + cC, dW = relu(Xp*s + t)^T . dY, dX = dY . W^T, (sum dyh, sum dyh*xhat) of the previous layer"""
+    dY = cA*[relu open]*dz + cB*y + cC, dW = relu(Xp*s + t)^T . dY, dX = dY . W^T, (sum dyh, sum dyh*xhat) of the previous layer.
+    with_part = False: part, mean_p, var_p and nparts_out NULL -- the layer below has no batch norm, so there are no reductions to carry
+    (bwd_fused_kernel<cin / 32, cout / 32, false, pooled>, all twelve); dX and dW are the same formulas at the same bounds."""
     import ctypes
     from gspn_amd import _lib as L
     lib = L.lib()
@@ -658,10 +691,11 @@ def test_fused_backward_entry_point_with_padded_pitches(cin, cout, pooled):
     dXb = torch.full((rows, ldx), 7.0, device=dev)
     dW = torch.empty(cin, cout, device=dev)
     work = torch.empty(int(lib.gspn_mlp_bwd_work_bytes(rows, cin, cout)) // 4 + 4, device=dev)
-    part = torch.empty(int(lib.gspn_rsum_part_floats(rows, cin)), device=dev)
+    part = torch.empty(int(lib.gspn_rsum_part_floats(rows, cin)), device=dev) if with_part else None
     npart = ctypes.c_int(0)
     L.check(lib.gspn_mlp_bwd_fused(rows, cin, cout, ctypes.byref(a), L.ptr(W), L.ptr(Xb), ldxp, L.ptr(isc), L.ptr(ish), L.ptr(dXb), ldx, L.ptr(work),
-                                   L.ptr(dW), L.ptr(pmean), L.ptr(pvar), 1e-3, L.ptr(part), ctypes.byref(npart), L.stream()), "fused")
+                                   L.ptr(dW), L.ptr(pmean if with_part else None), L.ptr(pvar if with_part else None), 1e-3, L.ptr(part),
+                                   ctypes.byref(npart) if with_part else None, L.stream()), "fused")
     torch.cuda.synchronize()
     # float64 on the device; the ReLU masks are taken with the float32 expressions the kernels use (two roundings), so no element sits
     # on the other side of a kink
@@ -674,6 +708,8 @@ def test_fused_backward_entry_point_with_padded_pitches(cin, cout, pooled):
     assert rel_err(dW, rdW) < 2e-5
     assert rel_err(dXb[:, :cin], rdX) < 2e-5
     assert bool((dXb[:, cin:] == 7.0).all())                       # the padding columns of dX are not touched
+    if not with_part:
+        return
     open_x = (Xp * isc + ish) > 0
     dxh = torch.where(open_x, rdX, torch.zeros_like(rdX))
     xhat = (Xp.double() - pmean.double()) / torch.sqrt(pvar.double() + 1e-3)

@@ -6,3 +6,15 @@ All compute goes through the C ABI of libgspn_hip.so (include/gspn_hip.h); there
 fallback.
 """
 __version__ = "0.1.0"
+
+# gspn_amd.dataset and its functions, resolved on first use: `import gspn_amd` (and `python -m gspn_amd.build`) stays free of torch
+_DATASET = ("fps_segments", "instance_point_sets", "resample_scene", "remap_labels", "augment_and_box")
+__all__ = ["dataset"] + list(_DATASET)
+
+
+def __getattr__(name):
+    if name == "dataset" or name in _DATASET:
+        import importlib
+        module = importlib.import_module(".dataset", __name__)
+        return module if name == "dataset" else getattr(module, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

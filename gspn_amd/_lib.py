@@ -136,6 +136,7 @@ SIGNATURES = {
     "gspn_crop_mean": [_I, _I, _I, _I, _I, _P, _P, _P, _P],
     "gspn_tile_add": [_L, _I, _I, _P, _P, _P, _P],
     "gspn_tile_sum": [_L, _I, _I, _P, _P, _P, _P],
+    "gspn_fps_segments": [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
 }
 
 # entry points that do not return an int status: symbol -> (argtypes, restype)
@@ -163,9 +164,10 @@ SPECIAL = {
     "gspn_crop_gather_grad_part_floats": ([_I, _I, _I], _L),
     "gspn_crop_linear_part_floats": ([_I, _I, _I, _I], _L),
     "gspn_tile_sum_part_floats": ([_L, _I, _I], _L),
+    "gspn_fps_segments_ws_bytes": ([_I, _I, _I], _L),
 }
 
-ABI_VERSION = 17        # == GSPN_ABI_VERSION of include/gspn_hip.h this binding was written against
+ABI_VERSION = 18       # == GSPN_ABI_VERSION of include/gspn_hip.h this binding was written against
 
 _lib = None
 

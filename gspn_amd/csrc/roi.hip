@@ -17,6 +17,7 @@
 // fp32 throughout, no atomics, no host synchronisation, no allocation.  Compiled with -ffp-contract=off: every bound, volume and IoU below
 // is evaluated exactly as the reference writes it.  The random numbers are gspn_roi_rand32 of include/gspn_hip.h.
 #include "box_common.h"
+#include "rand32.h"          // roi_rand_scene / roi_rand32
 
 #define SM_THREADS 256
 #define SM_WAVES (SM_THREADS / GSPN_WAVE)
@@ -26,23 +27,6 @@
 #define CG_CHUNK 64
 
 namespace {
-
-// ---------------------------------------------------------------------------------------------------- random numbers
-__device__ __forceinline__ unsigned long long roi_mix64(unsigned long long z) {
-    z ^= z >> 30;
-    z *= 0xBF58476D1CE4E5B9ull;
-    z ^= z >> 27;
-    z *= 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return z;
-}
-// the scene's stream: everything of gspn_roi_rand32 that does not depend on (a, b)
-__device__ __forceinline__ unsigned long long roi_rand_scene(long long seed, int scene) {
-    return roi_mix64((unsigned long long)seed + 0x9E3779B97F4A7C15ull * (unsigned long long)(scene + 1));
-}
-__device__ __forceinline__ unsigned roi_rand32(unsigned long long scene_state, unsigned a, unsigned b) {
-    return (unsigned)(roi_mix64(scene_state ^ (((unsigned long long)a << 32) | (unsigned long long)b)) >> 32);
-}
 
 // ---------------------------------------------------------------------------------------------------- points inside boxes
 // a point is inside when  pc >= (c - s/2) - margin  &&  pc <= (c + s/2) + margin  on all axes (:673-674 with margin 0, :764-765 with 1e-3).

@@ -44,8 +44,9 @@ extern "C" {
  *  14: gspn_class_nms3d / gspn_nearest_in_sets.
  *  15: gspn_crop_linear_fwd / gspn_crop_linear_bwd_side (+ _part_floats).
  *  16: gspn_crop_mean.
- *  17: gspn_tile_add / gspn_tile_sum (+ _part_floats). */
-#define GSPN_ABI_VERSION 17
+ *  17: gspn_tile_add / gspn_tile_sum (+ _part_floats).
+ *  18: gspn_fps_segments (+ _ws_bytes). */
+#define GSPN_ABI_VERSION 18
 int gspn_dist_policy(void);
 int gspn_abi_version(void);
 
@@ -106,6 +107,26 @@ int gspn_scatteraddpoint(int b, int n, int m, const float* out_g, const int* idx
 /* probsampleLauncher(b,n,m,inp_p,inp_r,temp,out)  tf_sampling.cpp:65, tf_sampling_g.cu:198-201.
  * temp: (b,n) floats (the cumulative sums). */
 int gspn_probsample(int b, int n, int m, const float* inp_p, const float* inp_r, float* temp, int* out, void* stream);
+
+/* Segmented farthest point sampling: dataset.py:107-118, the resampling of EVERY instance of every scene to m = npoint_ins points, in one
+ * fixed set of launches with one workgroup per (scene, group) (gspn_amd/csrc/sampling_segments.hip).  The reference runs
+ * farthestpointsamplingKernel once per instance, at b = 1, on the host-compacted cloud curpc[curgroup == j].
+ *   pc (b,n,3); order (b,n), offsets (b,g+1) = gspn_inverse_lists of the scenes' group labels over g targets (members of a group in
+ *   ascending point index; labels outside [0,g) dropped) -> idx_out (b,g,m) i32 scene indices, pts_out (b,g,m,3) = pc[idx_out],
+ *   count_out (b,g) i32 = the group sizes.
+ * For group j of scene s with c = offsets[j+1] - offsets[j] members L[k] = order[offsets[j] + k]:
+ *   j == 0 (background, :108-109) or c == 0:  idx_out = -1, pts_out = 0
+ *   c > m:   the picks of farthestpointsamplingKernel (tf_sampling_g.cu:105-170) on the cloud pc[L[0..c)]: the first pick is k = 0, equal
+ *            distances go to the lowest (k mod 512, k) of the COMPACTED position k; idx_out = L[pick]
+ *   c == m:  L in order (:114-115)
+ *   c < m:   L in order, then draw t = 0..m-c-1 is L[(uint64(gspn_roi_rand32(seed, s, j, t)) * c) >> 32] (:116-118; the reference draws with
+ *            np.random.choice, so this stream is this library's own; seed is read from seed_dev as in the ROI stage below)
+ * n <= 32768 (GSPN_ERR_UNSUPPORTED beyond; the reference's scans hold at most 30000 points, data_prep.py:65), m >= 1, g >= 1, b * g < 2^31.
+ * No host synchronisation and static shapes: the call captures in a graph.  ws: gspn_fps_segments_ws_bytes(b,n,g) bytes, which is 0 in this
+ * build (the kernels read an instance through order while they load it; ws may then be NULL). */
+long gspn_fps_segments_ws_bytes(int b, int n, int g);
+int gspn_fps_segments(int b, int n, int g, int m, const long long* seed_dev, const float* pc, const int* order, const int* offsets, void* ws,
+                      int* idx_out, float* pts_out, int* count_out, void* stream);
 
 /* ---------------- tf_ops/grouping ---------------------------------------------------- */
 

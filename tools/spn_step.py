@@ -26,6 +26,11 @@
             stages (the same parts chained by hand with an event between them) with fused_crop off and on, alternating in one process; the
             detections per scene; and crop_mean against the reference's own form of the per-ROI probabilities (concatenate the 20 columns
             to the 1024 features, points_cropping at width 1044, split, mean), alternating, with their largest relative difference
+  dataset   the instance resampling of dataset.py:107-118 (gspn_amd/dataset.py) on scenes whose instance sizes are the mix of
+            tests/test_gpu_dataset.py scaled to the shape, --points-per-instance picks per instance: fps_segments (one call for the batch)
+            against the loop the library offered before -- a boolean compaction and a b = 1 farthest_point_sample per instance -- and
+            against instance_point_sets replayed from a captured graph, alternating in one process; the loop's FPS calls and host
+            compactions, and whether the sampled rows of the two forms are equal
 
 Prints one JSON line per (shape, measurement): median / min milliseconds over --iters timed runs after --warmup runs.
     python tools/spn_step.py --shapes 2x18000,8x32768
@@ -35,6 +40,7 @@ Prints one JSON line per (shape, measurement): median / min milliseconds over --
     python tools/spn_step.py --shapes 2x18000 --measures heads --iters 30
     python tools/spn_step.py --shapes 2x18000 --measures infer --iters 5
     python tools/spn_step.py --shapes 2x18000 --measures train_heads --iters 10
+    python tools/spn_step.py --shapes 2x18000,2x30000 --measures dataset --iters 30
 """
 import argparse
 import json
@@ -523,8 +529,55 @@ def measure_train_heads(a, shape, b, n, dev):
                       "points_per_roi": p, "input_channels": c + 6, "max_relative_difference": diff, "iters": a.iters, **res}), flush=True)
 
 
+DATASET_MIX = ([300, 17000, 9000, 4500, 1300, 600, 68], [20000, 1800, 400, 64, 10, 0, 2500, 7994])      # of 32768 points: tests/test_gpu_dataset.py
+
+
+def measure_dataset(a, shape, b, n, dev):
+    from gspn_amd import dataset, graph
+    m, g = a.points_per_instance, max(len(s) for s in DATASET_MIX)
+    pcs, labels, sizes_used = [], [], []
+    for s in range(b):
+        rng = np.random.default_rng(90 + s)
+        mix = DATASET_MIX[s % len(DATASET_MIX)]
+        sizes = [c * n // 32768 for c in mix] + [0] * (g - len(mix))
+        sizes[1] += n - sum(sizes)
+        sizes_used.append(sizes)
+        pcs.append(synth.cloud_d(n, 90 + s))
+        labels.append(np.repeat(np.arange(g), sizes)[rng.permutation(n)])
+    pc, label = torch.from_numpy(np.stack(pcs)).to(dev), torch.from_numpy(np.stack(labels)).to(dev)
+    seed = torch.tensor([7], dtype=torch.int64, device=dev)
+    calls = {"fps": 0, "compactions": 0}
+
+    def loop():
+        """what the library offered before: one boolean compaction (a host synchronisation) and one b = 1 FPS call per instance"""
+        out = torch.zeros((b, g, m, 3), device=dev)
+        calls["fps"] = calls["compactions"] = 0
+        for s in range(b):
+            for j in range(1, g):
+                pts = pc[s][label[s] == j]
+                calls["compactions"] += 1
+                c = pts.shape[0]
+                if c > m:
+                    out[s, j] = pts[farthest_point_sample(m, pts[None])[0].long()]
+                    calls["fps"] += 1
+                elif c > 0:
+                    out[s, j] = torch.cat((pts, pts[torch.randint(0, c, (m - c,), device=dev)]))
+        return out
+
+    want, got = loop(), dataset.instance_point_sets(pc, label, g, m, seed)
+    sampled = [(s, j) for s in range(b) for j in range(1, g) if sizes_used[s][j] > m]
+    same = all(bool(torch.equal(want[s, j], got[s, j])) for s, j in sampled)
+    step = graph.CapturedStep(lambda: dataset.instance_point_sets(pc, label, g, m, seed))
+    res = timed_alternating({"fps_segments": lambda: dataset.fps_segments(pc, label, g, m, seed), "per_instance_loop": loop,
+                             "instance_point_sets_captured": step.replay}, a.warmup, a.iters)
+    print(json.dumps({"shape": shape, "measure": "dataset", "points_per_instance": m, "groups": g, "instance_sizes": sizes_used,
+                      "sampled_rows_equal_the_loop": same, "loop_fps_calls": calls["fps"], "loop_host_compactions": calls["compactions"],
+                      "iters": a.iters, **res}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--points-per-instance", type=int, default=512)  # npoint_ins of --measures dataset (dataset.py:14)
     ap.add_argument("--measures", default="step,full_fwd,nn,spn")
     ap.add_argument("--shapes", default="2x18000,8x32768")
     ap.add_argument("--kind", default="S")
@@ -553,6 +606,8 @@ def main():
             measure_infer(a, shape, b, n, dev)
         if "train_heads" in measures:
             measure_train_heads(a, shape, b, n, dev)
+        if "dataset" in measures:
+            measure_dataset(a, shape, b, n, dev)
         if not set(measures) & {"step", "full_fwd", "nn"}:
             continue
         xyz = torch.from_numpy(synth.batch(a.kind, b, n)).to(dev)

@@ -17,6 +17,7 @@ _P = _c.c_void_p
 _I = _c.c_int
 _L = _c.c_long
 _F = _c.c_float
+_D = _c.c_double
 
 
 class DyArgs(_c.Structure):
@@ -137,6 +138,9 @@ SIGNATURES = {
     "gspn_tile_add": [_L, _I, _I, _P, _P, _P, _P],
     "gspn_tile_sum": [_L, _I, _I, _P, _P, _P, _P],
     "gspn_fps_segments": [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "gspn_scene_confidence": [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _D, _P, _P, _P, _P, _P],
+    "gspn_scene_rank": [_I, _I, _I, _P, _P, _P, _P, _D, _D, _P, _P, _P, _P, _P, _P, _P],
+    "gspn_sem_iou_counts": [_L, _I, _P, _P, _P, _P, _P],
 }
 
 # entry points that do not return an int status: symbol -> (argtypes, restype)
@@ -167,7 +171,7 @@ SPECIAL = {
     "gspn_fps_segments_ws_bytes": ([_I, _I, _I], _L),
 }
 
-ABI_VERSION = 18       # == GSPN_ABI_VERSION of include/gspn_hip.h this binding was written against
+ABI_VERSION = 19       # == GSPN_ABI_VERSION of include/gspn_hip.h this binding was written against
 
 _lib = None
 

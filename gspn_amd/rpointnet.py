@@ -12,7 +12,9 @@ crop_linear (their first layer fused with the crop) and the R-PointNet losses (:
 re-exported here as callable parts.  Inference is its own driver, rpointnet_inference (:1064-1221 for mode='inference', with crop_mean for
 the per-ROI probabilities of :1146-1150), which lives in inference.py and is re-exported here.  Head training is its own driver too:
 rpointnet_head_training / rpointnet_heads_from_proposals (:1070-1115, :1198-1209 for TRAIN_MODULE == ['RPOINTNET']) and
-get_head_training_loss (:1325-1416 for it), which live in training.py and are re-exported here.  rpointnet itself does not chain the
+get_head_training_loss (:1325-1416 for it), which live in training.py and are re-exported here.  The prediction export stage behind
+inference -- scene_predictions, write_predictions, write_ground_truth (test.py:96-129, :155-206) and semantic_iou_counts / mean_iou
+(train.py:365-368, 385-386) -- lives in predict.py and is re-exported here.  rpointnet itself does not chain the
 parts: with mode='inference' or 'RPOINTNET' in TRAIN_MODULE, and get_loss with 'RPOINTNET' in TRAIN_MODULE, it raises NotImplementedError
 and names the function to call."""
 import torch
@@ -21,6 +23,8 @@ from . import _lib as L
 from .detect import (class_nms_3d, nearest_in_sets, refine_detections, refine_detections_batch, select_segmentation,
                      unmold_segmentation)
 from .inference import crop_mean, rpointnet_inference
+from .predict import (SCANNET_LABEL_MAP, mean_iou, scene_confidence, scene_predictions, scene_rank, semantic_iou_counts, write_ground_truth,
+                      write_predictions)
 from .heads import (classification_head, crop_linear, fpn_features, get_rpointnet_bbox_loss, get_rpointnet_class_loss, get_rpointnet_loss,
                     get_rpointnet_mask_loss, segmentation_head, shared_first_layers, tile_linear)
 from .proposal_head import chamfer_recons_loss
@@ -36,7 +40,8 @@ __all__ = ["Config", "box_shrink", "spn_target_gen", "spn_target_gen_batch", "ga
            "class_nms_3d", "refine_detections", "refine_detections_batch", "select_segmentation", "nearest_in_sets", "unmold_segmentation",
            "crop_linear", "classification_head", "segmentation_head", "fpn_features", "get_rpointnet_class_loss", "get_rpointnet_bbox_loss",
            "get_rpointnet_mask_loss", "get_rpointnet_loss", "crop_mean", "rpointnet_inference", "tile_linear", "shared_first_layers",
-           "rpointnet_heads_from_proposals", "rpointnet_head_training", "get_head_training_loss"]
+           "rpointnet_heads_from_proposals", "rpointnet_head_training", "get_head_training_loss", "SCANNET_LABEL_MAP", "scene_confidence",
+           "scene_rank", "scene_predictions", "semantic_iou_counts", "mean_iou", "write_predictions", "write_ground_truth"]
 
 
 class Config(object):

@@ -45,8 +45,9 @@ extern "C" {
  *  15: gspn_crop_linear_fwd / gspn_crop_linear_bwd_side (+ _part_floats).
  *  16: gspn_crop_mean.
  *  17: gspn_tile_add / gspn_tile_sum (+ _part_floats).
- *  18: gspn_fps_segments (+ _ws_bytes). */
-#define GSPN_ABI_VERSION 18
+ *  18: gspn_fps_segments (+ _ws_bytes).
+ *  19: gspn_scene_confidence / gspn_scene_rank / gspn_sem_iou_counts. */
+#define GSPN_ABI_VERSION 19
 int gspn_dist_policy(void);
 int gspn_abi_version(void);
 
@@ -690,6 +691,39 @@ int gspn_mlp_bwd_wgrad_gather(long rows, const gspn_gather_args* g, int cout, co
  * (Extension: the reference scatters with atomicAdd -- tf_grouping_g.cu:78-86, tf_interpolate.cpp:119-143 -- and needs no such lists.) */
 long gspn_inverse_lists_work_ints(int b, int L, int n);
 int gspn_inverse_lists(int b, int L, int n, const int* idx, int* work, int* order, int* offsets, void* stream);
+
+/* ---------------- the prediction export stage: the arithmetic of test.py:155-205 (gspn_amd/csrc/predict.hip, ABI 19) -------------- */
+
+/* test.py:163-189 and :204 for every detection of every scene, one workgroup per (scene, detection).  idx (b,r,n) i32: the position in
+ * detection k's crop of the crop point nearest to scene point j, -1 where j is outside k's box (gspn_nearest_in_sets with the boxes);
+ * masks (b,r,p) f32; class_ids (b,r) i32; sem_prob (b,n,c) f32; point_fb (b,n) f32.  With g[j] = idx[j] >= 0 ? masks[idx[j]] : 0, in double
+ * (every float product widened first, so every term is exact):
+ *   S0 = sum g,  S1 = sum g * sem_prob[j, class],  S2 = sum g * point_fb[j];  sem_conf = S1 / (1e-8 + S0),  fb_conf = S2 / (1e-8 + S0)
+ *   mask[j] = (double)g[j] > mask_th  (u8, 0 or 1);  mask_points = the number of set bytes of the row.
+ * The order of the additions depends on the shape alone (no atomics): the same bits on every call.  A row whose class is outside
+ * [1, c) writes zeros to all four outputs.  A point outside the box reads neither masks nor the tables; an index >= p is clamped.
+ * sem_conf, fb_conf (b,r) f64; mask (b,r,n) u8; mask_points (b,r) i32. */
+int gspn_scene_confidence(int b, int r, int n, int p, int c, const int* idx, const float* masks, const int* class_ids, const float* sem_prob,
+                          const float* point_fb, double mask_th, double* sem_conf, double* fb_conf, unsigned char* mask, int* mask_points,
+                          void* stream);
+
+/* test.py:159-161 and :191-205, one workgroup per scene, r <= GSPN_SCENE_RANK_MAX_R (GSPN_ERR_UNSUPPORTED above).  det_score (b,r) f32,
+ * class_ids (b,r) i32, sem_conf, fb_conf (b,r) f64, label_map (c,) i32.  score = ((double)det_score * sem_conf) * fb_conf.
+ * Group 0: class in [1, c), sem_conf > sem_th and fb_conf > fb_th;  group 1: class in [1, c) otherwise;  group 2: the other rows, which
+ * the reference drops (their score is 0).  A row's output position is its rank by (group ascending, score descending, row ascending),
+ * found by counting; a NaN score ranks as -infinity.  In output order: order (b,r) i32: the row at each position; label_ids (b,r) i32:
+ * label_map[class], 0 in group 2; confidence (b,r) f32: 1, 0.97, 0 by group; score (b,r) f64.  count (b,) i32: rows of groups 0 and 1. */
+#define GSPN_SCENE_RANK_MAX_R 1024
+int gspn_scene_rank(int b, int r, int c, const float* det_score, const int* class_ids, const double* sem_conf, const double* fb_conf,
+                    double sem_th, double fb_th, const int* label_map, int* order, int* count, int* label_ids, float* confidence,
+                    double* score, void* stream);
+
+/* train.py:365-368, 385-386 on the device.  logits (rows,c) f32, labels (rows,) i32; pred = the FIRST column of the row's maximum
+ * (np.argmax; a NaN never wins).  For s = 1..c-1: inter[s-1] += #(pred == s and label == s), uni[s-1] += #(pred == s or label == s),
+ * ADDED to the caller's (c-1,) int64 accumulators (per-workgroup LDS counters, then one 64-bit integer atomic per class and workgroup:
+ * exact in any order).  A label outside [1, c) counts for no class.  2 <= c <= GSPN_SEM_IOU_MAX_C. */
+#define GSPN_SEM_IOU_MAX_C 256
+int gspn_sem_iou_counts(long rows, int c, const float* logits, const int* labels, long long* inter, long long* uni, void* stream);
 
 /* utils/pointnet_util.py:157-160 in one kernel: dist (total,3) squared distances of three_nn -> weight (total,3):
  * d = max(d, 1e-10); weight_k = (1/d_k) / ((1/d_0 + 1/d_1) + 1/d_2) */

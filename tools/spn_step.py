@@ -31,6 +31,11 @@
             against the loop the library offered before -- a boolean compaction and a b = 1 farthest_point_sample per instance -- and
             against instance_point_sets replayed from a captured graph, alternating in one process; the loop's FPS calls and host
             compactions, and whether the sampled rows of the two forms are equal
+  predict   the prediction export stage (gspn_amd/predict.py) with Config(istrain=False)'s widths -- 100 detections x 1024 crop points, 19
+            categories, 2048 seeds -- on synthetic head outputs: scene_predictions against the same arithmetic written in torch on the
+            device (unmold_segmentation's (B, R, N) float tensor, a float64 matmul with the softmax table, two argsorts, the threshold),
+            alternating in one process, and the stage replayed from a captured graph; whether the two orders and masks are equal and the
+            largest relative difference of the confidences
 
 Prints one JSON line per (shape, measurement): median / min milliseconds over --iters timed runs after --warmup runs.
     python tools/spn_step.py --shapes 2x18000,8x32768
@@ -41,6 +46,7 @@ Prints one JSON line per (shape, measurement): median / min milliseconds over --
     python tools/spn_step.py --shapes 2x18000 --measures infer --iters 5
     python tools/spn_step.py --shapes 2x18000 --measures train_heads --iters 10
     python tools/spn_step.py --shapes 2x18000,2x30000 --measures dataset --iters 30
+    python tools/spn_step.py --shapes 2x18000 --measures predict --iters 30
 """
 import argparse
 import json
@@ -575,6 +581,66 @@ def measure_dataset(a, shape, b, n, dev):
                       "iters": a.iters, **res}), flush=True)
 
 
+def scene_predictions_torch(RP, masks, ep, pc, label_map, sem_th=0.01, fb_th=0.01, mask_th=0.4):
+    """test.py:163-205 in torch on the device: the unmolded (B, R, N) float tensor, float64 products with the tables, two argsorts"""
+    from gspn_amd.inference import _point_probabilities
+    det = ep["detections"]
+    cls = det[:, :, 6].long()
+    valid = cls > 0
+    table = _point_probabilities(pc, ep).double()
+    g = RP.unmold_segmentation(masks, det[:, :, :6].contiguous(), det[:, :, 6], ep["pc_coord_cropped_final_unnormalized"], pc).double()
+    g = g * valid.unsqueeze(-1)
+    total = 1e-8 + g.sum(-1)
+    sem_conf = torch.gather(torch.matmul(g, table[:, :, 1:]), 2, cls.unsqueeze(-1)).squeeze(-1) / total
+    fb_conf = torch.matmul(g, table[:, :, :1]).squeeze(-1) / total
+    score = (det[:, :, 7].double() * sem_conf * fb_conf) * valid
+    group = torch.where(valid, torch.where((sem_conf > sem_th) & (fb_conf > fb_th), 0, 1), 2)
+    by_score = torch.argsort(-score, dim=1, stable=True)
+    order = torch.gather(by_score, 1, torch.argsort(torch.gather(group, 1, by_score), dim=1, stable=True))
+    mask = (g > mask_th).to(torch.uint8)
+    rows = order.unsqueeze(-1).expand(-1, -1, pc.shape[1])
+    return {"order": order.int(), "count": valid.sum(1).int(), "label_ids": torch.gather(label_map[cls] * valid, 1, order).int(),
+            "confidence": torch.gather(torch.where(group == 0, 1.0, 0.97) * valid, 1, order).float(), "sem_conf": torch.gather(sem_conf, 1, order),
+            "fb_conf": torch.gather(fb_conf, 1, order), "score": torch.gather(score, 1, order), "masks": torch.gather(mask, 1, rows),
+            "mask_points": torch.gather(mask.sum(-1), 1, order).int()}
+
+
+def measure_predict(a, shape, b, n, dev):
+    from gspn_amd import graph
+    from gspn_amd import rpointnet as RP
+    cfg = RP.Config(istrain=False)
+    sc = {k: torch.from_numpy(v) for k, v in synth.spn_batch(a.kind, b, n, 100, 512, 19, seed0=7).items()}
+    ext = sc["pc"].amax((0, 1))
+    pc = sc["pc"].to(dev)
+    gen = torch.Generator().manual_seed(19)
+    m, p, c, ns = cfg.DETECTION_MAX_INSTANCES, cfg.NUM_POINT_INS_MASK, cfg.NUM_CATEGORY, cfg.NUM_SAMPLE
+    boxes = roi_proposals(sc["bbox_ins"], ext, m, gen)[0].to(dev)
+    det_rois, idx = RP.mask_selection_gen_batch(boxes, pc, m, cfg, False, torch.zeros(1, dtype=torch.int64, device=dev))
+    crop = RP.points_cropping(pc, pc, pc, det_rois, idx, m, p, cfg.NORMALIZE_CROP_REGION)[3].contiguous()
+    masks = torch.sigmoid(torch.randn(b, m, p, c, generator=gen) * 3.0).to(dev)
+    ids = torch.randint(1, c, (b, m), generator=gen)
+    ids[:, 3 * m // 4:] = 0                                          # the padding rows behind the last detection
+    det = torch.cat((det_rois, ids.float().unsqueeze(-1).to(dev), torch.rand(b, m, 1, generator=gen).to(dev)), -1).contiguous()
+    seeds = torch.stack([torch.randperm(n, generator=gen)[:ns] for _ in range(b)]).to(dev)
+    ep = {"detections": det, "rpointnet_mask_selected": RP.select_segmentation(masks, det[:, :, 6]).contiguous(),
+          "pc_coord_cropped_final_unnormalized": crop, "pc_seed": torch.gather(pc, 1, seeds.unsqueeze(-1).expand(-1, -1, 3)).contiguous(),
+          "fb_prob": torch.softmax(torch.randn(b, ns, 2, generator=gen), -1).to(dev), "sem_class_logits": (torch.randn(b, n, c, generator=gen) * 2).to(dev)}
+    label_map = torch.tensor(RP.SCANNET_LABEL_MAP, device=dev)
+    ours, theirs = RP.scene_predictions(ep, pc), scene_predictions_torch(RP, masks, ep, pc, label_map)
+    live = theirs["sem_conf"] > 0
+    res = {"predictions": ours["count"].tolist(), "inside_share": round(float((RP.nearest_in_sets(pc, crop, det_rois) >= 0).float().mean()), 5),
+           "order_equal": bool(torch.equal(ours["order"], theirs["order"])), "masks_equal": bool(torch.equal(ours["masks"], theirs["masks"])),
+           "labels_equal": bool(torch.equal(ours["label_ids"], theirs["label_ids"])),
+           "confidence_rel_diff": float(max(((ours[k] - theirs[k]).abs()[live] / theirs[k][live]).max() for k in ("sem_conf", "fb_conf")))}
+    st = {}
+    step = graph.CapturedStep(lambda: st.update(pred=RP.scene_predictions(ep, pc)))
+    res.update(timed_alternating({"scene_predictions": lambda: RP.scene_predictions(ep, pc),
+                                  "torch_on_device": lambda: scene_predictions_torch(RP, masks, ep, pc, label_map),
+                                  "scene_predictions_captured": step.replay}, a.warmup, a.iters))
+    print(json.dumps({"shape": shape, "kind": a.kind, "measure": "predict", "detections_per_scene": m, "points_per_roi": p, "categories": c,
+                      "seeds": ns, "iters": a.iters, **res}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points-per-instance", type=int, default=512)  # npoint_ins of --measures dataset (dataset.py:14)
@@ -608,6 +674,8 @@ def main():
             measure_train_heads(a, shape, b, n, dev)
         if "dataset" in measures:
             measure_dataset(a, shape, b, n, dev)
+        if "predict" in measures:
+            measure_predict(a, shape, b, n, dev)
         if not set(measures) & {"step", "full_fwd", "nn"}:
             continue
         xyz = torch.from_numpy(synth.batch(a.kind, b, n)).to(dev)

@@ -141,6 +141,10 @@ SIGNATURES = {
     "gspn_scene_confidence": [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _D, _P, _P, _P, _P, _P],
     "gspn_scene_rank": [_I, _I, _I, _P, _P, _P, _P, _D, _D, _P, _P, _P, _P, _P, _P, _P],
     "gspn_sem_iou_counts": [_L, _I, _P, _P, _P, _P, _P],
+    "gspn_batch_assemble": [_I, _I, _L, _I, _I] + [_P] * 8 + [_I, _I] + [_P] * 10 + [_P],
+    "gspn_adam_tf_flat": [_L, _P, _P, _P, _P, _F, _F, _F, _F, _F, _L, _P],
+    "gspn_momentum_flat": [_L, _P, _P, _P, _F, _F, _F, _P],
+    "gspn_scalars_accumulate": [_I, _P, _P, _P, _P],
 }
 
 # entry points that do not return an int status: symbol -> (argtypes, restype)
@@ -171,7 +175,7 @@ SPECIAL = {
     "gspn_fps_segments_ws_bytes": ([_I, _I, _I], _L),
 }
 
-ABI_VERSION = 19       # == GSPN_ABI_VERSION of include/gspn_hip.h this binding was written against
+ABI_VERSION = 20       # == GSPN_ABI_VERSION of include/gspn_hip.h this binding was written against
 
 _lib = None
 

@@ -187,6 +187,23 @@ class FlatGradBucket:
         return self.all_reduce()
 
 
+def move_parameters_into_flat(bucket):
+    """Move the bucket's parameters into one flat fp32 tensor laid out like bucket.flat -- each `p.data` becomes a view of it -- and return
+    that tensor.  The parameters' storage moves: do this before anything captures their addresses; gradient sinks, which are keyed by
+    the parameters' data pointers, are re-attached here.  Shared by every flat optimiser (FlatAdam; gspn_amd.train's)."""
+    flat = torch.empty_like(bucket.flat)
+    off = 0
+    with torch.no_grad():
+        for p, s in zip(bucket.params, bucket.sizes):
+            view = flat[off:off + s].view_as(p)
+            view.copy_(p)
+            p.data = view
+            off += s
+    if getattr(bucket, "sinks", False):
+        bucket.attach_sinks()                       # the parameters have just moved: the sinks are keyed by their data pointers
+    return flat
+
+
 class FlatAdam:
     """Adam over the bucket's parameters as ONE buffer: the parameters are moved into a flat fp32 tensor (each `p.data` becomes a view of
     it -- do this before anything captures their addresses), the gradients are the bucket's flat tensor, and step() is a single
@@ -197,16 +214,7 @@ class FlatAdam:
         step() can then be captured into a hipGraph together with the backward pass and replays correctly (`t` reads the counter back)"""
         self.bucket = bucket
         self.lr, self.betas, self.eps, self.weight_decay = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
-        self.flat = torch.empty_like(bucket.flat)
-        off = 0
-        with torch.no_grad():
-            for p, s in zip(bucket.params, bucket.sizes):
-                view = self.flat[off:off + s].view_as(p)
-                view.copy_(p)
-                p.data = view
-                off += s
-        if getattr(bucket, "sinks", False):
-            bucket.attach_sinks()                   # the parameters have just moved: the sinks are keyed by their data pointers
+        self.flat = move_parameters_into_flat(bucket)
         self.m = torch.zeros_like(self.flat)
         self.v = torch.zeros_like(self.flat)
         self._t = 0

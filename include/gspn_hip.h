@@ -46,8 +46,9 @@ extern "C" {
  *  16: gspn_crop_mean.
  *  17: gspn_tile_add / gspn_tile_sum (+ _part_floats).
  *  18: gspn_fps_segments (+ _ws_bytes).
- *  19: gspn_scene_confidence / gspn_scene_rank / gspn_sem_iou_counts. */
-#define GSPN_ABI_VERSION 19
+ *  19: gspn_scene_confidence / gspn_scene_rank / gspn_sem_iou_counts.
+ *  20: gspn_batch_assemble / gspn_adam_tf_flat / gspn_momentum_flat / gspn_scalars_accumulate. */
+#define GSPN_ABI_VERSION 20
 int gspn_dist_policy(void);
 int gspn_abi_version(void);
 
@@ -724,6 +725,57 @@ int gspn_scene_rank(int b, int r, int c, const float* det_score, const int* clas
  * exact in any order).  A label outside [1, c) counts for no class.  2 <= c <= GSPN_SEM_IOU_MAX_C. */
 #define GSPN_SEM_IOU_MAX_C 256
 int gspn_sem_iou_counts(long rows, int c, const float* logits, const int* labels, long long* inter, long long* uni, void* stream);
+
+/* ---------------- train.py: the per-step batch, the reference's optimisers, the running loss sums (gspn_amd/csrc/train.hip, ABI 20) -------
+ *
+ * gspn_batch_assemble: get_batch (train.py:221-240) over dataset.py:143-190 for b batch slots from a cache of nscene scenes on the device.
+ *   cache:   pc_all, color_all (nscene,n,3) f32; group_all, seg_all (nscene,n) i32; pc_ins_all (nscene,g,m,3) f32, zero rows beyond a
+ *            scene's groups; ngroup_all (nscene) i32; scene_idx (b) i32 ON THE DEVICE (clamped to [0, nscene)); seed_dev: one int64.
+ *   outputs: pc, color (b,n,3); group_label, seg_label (b,n) i32; pc_ins (b,g,m,3); group_indicator (b,g) i32; bbox_ins (b,g,6);
+ *            smpw (b,n) = 1; rotation (b,3,3) f64 and translation (b,3) f64, as drawn.
+ * Slot s takes scene k = scene_idx[s].  Nothing is read back and there is no workspace: the call captures.  n <= 2^31.
+ *
+ * Permutation (dataset.py:156-160): out[s, i] = in[k, gspn_batch_perm(seed, s, n, i)] for pc, color and both label rows; permute = 0: the
+ * identity (:162-166).  gspn_batch_perm is a stateless bijection of [0, n), a function of (seed, s) only.  With h = the smallest integer
+ * in 1..16 with 4^h >= n, mask = 2^h - 1 and the round keys key[r] = gspn_roi_rand32(seed, s, GSPN_PERM_STREAM, r), r = 0..3:
+ *   fmix32(x):  x ^= x >> 16;  x *= 0x85EBCA6B;  x ^= x >> 13;  x *= 0xC2B2AE35;  x ^= x >> 16          (uint32, modulo 2^32)
+ *   E(x):       l = x >> h, r = x & mask;  four times, for key[0..3]:  (l, r) = (r, l ^ (fmix32(r ^ key) >> (32 - h)));  E = l << h | r
+ *   gspn_batch_perm(seed, s, n, i) = the first of E(i), E(E(i)), ... that is < n
+ * (a balanced Feistel network over 2h bits, cycle-walked: E permutes [0, 4^h), so the walk ends and distinct i end on distinct values).
+ *
+ * Augmentation (:174-183), augment = 1, with draw(t) = gspn_roi_rand32(seed, s, GSPN_AUGMENT_STREAM, t) and float64 throughout:
+ *   angle = (6.283185307179586 * draw(0)) / 2^32;  c = cos(angle), sn = sin(angle);  R = [[c, sn, 0], [-sn, c, 0], [0, 0, 1]]
+ *   Box-Muller, pair p = 0, 1:  u1 = (draw(1 + 2p) + 1) / 2^32,  u2 = draw(2 + 2p) / 2^32,  rad = sqrt(-2 log(u1)),
+ *                               z[2p] = rad * cos(6.283185307179586 * u2),  z[2p + 1] = rad * sin(6.283185307179586 * u2);   t = z[0..2]
+ *   every row x of pc and of pc_ins (the all-zero padding rows included) becomes, for a = 0..2,
+ *       (float)(((x0 * R[0][a] + x1 * R[1][a]) + x2 * R[2][a]) + t[a]),   nothing fused.
+ * R and t are drawn once, by a one-wave launch, into the rotation / translation outputs; the launches that transform pc and pc_ins read
+ * them from there.  augment = 0: R = identity, t = 0 and the coordinates are copied, not passed through the transform.
+ * Padding (:168-172): group_indicator[s, j] = j < ngroup_all[k].  Boxes (:185-188): bbox_ins = gspn_points_bbox of the output pc_ins. */
+#define GSPN_PERM_STREAM 0xFFFFFFFDu    /* `a` of the round keys: no group, no ROI, nor the scene stream 0xFFFFFFFE of gspn_amd/dataset.py */
+#define GSPN_AUGMENT_STREAM 0xFFFFFFFCu /* `a` of the draws of R and t */
+int gspn_batch_assemble(int nscene, int b, long n, int g, int m, const float* pc_all, const float* color_all, const int* group_all,
+                        const int* seg_all, const float* pc_ins_all, const int* ngroup_all, const int* scene_idx,
+                        const long long* seed_dev, int permute, int augment, float* pc, float* color, int* group_label, int* seg_label,
+                        float* pc_ins, int* group_indicator, float* bbox_ins, float* smpw, double* rotation, double* translation,
+                        void* stream);
+
+/* tf.train.AdamOptimizer's rule (train.py:156) over one flat fp32 buffer, gspn_adam_flat's arguments without weight_decay:
+ *   m += (g - m) * (1 - b1);  v += (g * g - v) * (1 - b2);  lr_t = lr * sqrt(1 - b2^step) / (1 - b1^step);  p -= (m * lr_t) / (sqrt(v) + eps)
+ * with g multiplied by grad_scale first and lr_t computed on the host in double.  It parts from gspn_adam_flat where sqrt(v) is not
+ * large against eps: there eps is added to the bias-corrected root. */
+int gspn_adam_tf_flat(long n, float* p, const float* g, float* m, float* v, float lr, float b1, float b2, float eps, float grad_scale,
+                      long step, void* stream);
+
+/* tf.train.MomentumOptimizer (train.py:154; torch.optim.SGD(momentum=, dampening=0) is the same rule):
+ *   accum = momentum * accum + g * grad_scale;  p -= lr * accum */
+int gspn_momentum_flat(long n, float* p, const float* g, float* accum, float lr, float momentum, float grad_scale, void* stream);
+
+/* sums[i] += *ptrs[i] for i < k <= GSPN_SCALARS_MAX, count[0] += 1: the running loss sums of train.py:288-297 without the per-step
+ * read-back.  ptrs: k pointers to fp32 scalars ON THE DEVICE, the array itself in HOST memory (it is passed to the kernel by value);
+ * sums (k) f64 and count (1) i64 on the device.  One wave. */
+#define GSPN_SCALARS_MAX 16
+int gspn_scalars_accumulate(int k, const float* const* ptrs, double* sums, long long* count, void* stream);
 
 /* utils/pointnet_util.py:157-160 in one kernel: dist (total,3) squared distances of three_nn -> weight (total,3):
  * d = max(d, 1e-10); weight_k = (1/d_k) / ((1/d_0 + 1/d_1) + 1/d_2) */

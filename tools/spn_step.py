@@ -47,6 +47,7 @@ Prints one JSON line per (shape, measurement): median / min milliseconds over --
     python tools/spn_step.py --shapes 2x18000 --measures train_heads --iters 10
     python tools/spn_step.py --shapes 2x18000,2x30000 --measures dataset --iters 30
     python tools/spn_step.py --shapes 2x18000 --measures predict --iters 30
+    python tools/spn_step.py --shapes 2x18000,8x32768 --measures train --iters 20
 """
 import argparse
 import json
@@ -641,6 +642,70 @@ def measure_predict(a, shape, b, n, dev):
                       "seeds": ns, "iters": a.iters, **res}), flush=True)
 
 
+def measure_train(a, shape, b, n, dev):
+    """train.py's per-step work around the network: DeviceDataset.batch (one gspn_batch_assemble call) against the same batch made with
+    index_select + dataset.augment_and_box (given the same R and t on the device: its best case; it has no permutation, so the
+    like-for-like pair is permute=0), and a captured SPN training step that accumulates its loss terms on the device against the same
+    step with a per-step host read of them (train.py:283-285)."""
+    import time
+    from gspn_amd import dataset
+    from gspn_amd import rpointnet as RP
+    from gspn_amd import train as T
+    cfg = RP.Config()
+    cfg.BATCH_SIZE = b
+    scenes = 2 * b
+    d = {k: torch.from_numpy(v).to(dev) for k, v in
+         synth.spn_batch(a.kind, scenes, n, cfg.NUM_GROUP, cfg.NUM_POINT_INS, cfg.NUM_CATEGORY, seed0=7).items()}
+    ngroup = torch.full((scenes,), cfg.NUM_GROUP, dtype=torch.int32, device=dev)
+    make = lambda **kw: T.DeviceDataset(d["pc"], d["color"], d["group_label"], d["seg_label"], d["pc_ins"], ngroup, **kw)
+    idx = torch.arange(b - 1, 2 * b - 1, dtype=torch.int32, device=dev)
+    seed = torch.tensor([7], dtype=torch.int64, device=dev)
+    plain, full = make(is_augment=True, permute_points=False), make(is_augment=True, permute_points=True)
+    out_plain, out_full = plain.batch(idx, seed), full.batch(idx, seed)
+    rot, tr, idx_long = out_plain["rotation"], out_plain["translation"], idx.long()
+    group, seg = d["group_label"].int(), d["seg_label"].int()
+
+    def chain():
+        pc, color = d["pc"].index_select(0, idx_long), d["color"].index_select(0, idx_long)
+        g, s = group.index_select(0, idx_long), seg.index_select(0, idx_long)
+        pc, pc_ins, indicator, bbox = dataset.augment_and_box(pc, d["pc_ins"].index_select(0, idx_long), ngroup.index_select(0, idx_long), rot, tr)
+        return pc, color, pc_ins, g, indicator, s, bbox, torch.ones((b, n), device=dev)
+
+    want = chain()
+    same = all(bool(torch.equal(out_plain[k], w)) for k, w in
+               zip(("pc", "color", "pc_ins", "group_label", "group_indicator", "seg_label", "bbox_ins", "smpw"), want))
+    res = timed_alternating({"batch_assemble": lambda: plain.batch(idx, seed, out=out_plain),
+                             "batch_assemble_with_permutation": lambda: full.batch(idx, seed, out=out_full),
+                             "index_select_augment_and_box": chain}, a.warmup, a.iters)
+    print(json.dumps({"shape": shape, "kind": a.kind, "measure": "train_batch", "groups": cfg.NUM_GROUP, "points_per_instance": cfg.NUM_POINT_INS,
+                      "equal_to_the_chain": same, "iters": a.iters, **res}), flush=True)
+
+    # the captured step, the loss terms summed on the device or read per step
+    trainer = T.Trainer(cfg, make(is_augment=True, permute_points=True), make(is_augment=False, permute_points=False), seed=1, captured=True)
+    batches = [list(range(k, k + b)) for k in range(0, scenes, b)]
+    read = lambda info: [float(v) for v in info["terms"].values()]
+
+    def steps(hook, count):
+        trainer.on_step = hook
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for k in range(count):
+            trainer.train_step(batches[k % len(batches)])
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / count
+
+    steps(None, a.warmup + 2)
+    ts = {"device_sums": [], "host_read_per_step": []}
+    for _ in range(5):
+        ts["device_sums"].append(steps(None, a.iters))
+        ts["host_read_per_step"].append(steps(read, a.iters))
+    trainer.sums.read()
+    print(json.dumps({"shape": shape, "kind": a.kind, "measure": "train_step", "terms": len(trainer.terms), "steps_per_block": a.iters,
+                      "includes": "batch assembly, geometry, graph replay, optimiser",
+                      **{k: {"median_ms": round(sorted(v)[len(v) // 2], 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4)}
+                         for k, v in ts.items()}}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points-per-instance", type=int, default=512)  # npoint_ins of --measures dataset (dataset.py:14)
@@ -676,6 +741,8 @@ def main():
             measure_dataset(a, shape, b, n, dev)
         if "predict" in measures:
             measure_predict(a, shape, b, n, dev)
+        if "train" in measures:
+            measure_train(a, shape, b, n, dev)
         if not set(measures) & {"step", "full_fwd", "nn"}:
             continue
         xyz = torch.from_numpy(synth.batch(a.kind, b, n)).to(dev)

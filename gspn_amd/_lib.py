@@ -145,6 +145,8 @@ SIGNATURES = {
     "gspn_adam_tf_flat": [_L, _P, _P, _P, _P, _F, _F, _F, _F, _F, _L, _P],
     "gspn_momentum_flat": [_L, _P, _P, _P, _F, _F, _F, _P],
     "gspn_scalars_accumulate": [_I, _P, _P, _P, _P],
+    "gspn_instance_overlaps": [_I, _I, _I, _I, _I] + [_P] * 8 + [_P],
+    "gspn_instance_match": [_I, _I, _I, _I, _I, _I] + [_P] * 13 + [_P],
 }
 
 # entry points that do not return an int status: symbol -> (argtypes, restype)

@@ -48,6 +48,8 @@ extern "C" {
  *  18: gspn_fps_segments (+ _ws_bytes).
  *  19: gspn_scene_confidence / gspn_scene_rank / gspn_sem_iou_counts.
  *  20: gspn_batch_assemble / gspn_adam_tf_flat / gspn_momentum_flat / gspn_scalars_accumulate. */
+/* Additive at 20: gspn_instance_overlaps / gspn_instance_match.  Nothing that was there changed, so the number stays; a binder that wants
+ * the two and finds an older library fails at the symbol lookup. */
 #define GSPN_ABI_VERSION 20
 int gspn_dist_policy(void);
 int gspn_abi_version(void);
@@ -725,6 +727,34 @@ int gspn_scene_rank(int b, int r, int c, const float* det_score, const int* clas
  * exact in any order).  A label outside [1, c) counts for no class.  2 <= c <= GSPN_SEM_IOU_MAX_C. */
 #define GSPN_SEM_IOU_MAX_C 256
 int gspn_sem_iou_counts(long rows, int c, const float* logits, const int* labels, long long* inter, long long* uni, void* stream);
+
+/* ---------------- instance AP evaluation: overlap counts and matching (gspn_amd/csrc/evaluate.hip, additive at ABI 20) ---- */
+
+/* The counts the metric needs, one workgroup per (scene, row) and one per scene.  masks (b,r,n) u8, a byte that is not 0 is a set point;
+ * pred_class (b,r) i32; seg_label, group_label (b,n) i32.  A point is VOID when its seg label is outside [1, c) or its group label is
+ * outside [0, g).  For a row k of class s in [1, c):
+ *   inter[k, j]   = the set points of k with seg == s and group == j          (b,r,g) i32
+ *   void_count[k] = its set points that are void,  pred_count[k] = its set points          (b,r) i32
+ * A row whose class is outside [1, c) writes zeros to all three.  gt_count[s, j] = the points of the scene that are not void and have
+ * seg == s and group == j, (b,c,g) i32; its row s = 0 is zero.  The mask is read 16 bytes per lane between the first and the last 16-byte
+ * boundary of a row and byte-wise outside, so masks needs no alignment; the label arrays are read at set bytes only.
+ * g <= GSPN_INSTANCE_MAX_G, c * g <= GSPN_INSTANCE_MAX_CG, b * r < 2^31 (GSPN_ERR_UNSUPPORTED beyond, before anything is launched). */
+#define GSPN_INSTANCE_MAX_G 4096
+#define GSPN_INSTANCE_MAX_CG 8192
+int gspn_instance_overlaps(int b, int r, int n, int c, int g, const unsigned char* masks, const int* pred_class, const int* seg_label,
+                           const int* group_label, int* inter, int* void_count, int* pred_count, int* gt_count, void* stream);
+
+/* The matching of DESIGN.md 4.18, one wave per (scene, threshold, class).  inter, void_count, pred_count, gt_count: gspn_instance_overlaps';
+ * pred_class (b,r) i32; confidence (b,r) f32; count (b,) i32: the rows k < count are the scene's predictions; thresholds (t,) f64.
+ * A row is valid when k < count, its class is in [1, c) and pred_count >= min_region; a gt (s, j) is eligible when gt_count >= min_region.
+ * iou = (double)inter / (double)(gt_count + pred_count - inter), compared by a strict > with the threshold.
+ *   n_true, n_false (b,t,r) i32: the records (true = 1 / true = 0, confidence[k]) row k contributes at that threshold
+ *   hard_fn (b,t,c) i32: the eligible gts of the class without an event;  n_gt, n_pred (b,c) i32: its eligible gts and its valid rows.
+ * r <= GSPN_INSTANCE_MATCH_MAX_R, min_region >= 1, b * t * c < 2^31 (GSPN_ERR_UNSUPPORTED beyond, before anything is launched). */
+#define GSPN_INSTANCE_MATCH_MAX_R 1024
+int gspn_instance_match(int b, int r, int c, int g, int t, int min_region, const int* inter, const int* void_count, const int* pred_count,
+                        const int* pred_class, const float* confidence, const int* count, const int* gt_count, const double* thresholds,
+                        int* n_true, int* n_false, int* hard_fn, int* n_gt, int* n_pred, void* stream);
 
 /* ---------------- train.py: the per-step batch, the reference's optimisers, the running loss sums (gspn_amd/csrc/train.hip, ABI 20) -------
  *

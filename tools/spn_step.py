@@ -36,6 +36,10 @@
             device (unmold_segmentation's (B, R, N) float tensor, a float64 matmul with the softmax table, two argsorts, the threshold),
             alternating in one process, and the stage replayed from a captured graph; whether the two orders and masks are equal and the
             largest relative difference of the confidences
+  evaluate  the instance AP counts of one batch (gspn_amd/evaluate.py) on synthetic masks at Config(istrain=False)'s widths -- 100 rows, 100
+            groups, 19 categories, the benchmark's 10 thresholds: instance_overlaps against the same counts written in torch on the device
+            (masks.float() against a one-hot of seg * G + group), each alone and in front of instance_match, alternating in one process,
+            and the two kernels replayed from a captured graph; whether the counts are equal
 
 Prints one JSON line per (shape, measurement): median / min milliseconds over --iters timed runs after --warmup runs.
     python tools/spn_step.py --shapes 2x18000,8x32768
@@ -48,6 +52,7 @@ Prints one JSON line per (shape, measurement): median / min milliseconds over --
     python tools/spn_step.py --shapes 2x18000,2x30000 --measures dataset --iters 30
     python tools/spn_step.py --shapes 2x18000 --measures predict --iters 30
     python tools/spn_step.py --shapes 2x18000,8x32768 --measures train --iters 20
+    python tools/spn_step.py --shapes 2x18000 --measures evaluate --iters 30
 """
 import argparse
 import json
@@ -642,6 +647,60 @@ def measure_predict(a, shape, b, n, dev):
                       "seeds": ns, "iters": a.iters, **res}), flush=True)
 
 
+def instance_counts_torch(masks, pred_class, seg, group, c, g):
+    """instance_overlaps' four outputs in torch on the device: masks.float() against a one-hot of seg * G + group, a (B, N, C * G) float tensor"""
+    live = (seg > 0) & (seg < c) & (group >= 0) & (group < g)
+    onehot = torch.nn.functional.one_hot(torch.where(live, seg * g + group, 0).long(), c * g).float() * live.unsqueeze(-1)
+    m = (masks != 0).float()
+    valid = (pred_class > 0) & (pred_class < c)
+    per_pair = torch.bmm(m, onehot).view(masks.shape[0], masks.shape[1], c, g)      # exact: counts below 2^24
+    at = pred_class.clamp(0, c - 1).long().view(masks.shape[0], masks.shape[1], 1, 1).expand(-1, -1, 1, g)
+    inter = (torch.gather(per_pair, 2, at).squeeze(2) * valid.unsqueeze(-1)).int()
+    void = (torch.bmm(m, (~live).float().unsqueeze(-1)).squeeze(-1) * valid).int()
+    return inter, void, (m.sum(-1) * valid).int(), onehot.sum(1).view(-1, c, g).int()
+
+
+def measure_evaluate(a, shape, b, n, dev):
+    """the instance AP counts of one batch (gspn_amd/evaluate.py) at Config(istrain=False)'s widths on synthetic masks: the two kernels, the
+    same counts in torch on the device in front of the same matching kernel, and the two kernels replayed from a captured graph"""
+    from gspn_amd import evaluate as EV
+    from gspn_amd import graph
+    from gspn_amd import rpointnet as RP
+    cfg = RP.Config(istrain=False)
+    r, c, g = cfg.DETECTION_MAX_INSTANCES, cfg.NUM_CATEGORY, 100
+    gen = torch.Generator().manual_seed(23)
+    cuts = torch.sort(torch.randint(0, n, (b, g - 1), generator=gen), 1)[0]
+    group = torch.searchsorted(cuts, torch.arange(n).expand(b, n).contiguous()).int()          # g runs of points, about 1 % of the scene each
+    seg_of = torch.randint(0, c, (b, g), generator=gen).int()
+    seg = torch.gather(seg_of, 1, group.long())
+    rows = torch.randint(0, g, (b, r), generator=gen)
+    masks = ((group.unsqueeze(1) == rows.unsqueeze(-1)) & (torch.rand(b, r, n, generator=gen) < 0.85)) | (torch.rand(b, r, n, generator=gen) < 0.001)
+    pred_class = torch.gather(seg_of, 1, rows)
+    confidence = torch.where(torch.rand(b, r, generator=gen) < 0.5, 1.0, 0.97).float()
+    count = torch.full((b,), 3 * r // 4, dtype=torch.int32)
+    masks, pred_class, seg, group, confidence, count = (t.to(dev).contiguous() for t in (masks.to(torch.uint8), pred_class, seg, group, confidence, count))
+    ours = EV.instance_overlaps(masks, pred_class, seg, group, c, g)
+    theirs = instance_counts_torch(masks, pred_class, seg, group, c, g)
+
+    def kernels():
+        return EV.instance_match(*EV.instance_overlaps(masks, pred_class, seg, group, c, g)[:3], pred_class, confidence, count, ours[3])
+
+    def torch_form():
+        inter, void, size, gt = instance_counts_torch(masks, pred_class, seg, group, c, g)
+        return EV.instance_match(inter, void, size, pred_class, confidence, count, gt)
+
+    res = {"mask_density": round(float((masks != 0).float().mean()), 5), "counts_equal": all(bool(torch.equal(x, y)) for x, y in zip(ours, theirs)),
+           "records": [int(v.sum()) for v in kernels()[:2]]}
+    st = {}
+    step = graph.CapturedStep(lambda: st.update(out=kernels()))
+    res.update(timed_alternating({"instance_overlaps": lambda: EV.instance_overlaps(masks, pred_class, seg, group, c, g),
+                                  "counts_torch_on_device": lambda: instance_counts_torch(masks, pred_class, seg, group, c, g),
+                                  "overlaps_and_match": kernels, "torch_counts_and_match": torch_form,
+                                  "overlaps_and_match_captured": step.replay}, a.warmup, a.iters))
+    print(json.dumps({"shape": shape, "measure": "evaluate", "rows": r, "groups": g, "categories": c, "thresholds": len(EV.DEFAULT_OVERLAPS),
+                      "iters": a.iters, **res}), flush=True)
+
+
 def measure_train(a, shape, b, n, dev):
     """train.py's per-step work around the network: DeviceDataset.batch (one gspn_batch_assemble call) against the same batch made with
     index_select + dataset.augment_and_box (given the same R and t on the device: its best case; it has no permutation, so the
@@ -743,6 +802,8 @@ def main():
             measure_predict(a, shape, b, n, dev)
         if "train" in measures:
             measure_train(a, shape, b, n, dev)
+        if "evaluate" in measures:
+            measure_evaluate(a, shape, b, n, dev)
         if not set(measures) & {"step", "full_fwd", "nn"}:
             continue
         xyz = torch.from_numpy(synth.batch(a.kind, b, n)).to(dev)

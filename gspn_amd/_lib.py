@@ -31,6 +31,18 @@ class GatherArgs(_c.Structure):
     _fields_ = [("feat", _P), ("ldf", _I), ("c", _I), ("gidx", _P), ("rel", _P), ("xyz_first", _I)]
 
 
+class DwArgs(_c.Structure):
+    """mirror of struct gspn_dw_args (include/gspn_hip.h)"""
+    _fields_ = [("X", _P), ("ldx", _I), ("var", _P), ("gamma", _P), ("eps", _F), ("use_bn", _I), ("is_training", _I), ("work", _P), ("dW", _P),
+                ("part2", _P), ("cin2", _I), ("nslots2", _I), ("dW2", _P)]
+
+
+class RsumArgs(_c.Structure):
+    """mirror of struct gspn_rsum_args (include/gspn_hip.h)"""
+    _fields_ = [("Yp", _P), ("ldyp", _I), ("scale", _P), ("shift", _P), ("mean", _P), ("var", _P), ("eps", _F), ("part", _P),
+                ("nparts_out", _c.POINTER(_I))]
+
+
 # symbol -> argtypes; every entry point of include/gspn_hip.h (tests check the list against the header)
 SIGNATURES = {
     "gspn_dist_policy": [],
@@ -88,8 +100,6 @@ SIGNATURES = {
     "gspn_dense_rsum": [_L, _I, _P, _I, _P, _I, _P, _P, _P, _P, _F, _P, _c.POINTER(_I), _P],
     "gspn_mlp_bwd_coef": [_L, _I, _I, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P],
     "gspn_mlp_bwd_wgrad_known": [_L, _I, _I, _c.POINTER(DyArgs), _P, _I, _P, _P, _c.POINTER(GatherArgs), _P, _P, _P],
-    "gspn_mlp_bwd_data_ex": [_L, _I, _I, _c.POINTER(DyArgs), _P, _I, _I, _P, _I, _P, _I, _P, _P, _F, _I, _I, _P, _P,
-                             _P, _I, _P, _P, _P, _P, _F, _P, _c.POINTER(_I), _P],
     "gspn_mlp_bwd_fused": [_L, _I, _I, _c.POINTER(DyArgs), _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _F, _P, _c.POINTER(_I), _P],
     "gspn_mlp_bwd_fused_coef": [_L, _I, _I, _c.POINTER(DyArgs), _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _F, _P, _c.POINTER(_I), _P, _P, _P, _P, _P, _P, _P, _P],
     "gspn_bn_finalize": [_L, _I, _P, _P, _P, _F, _F, _I, _P, _P, _P, _P, _P, _P, _P],
@@ -100,14 +110,10 @@ SIGNATURES = {
     "gspn_bn_colsum": [_L, _I, _P, _I, _P, _I, _P, _P, _F, _P, _c.POINTER(_I), _P],
     "gspn_bn_apply": [_L, _I, _P, _I, _P, _P, _I, _P, _I, _P],
     "gspn_bn_backward_apply": [_L, _I, _P, _I, _P, _I, _P, _P, _P, _P, _I, _P],
-    "gspn_mlp_bwd_data_pooltop": [_L, _I, _I, _c.POINTER(DyArgs), _P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _F, _I, _I, _P, _P,
-                                  _P, _I, _P, _P, _P, _P, _F, _P, _c.POINTER(_I), _P],
     "gspn_mlp_bwd_wgrad": [_L, _I, _I, _c.POINTER(DyArgs), _P, _I, _P, _P, _P, _P, _P, _F, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
-    "gspn_mlp_bwd_dw": [_L, _I, _I, _c.POINTER(DyArgs), _P, _I, _P, _P, _F, _I, _I, _P, _P, _P],
-    "gspn_mlp_bwd_data": [_L, _I, _I, _c.POINTER(DyArgs), _P, _P, _I, _P],
-    "gspn_mlp_bwd_data_cols": [_L, _I, _I, _c.POINTER(DyArgs), _P, _I, _I, _P, _I, _P],
-    "gspn_mlp_bwd_data_dw2": [_L, _I, _I, _c.POINTER(DyArgs), _P, _I, _I, _P, _I, _P, _I, _P, _P, _F, _I, _I, _P, _P, _P, _I, _I, _P, _P],
-    "gspn_mlp_bwd_data_dw": [_L, _I, _I, _c.POINTER(DyArgs), _P, _I, _I, _P, _I, _P, _I, _P, _P, _F, _I, _I, _P, _P, _P],
+    "gspn_mlp_bwd_dw": [_L, _I, _I, _c.POINTER(DyArgs), _c.POINTER(DwArgs), _P],
+    "gspn_mlp_bwd_data": [_L, _I, _I, _c.POINTER(DyArgs), _P, _I, _I, _P, _I, _c.POINTER(DwArgs), _c.POINTER(RsumArgs), _P],
+    "gspn_mlp_bwd_data_pooltop": [_L, _I, _I, _c.POINTER(DyArgs), _P, _P, _P, _P, _P, _I, _c.POINTER(DwArgs), _c.POINTER(RsumArgs), _P],
     "gspn_inverse_lists": [_I, _I, _I, _P, _P, _P, _P, _P],
     "gspn_grouppoint_grad_ws": [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     "gspn_scatteraddpoint_ws": [_I, _I, _I, _P, _P, _P, _P, _P],
@@ -177,7 +183,7 @@ SPECIAL = {
     "gspn_fps_segments_ws_bytes": ([_I, _I, _I], _L),
 }
 
-ABI_VERSION = 20       # == GSPN_ABI_VERSION of include/gspn_hip.h this binding was written against
+ABI_VERSION = 21       # == GSPN_ABI_VERSION of include/gspn_hip.h this binding was written against
 
 _lib = None
 

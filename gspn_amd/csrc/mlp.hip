@@ -2638,15 +2638,14 @@ static WgradPlan wgrad_choose(long rows, int cin, int cout, const gspn_dy_args* 
     *use_stream_out = use_stream;
     return p;
 }
-// the dW job of a layer whose pass A (gspn_mlp_bwd_wgrad(..., dW = NULL, ...) with the same rows/cin/cout/a/X/ldx_in, so that the workspace layout is found
-// again) left its partial tiles and sums in `work`
-static DwJob dw_job_from_work(long rows, int cin, int cout, const gspn_dy_args* a, const float* X, int ldx_in, const float* work, const float* var,
-                              const float* gamma, float eps, int use_bn, int is_training, float* dW) {
+// the dW job of a layer whose pass A (gspn_mlp_bwd_wgrad(..., dW = NULL, ...) with the same rows/cin/cout/a and dw->X / dw->ldx, so that the workspace
+// layout is found again) left its partial tiles and sums in dw->work
+static DwJob dw_job_from_work(long rows, int cin, int cout, const gspn_dy_args* a, const gspn_dw_args* dw) {
     bool use_stream;
-    const WgradPlan p = wgrad_choose(rows, cin, cout, a, X, ldx_in, &use_stream);
-    const char* wb = reinterpret_cast<const char*>(work);
+    const WgradPlan p = wgrad_choose(rows, cin, cout, a, dw->X, dw->ldx, &use_stream);
+    const char* wb = reinterpret_cast<const char*>(dw->work);
     return dw_job(rows, cin, cout, p.nslots, reinterpret_cast<const float*>(wb + ws_off_pp(p.nch, cin, cout)), reinterpret_cast<const double*>(wb),
-                  reinterpret_cast<const float*>(wb + ws_off_g3(cout)), var, gamma, eps, use_bn, is_training, dW);
+                  reinterpret_cast<const float*>(wb + ws_off_g3(cout)), dw->var, dw->gamma, dw->eps, dw->use_bn, dw->is_training, dw->dW);
 }
 
 static int wgrad_impl(long rows, int cin, int cout, const gspn_dy_args* a, const float* X, int ldx,
@@ -2954,7 +2953,7 @@ __device__ __forceinline__ void bwd_coef_block(const CoefJob& q, int n, double (
     if (dbeta) dbeta[n] = (float)r0;
     if (dbias) dbias[n] = 0.f;                                        // sum(dY) is exactly 0 under batch statistics
 }
-// coefficients of a training-mode BN layer from partial sums [nparts][2][c] (gspn_pool_rsum, or pass B's epilogue: gspn_mlp_bwd_data_rsum)
+// coefficients of a training-mode BN layer from partial sums [nparts][2][c] (gspn_pool_rsum, or pass B's epilogue: gspn_mlp_bwd_data with rs)
 extern "C" int gspn_mlp_bwd_coef(long rows, int c, int nparts, const float* part, const float* mean, const float* var, const float* gamma, float eps,
                                  float* cA, float* cB, float* cC, float* dgamma, float* dbeta, float* dbias, void* stream) {
     if (rows <= 0 || c <= 0 || nparts <= 0 || !part || !mean || !var || !cA || !cB || !cC) return GSPN_ERR_ARG;
@@ -2963,7 +2962,7 @@ extern "C" int gspn_mlp_bwd_coef(long rows, int c, int nparts, const float* part
 }
 static int gather_src(const gspn_gather_args* g, GatherSrc* out);
 // pass A with final coefficients in a->cA/cB/cC (one GEMM).  g: gather descriptor of a fused-front-end first layer, or NULL (then X/ldx/
-// in_scale/in_shift as in gspn_mlp_bwd_wgrad).  dW may be NULL (sum of the partial tiles left to gspn_mlp_bwd_data_dw with use_bn = 0).
+// in_scale/in_shift as in gspn_mlp_bwd_wgrad).  dW may be NULL (sum of the partial tiles left to gspn_mlp_bwd_data's dW job with use_bn = 0).
 extern "C" int gspn_mlp_bwd_wgrad_known(long rows, int cin, int cout, const gspn_dy_args* a, const float* X, int ldx, const float* in_scale,
                                         const float* in_shift, const gspn_gather_args* g, float* work, float* dW, void* stream) {
     if (g) {
@@ -3337,7 +3336,7 @@ __global__ __launch_bounds__(256) void preagg_bwd_dy_kernel(long rows, int cout,
 }
 extern "C" long gspn_preagg_part_floats(int cout, int side_n) { return (long)PREAGG_BWD_BLOCKS * 2 * side_n * cout + 4; }
 // dY (rows, cout) from (a.dZ, a.Y, a.scale/shift, a.cA/cB/cC); dWside (side_n, cout) = side^T . dY (deterministic two-level sum).
-// dWside == NULL leaves the second level to the caller: *nslots_out partial tiles at part (gspn_mlp_bwd_data_dw2 can carry it).
+// dWside == NULL leaves the second level to the caller: *nslots_out partial tiles at part (gspn_mlp_bwd_data can carry it as its second job).
 extern "C" int gspn_preagg_bwd_dy(long rows, int cout, const gspn_dy_args* a, const float* side, int side_ld, int side_n, float* dY, float* part,
                                   float* dWside, int* nslots_out, void* stream) {
     if (rows <= 0 || !a || !a->Y || !a->dZ || !a->scale || !a->shift || !a->cA || !a->cB || !a->cC || !dY || side_n < 0 || side_n > 4) return GSPN_ERR_ARG;
@@ -3360,12 +3359,11 @@ extern "C" int gspn_preagg_bwd_dy(long rows, int cout, const gspn_dy_args* a, co
     return gspn_launch_status();
 }
 
-extern "C" int gspn_mlp_bwd_dw(long rows, int cin, int cout, const gspn_dy_args* a, const float* X, int ldx, const float* var, const float* gamma,
-                               float eps, int use_bn, int is_training, const float* work, float* dW, void* stream) {
-    if (rows <= 0 || cin <= 0 || cout <= 0 || ldx < cin || !a || !a->Y || !work || !dW) return GSPN_ERR_ARG;
-    if (use_bn && !var) return GSPN_ERR_ARG;
+extern "C" int gspn_mlp_bwd_dw(long rows, int cin, int cout, const gspn_dy_args* a, const gspn_dw_args* dw, void* stream) {
+    if (rows <= 0 || cin <= 0 || cout <= 0 || !dw || dw->ldx < cin || !a || !a->Y || !dw->work || !dw->dW) return GSPN_ERR_ARG;
+    if (dw->use_bn && !dw->var) return GSPN_ERR_ARG;
     if (cin > MAXCH || cout > MAXCH || rows >= (1L << 31)) return GSPN_ERR_UNSUPPORTED;
-    const DwJob j = dw_job_from_work(rows, cin, cout, a, X, ldx, work, var, gamma, eps, use_bn, is_training, dW);
+    const DwJob j = dw_job_from_work(rows, cin, cout, a, dw);
     hipLaunchKernelGGL(wgrad_dw_kernel, dim3((unsigned)dw_blocks((long)j.cin * j.cout, j.nslots, 1024)), dim3(1024), 0, (hipStream_t)stream, j);
     return gspn_launch_status();
 }
@@ -3394,7 +3392,7 @@ template <int BN, bool VEC, bool POOLED, bool DW>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BN <= 32 ? GSPN_BWD_WPE32 : (BN <= 64 ? GSPN_BWD_WPE64 : 2))))
 void mlp_bwd_data_kernel(long rows, int cin, int cout, gspn_dy_args a, const float* __restrict__ W,
                                                            float* __restrict__ dX, int ldx, int col0, DwJob dwj, RsumArgs rs) {
-    // `cin` is the END of the column range [col0, cin) of dX this launch produces (gspn_mlp_bwd_data_cols)
+    // `cin` is the END of the column range [col0, cin) of dX this launch produces (gspn_mlp_bwd_data's col0 / ncols)
     constexpr int NT = BN / 32;
     constexpr int LDBT = BN + 1;                 // B written transposed: odd pitch
     constexpr int TKB = GSPN_BWD_TK;             // K chunk of THIS kernel: the chunk sequence (fetch, barrier, transform, barrier, MFMA) bounds it
@@ -4148,7 +4146,7 @@ extern "C" long gspn_mlp_bwd_fused_work_bytes(long rows, int cin, int cout) {
 // One launch for both backward products of a layer with KNOWN coefficients (a->cA/cB/cC final) and a dense upstream gradient:
 //   dW (cin, cout) = relu(Xp*in_scale + in_shift)^T . dY        (work: gspn_mlp_bwd_work_bytes(rows, cin, cout) bytes, as for pass A)
 //   dX (rows, ldx >= cin) = dY . W^T
-//   part (optional, with Xp's layer statistics): the BN reductions of dX against Xp, as gspn_mlp_bwd_data_ex leaves them; *nparts_out rows
+//   part (optional, with Xp's layer statistics): the BN reductions of dX against Xp, as gspn_mlp_bwd_data leaves them with rs; *nparts_out rows
 // GSPN_ERR_UNSUPPORTED for every shape outside the kernel's own (the caller then runs pass A and pass B).
 static int bwd_fused_impl(long rows, int cin, int cout, const gspn_dy_args* a, const float* W, const float* Xp, int ldxp, const float* in_scale,
                           const float* in_shift, float* dX, int ldx, float* work, float* dW, const float* mean_p, const float* var_p,
@@ -4245,42 +4243,31 @@ static int bwd_data_check(long rows, int cin, int cout, const gspn_dy_args* a, i
     if (rows >= (1L << 31)) return GSPN_ERR_UNSUPPORTED;
     return 0;
 }
-// columns [col0, col0 + ncols) of dX only: the rest of the row is left untouched (the caller does not need it -- e.g. the xyz columns
-// of a set-abstraction input, whose gradient pointnet_util.py never uses -- which can halve the N dimension of the GEMM)
-extern "C" int gspn_mlp_bwd_data_cols(long rows, int cin, int cout, const gspn_dy_args* a, const float* W, int col0, int ncols, float* dX, int ldx,
-                                      void* stream) {
+// The one pass-B entry point.  Columns [col0, col0 + ncols) of dX only: the rest of the row is left untouched (the caller does not need it
+// -- e.g. the xyz columns of a set-abstraction input, whose gradient pointnet_util.py never uses -- which can halve the N dimension of
+// the GEMM).  dw: the dW reduction that gspn_mlp_bwd_wgrad(..., dW = NULL) left undone rides in spare workgroups (same sums as
+// gspn_mlp_bwd_dw, 16 instead of 64 slot slices per output), with an optional second, plain reduction (what gspn_preagg_bwd_dy leaves
+// when it is not asked to reduce its partial tiles itself).  rs: the previous layer's BN reductions in the epilogue; *nparts_out = rows
+// of partials written to part, for gspn_mlp_bwd_coef.  The reductions need the whole row: col0 = 0, ncols = cin.
+extern "C" int gspn_mlp_bwd_data(long rows, int cin, int cout, const gspn_dy_args* a, const float* W, int col0, int ncols, float* dX, int ldx,
+                                 const gspn_dw_args* dw, const gspn_rsum_args* rs, void* stream) {
     const int rc = bwd_data_check(rows, cin, cout, a, col0, ncols, ldx);
     if (rc) return rc;
-    if (rows == 0) return 0;
-    return bwd_data_launch(rows, cin, cout, a, W, col0, ncols, dX, ldx, nullptr, (hipStream_t)stream);
-}
-// gspn_mlp_bwd_data_cols and gspn_mlp_bwd_dw in ONE launch: pass B of a layer plus the dW reduction that gspn_mlp_bwd_wgrad(..., dW = NULL)
-// left undone (same rows/cin/cout/a/X/ldx_in as that call, so that the workspace layout is found again).  dX and dW are what the two
-// separate calls produce (dW: same sums, 16 instead of 64 slot slices per output).
-extern "C" int gspn_mlp_bwd_data_dw(long rows, int cin, int cout, const gspn_dy_args* a, const float* W, int col0, int ncols, float* dX, int ldx,
-                                    const float* X, int ldx_in, const float* var, const float* gamma, float eps, int use_bn, int is_training,
-                                    const float* work, float* dW, void* stream) {
-    const int rc = bwd_data_check(rows, cin, cout, a, col0, ncols, ldx);
-    if (rc) return rc;
-    if (rows <= 0 || !work || !dW || ldx_in < cin || (use_bn && !var)) return GSPN_ERR_ARG;
-    const DwJob j = dw_job_from_work(rows, cin, cout, a, X, ldx_in, work, var, gamma, eps, use_bn, is_training, dW);
-    return bwd_data_launch(rows, cin, cout, a, W, col0, ncols, dX, ldx, &j, (hipStream_t)stream);
-}
-// gspn_mlp_bwd_data_dw with a second, plain reduction riding along: dW2 (cin2, cout) = the sum of nslots2 partial tiles at part2
-// (layout [slot][2][cin2*cout], first half used -- what gspn_preagg_bwd_dy leaves when it is not asked to reduce them itself)
-extern "C" int gspn_mlp_bwd_data_dw2(long rows, int cin, int cout, const gspn_dy_args* a, const float* W, int col0, int ncols, float* dX, int ldx,
-                                     const float* X, int ldx_in, const float* var, const float* gamma, float eps, int use_bn, int is_training,
-                                     const float* work, float* dW, const float* part2, int cin2, int nslots2, float* dW2, void* stream) {
-    const int rc = bwd_data_check(rows, cin, cout, a, col0, ncols, ldx);
-    if (rc) return rc;
-    if (rows <= 0 || !work || !dW || ldx_in < cin || (use_bn && !var)) return GSPN_ERR_ARG;
-    if (cin2 < 0 || nslots2 < 0 || (cin2 > 0 && (!part2 || !dW2 || nslots2 <= 0))) return GSPN_ERR_ARG;
-    DwJob j = dw_job_from_work(rows, cin, cout, a, X, ldx_in, work, var, gamma, eps, use_bn, is_training, dW);
-    if (cin2 > 0) {
-        j.PP2 = part2; j.dW2 = dW2; j.cin2 = cin2; j.nslots2 = nslots2;
-        j.nblk2 = (int)dw_blocks((long)cin2 * cout, nslots2, 256);
+    if (rows == 0) return (dw || rs) ? GSPN_ERR_ARG : 0;          // nothing to do, unless a job rides: that one needs rows
+    DwJob j;
+    if (dw) {
+        if (!dw->work || !dw->dW || (dw->X && dw->ldx < cin) || (dw->use_bn && !dw->var)) return GSPN_ERR_ARG;
+        if (dw->cin2 < 0 || dw->nslots2 < 0 || (dw->cin2 > 0 && (!dw->part2 || !dw->dW2 || dw->nslots2 <= 0))) return GSPN_ERR_ARG;
+        j = dw_job_from_work(rows, cin, cout, a, dw);
+        if (dw->cin2 > 0) {
+            j.PP2 = dw->part2; j.dW2 = dw->dW2; j.cin2 = dw->cin2; j.nslots2 = dw->nslots2;
+            j.nblk2 = (int)dw_blocks((long)dw->cin2 * cout, dw->nslots2, 256);
+        }
     }
-    return bwd_data_launch(rows, cin, cout, a, W, col0, ncols, dX, ldx, &j, (hipStream_t)stream);
+    if (rs && (!rs->part || !rs->Yp || rs->ldyp < cin || !rs->scale || !rs->shift || !rs->mean || !rs->var || !rs->nparts_out || col0 != 0 || ncols != cin))
+        return GSPN_ERR_ARG;
+    const RsumArgs r = rs ? RsumArgs{rs->Yp, rs->ldyp, rs->scale, rs->shift, rs->mean, rs->var, rs->eps, rs->part} : RsumArgs{};
+    return bwd_data_launch(rows, cin, cout, a, W, col0, ncols, dX, ldx, dw ? &j : nullptr, (hipStream_t)stream, rs ? &r : nullptr, rs ? rs->nparts_out : nullptr);
 }
 // ---- pass B of a pooled top layer as a streaming GEMM on the layer's input (mlp_fwd_stream_kernel<.., BWDP>) ----
 // the small operands: workgroups [0, cin): row n of M = W diag(cB) W^T and cvec[n] = sum_c (b[c]*cB[c] + cC[c]) * W[n][c]; the rest: the
@@ -4321,20 +4308,16 @@ extern "C" long gspn_pooltop_scratch_floats(long rows, int cin, int ctop) {
 // Pass B of a pooled top layer (pool groups of 32 rows) without reading the layer's (rows, ctop) output -- see BwdPool.  a: the layer's
 // gspn_dy_args (dPool, pool_arg, ns = 32, cA/cB/cC; Y only for the dW job's plan); pooled: the (rows/32, ctop) pooled output of the
 // forward pass; scratch: gspn_pooltop_scratch_floats floats.  The dW reduction of the layer rides in the small-operand launch; the previous
-// layer's BN reductions come out of the GEMM's epilogue (part / nparts_out as for gspn_mlp_bwd_data_ex, both required).
+// layer's BN reductions come out of the GEMM's epilogue (dw and rs as for gspn_mlp_bwd_data, both required; no second dW job here).
 // GSPN_ERR_UNSUPPORTED outside cin <= 64 (multiple of 4), ctop <= 128 (multiple of 4), ns = 32, 16-byte aligned operands.
 extern "C" int gspn_mlp_bwd_data_pooltop(long rows, int cin, int ctop, const gspn_dy_args* a, const float* W, const float* bias, const float* pooled,
-                                         float* scratch, float* dX, int ldx,
-                                         const float* X, int ldx_in, const float* var, const float* gamma, float eps, int use_bn, int is_training,
-                                         const float* work, float* dW,
-                                         const float* Yp, int ldyp, const float* scale_p, const float* shift_p, const float* mean_p, const float* var_p,
-                                         float eps_p, float* part, int* nparts_out, void* stream) {
-    if (rows <= 0 || cin <= 0 || ctop <= 0 || !a || !a->dPool || !a->pool_arg || !a->cA || !a->cB || !a->cC || !W || !pooled || !scratch || !dX ||
-        ldx < cin || !work || !dW || !part || !Yp || ldyp < cin || !scale_p || !shift_p || !mean_p || !var_p || !nparts_out)
+                                         float* scratch, float* dX, int ldx, const gspn_dw_args* dw, const gspn_rsum_args* rs, void* stream) {
+    if (rows <= 0 || cin <= 0 || ctop <= 0 || !a || !a->dPool || !a->pool_arg || !a->cA || !a->cB || !a->cC || !W || !pooled || !scratch || !dX || ldx < cin ||
+        !dw || !dw->work || !dw->dW || !rs || !rs->part || !rs->Yp || rs->ldyp < cin || !rs->scale || !rs->shift || !rs->mean || !rs->var || !rs->nparts_out)
         return GSPN_ERR_ARG;
-    if ((X && ldx_in < cin) || (use_bn && !var)) return GSPN_ERR_ARG;
+    if ((dw->X && dw->ldx < cin) || (dw->use_bn && !dw->var)) return GSPN_ERR_ARG;
     if (a->ns != 32 || (rows & 31) || (cin & 3) || cin > 64 || (ctop & 3) || ctop > 128 || rows >= (1L << 31) || rows * (long)ldx >= (1L << 31) ||
-        rows * (long)ldyp >= (1L << 31) || !vec_ok(Yp, ldyp) || ((uintptr_t)scratch % 16))
+        rows * (long)rs->ldyp >= (1L << 31) || !vec_ok(rs->Yp, rs->ldyp) || ((uintptr_t)scratch % 16))
         return GSPN_ERR_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
     const int BNs = cin <= 32 ? 32 : 64;
@@ -4343,7 +4326,7 @@ extern "C" int gspn_mlp_bwd_data_pooltop(long rows, int cin, int ctop, const gsp
     if (!trg) return GSPN_ERR_UNSUPPORTED;
     float* M = scratch;
     float* cvec = M + (size_t)cin * cin;
-    const DwJob j = dw_job_from_work(rows, cin, ctop, a, X, ldx_in, work, var, gamma, eps, use_bn, is_training, dW);
+    const DwJob j = dw_job_from_work(rows, cin, ctop, a, dw);
     hipLaunchKernelGGL(pooltop_prep_kernel, dim3((unsigned)(cin + j.nblk)), dim3(256), 0, st, cin, ctop, W, bias, a->cB, a->cC, M, cvec, j);
     const size_t dyn = sp.dyn;
     const long ntiles = (rows + 32 * trg - 1) / (32 * trg);
@@ -4352,41 +4335,12 @@ extern "C" int gspn_mlp_bwd_data_pooltop(long rows, int cin, int ctop, const gsp
     if (bpc < 1) bpc = 1;
     long gx = (long)GSPN_PLAN_CUS * bpc;
     if (gx > ntiles) gx = ntiles;
-    const BwdPool bp{a->pool_arg, a->dPool, pooled, a->cA, W, ctop, mean_p, var_p, eps_p};
+    const BwdPool bp{a->pool_arg, a->dPool, pooled, a->cA, W, ctop, rs->mean, rs->var, rs->eps};
 #define BWDP_GO(BN_, TRG_)                                                                                                             \
-    stream_launch<BN_, TRG_, false, true>(dim3((unsigned)gx, 1), dyn, st, (int)rows, cin, cin, Yp, ldyp, scale_p, shift_p, M, cvec, dX, ldx, part, (int)gx, \
+    stream_launch<BN_, TRG_, false, true>(dim3((unsigned)gx, 1), dyn, st, (int)rows, cin, cin, rs->Yp, rs->ldyp, rs->scale, rs->shift, M, cvec, dX, ldx, rs->part, (int)gx, \
                                           PoolOut{nullptr, nullptr}, GatherSrc{}, bp)
     const int rc = (BNs == 32 && trg == 4) ? BWDP_GO(32, 4) : ((BNs == 64 && trg == 4) ? BWDP_GO(64, 4) : BWDP_GO(64, 2));
 #undef BWDP_GO
-    *nparts_out = (int)gx;
+    *rs->nparts_out = (int)gx;
     return rc;
-}
-// Pass B with both options: the fused dW reduction of gspn_mlp_bwd_data_dw (work != NULL) and the previous layer's BN reductions in the
-// epilogue (part != NULL: Yp (rows, ldyp) = that layer's pre-BN output = this layer's input before activation; scale_p/shift_p its
-// forward scale/shift; mean_p/var_p its batch statistics; part = gspn_rsum_part_floats(rows, cin) floats; *nparts_out = rows of partials
-// written, for gspn_mlp_bwd_coef).  The reductions need the whole row: col0 = 0, ncols = cin.
-extern "C" int gspn_mlp_bwd_data_ex(long rows, int cin, int cout, const gspn_dy_args* a, const float* W, int col0, int ncols, float* dX, int ldx,
-                                    const float* X, int ldx_in, const float* var, const float* gamma, float eps, int use_bn, int is_training,
-                                    const float* work, float* dW,
-                                    const float* Yp, int ldyp, const float* scale_p, const float* shift_p, const float* mean_p, const float* var_p,
-                                    float eps_p, float* part, int* nparts_out, void* stream) {
-    const int rc = bwd_data_check(rows, cin, cout, a, col0, ncols, ldx);
-    if (rc) return rc;
-    if (rows <= 0) return GSPN_ERR_ARG;
-    DwJob j;
-    const DwJob* jp = nullptr;
-    if (work) {
-        if (!dW || (X && ldx_in < cin) || (use_bn && !var)) return GSPN_ERR_ARG;
-        j = dw_job_from_work(rows, cin, cout, a, X, ldx_in, work, var, gamma, eps, use_bn, is_training, dW);
-        jp = &j;
-    }
-    RsumArgs rs{nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0.f, nullptr};
-    if (part) {
-        if (!Yp || ldyp < cin || !scale_p || !shift_p || !mean_p || !var_p || !nparts_out || col0 != 0 || ncols != cin) return GSPN_ERR_ARG;
-        rs = RsumArgs{Yp, ldyp, scale_p, shift_p, mean_p, var_p, eps_p, part};
-    }
-    return bwd_data_launch(rows, cin, cout, a, W, col0, ncols, dX, ldx, jp, (hipStream_t)stream, part ? &rs : nullptr, nparts_out);
-}
-extern "C" int gspn_mlp_bwd_data(long rows, int cin, int cout, const gspn_dy_args* a, const float* W, float* dX, int ldx, void* stream) {
-    return gspn_mlp_bwd_data_cols(rows, cin, cout, a, W, 0, cin, dX, ldx, stream);
 }

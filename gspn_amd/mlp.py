@@ -7,8 +7,10 @@ reduce_max of :123-124 when `pool_ns` is given) as one autograd node: pre-BN act
 once, the BN+ReLU of layer l is applied inside the operand load of layer l+1, and backward rebuilds
 dY on the fly inside the two backward GEMMs.
 """
+import collections
 import ctypes
 import os
+import types
 
 import torch
 
@@ -35,7 +37,7 @@ PREAGG = os.environ.get("GSPN_PREAGG", "1") != "0"
 PREAGG_MIN_C = int(os.environ.get("GSPN_PREAGG_MIN_C", "16"))      # below this many feature columns the grouped GEMM is as cheap
 # pass B of a pooled top layer as a streaming GEMM on the layer's INPUT (gspn_mlp_bwd_data_pooltop): its (rows, cout) output is not read
 POOLTOP_STREAM = os.environ.get("GSPN_POOLTOP_STREAM", "1") != "0"
-# one launch for pass B + the dW reduction of the same layer (gspn_mlp_bwd_data_dw) instead of two
+# one launch for pass B + the dW reduction of the same layer (gspn_mlp_bwd_data with a gspn_dw_args) instead of two
 FUSE_DW = os.environ.get("GSPN_FUSE_DW", "1") != "0"
 # pass A and pass B of a layer in one launch where the library has the kernel for the shape (gspn_mlp_bwd_fused: both products from one staged
 # dY tile); the library's own switch is GSPN_BWD_FUSED
@@ -163,6 +165,11 @@ def _grad_release(param, buf, sunk):
         sunk.discard(buf.data_ptr())
 
 
+# what the forward pass keeps of one layer for backward: its input x (rows, ldx) (None when the rows are virtual) with the scale / shift
+# applied while loading it, its pre-BN output y, the statistics it normalised with and its own forward scale / shift
+_Saved = collections.namedtuple("_Saved", "x ldx cin in_scale in_shift y mean var scale shift")
+
+
 def _zeros(n, dev, dtype=torch.float32):
     return torch.zeros(n, dtype=dtype, device=dev)
 
@@ -263,7 +270,7 @@ class _MlpStack(torch.autograd.Function):
                     shift.zero_()
                     mean.zero_()
                     var.fill_(1.0)
-                saved.append((None if (li == 0 and (gather is not None or pre is not None)) else cur, cur_ld, cin, in_scale, in_shift, y, mean, var, scale, shift))
+                saved.append(_Saved(None if (li == 0 and (gather is not None or pre is not None)) else cur, cur_ld, cin, in_scale, in_shift, y, mean, var, scale, shift))
                 cur, cur_ld, cin, in_scale, in_shift = y, cout, cout, scale, shift
             cl = cin
             arg = None
@@ -312,252 +319,261 @@ class _MlpStack(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_out):
-        lib = L.lib()
         spec = ctx.spec
         layers = spec["layers"]
         for lp, (vw, vg) in zip(layers, ctx.versions):
             if lp.weights._version != vw or (lp.bn and lp.gamma._version != vg):
                 raise RuntimeError("mlp_stack: a weight or gamma tensor was modified in place between forward and backward")
-        is_training = bool(spec["is_training"])
-        pool_ns = spec["pool_ns"]
-        rows = ctx.rows
-        sw = ctx.sw
-        gather = ctx.gather
         d_out = d_out.contiguous()
         dev = d_out.device
+        is_training = bool(spec["is_training"])
+        # what the steps of this backward pass share.  coef: layer index -> (cA, cB, cC, dgamma, dbeta, dbias) taken BEFORE that layer's pass A;
+        # sunk: data pointers of gradient buffers that ARE bucket slices (returned to autograd as None)
+        b = types.SimpleNamespace(lib=L.lib(), ctx=ctx, spec=spec, layers=layers, rows=ctx.rows, sw=ctx.sw, dev=dev, d_out=d_out, pool_ns=spec["pool_ns"],
+                                  is_training=is_training, tr_all=is_training and EARLY_R and not DEFER_DW, coef={}, sunk=set(), side=None, main=None, keep=[])
         grads = []
-        sunk = set()                             # data pointers of gradient buffers that ARE bucket slices (returned to autograd as None)
-        dz = None if pool_ns else d_out          # dense upstream gradient of the current layer
-        ldz = d_out.shape[1]
-        dx0 = None
-        side = main = None
-        keep = []
+        dz, ldz = (None if b.pool_ns else d_out), d_out.shape[1]        # dz: dense upstream gradient of the current layer
         with torch.cuda.device(dev):
-            st = L.stream()
-            tr_all = is_training and EARLY_R and not DEFER_DW
-            coef = {}                            # layer index -> (cA, cB, cC, dgamma, dbeta, dbias) taken BEFORE that layer's pass A
+            b.st = L.stream()
             for li in range(len(layers) - 1, -1, -1):
-                lp = layers[li]
-                (xin, xld, cin, in_scale, in_shift, y, mean, var, scale, shift) = ctx.saved[li]
-                cout = lp.weights.shape[1]
+                lp, s = layers[li], ctx.saved[li]
+                cin, cout = s.cin, lp.weights.shape[1]
                 a = L.DyArgs()
-                a.Y, a.ldy = y.data_ptr(), cout
+                a.Y, a.ldy = s.y.data_ptr(), cout
                 if dz is None:
-                    a.dZ, a.ldz, a.dPool, a.pool_arg, a.ns = None, 0, d_out.data_ptr(), ctx.arg.data_ptr(), pool_ns
+                    a.dZ, a.ldz, a.dPool, a.pool_arg, a.ns = None, 0, d_out.data_ptr(), ctx.arg.data_ptr(), b.pool_ns
                 else:
                     a.dZ, a.ldz, a.dPool, a.pool_arg, a.ns = dz.data_ptr(), ldz, None, None, 0
-                a.scale, a.shift = scale.data_ptr(), shift.data_ptr()
-                gather0 = gather if li == 0 else None
-                # ---- early coefficients of the top layer of a pooled stack: (groups x c) work on (dPool, arg, Y) ----
-                if tr_all and lp.bn and dz is None and li not in coef:
-                    part = torch.empty(int(lib.gspn_rsum_part_floats(rows, cout)), dtype=torch.float32, device=dev)
-                    npart = ctypes.c_int(0)
-                    yarg = ctx.pool_yarg           # y at the arg row, left by gspn_pool32_select (None: gather it from Y)
-                    L.check(lib.gspn_pool_rsum(rows // pool_ns, pool_ns, cout, L.ptr(d_out), L.ptr(ctx.arg), L.ptr(y if yarg is None else yarg),
-                                               cout if yarg is None else 0, L.ptr(scale), L.ptr(shift),
-                                               L.ptr(mean), L.ptr(var), BN_EPS, L.ptr(part), ctypes.byref(npart), st), "pool_rsum")
-                    coef[li] = _coef_from_parts(lib, rows, cout, npart.value, part, mean, var, lp, dev, st, sw, sunk)
-                # ---- early coefficients of the top layer of a DENSE stack: one streaming pass over (d_out, Y); worth its launch on the long
-                #      layers only (the two-product pass A of a short layer costs less than the extra dependent kernels) ----
-                if (tr_all and (DENSE_TOP_RSUM or sw > 1) and lp.bn and dz is not None and li == len(layers) - 1 and li not in coef
-                        and ((li > 0 and rows >= DENSE_TOP_MIN_ROWS) or (sw > 1 and gather0 is None and not (li == 0 and ctx.pre is not None)))):
-                    part = torch.empty(int(lib.gspn_rsum_part_floats(rows, cout)), dtype=torch.float32, device=dev)
-                    npart = ctypes.c_int(0)
-                    try:
-                        L.check(lib.gspn_dense_rsum(rows, cout, L.ptr(dz), ldz, L.ptr(y), cout, L.ptr(scale), L.ptr(shift), L.ptr(mean), L.ptr(var),
-                                                    BN_EPS, L.ptr(part), ctypes.byref(npart), st), "dense_rsum")
-                        coef[li] = _coef_from_parts(lib, rows, cout, npart.value, part, mean, var, lp, dev, st, sw, sunk)
-                    except NotImplementedError:
-                        pass
-                known = coef.get(li)
-                if sw > 1 and lp.bn and known is None:
+                a.scale, a.shift = s.scale.data_ptr(), s.shift.data_ptr()
+                gather0 = ctx.gather if li == 0 else None
+                if li == len(layers) - 1:
+                    _early_top_coef(b, li, dz, ldz)
+                known = b.coef.get(li)
+                if b.sw > 1 and lp.bn and known is None:
                     raise RuntimeError("mlp_stack (fused SyncBN): layer %d has no early BN coefficients -- its reductions would be per replica" % li)
-                if known is not None:
-                    cA, cB, cC, dgamma, dbeta, dbias = known
-                else:
-                    cA = torch.empty(cout, dtype=torch.float32, device=dev)
-                    cB = torch.empty(cout, dtype=torch.float32, device=dev)
-                    cC = torch.empty(cout, dtype=torch.float32, device=dev)
-                    dgamma = _grad_buffer(lp.gamma, sunk) if lp.bn else None
-                    dbeta = _grad_buffer(lp.beta, sunk) if lp.bn else None
-                    dbias = _grad_buffer(lp.biases, sunk)
+                cf = known
+                if known is None:
+                    cf = [torch.empty(cout, dtype=torch.float32, device=dev) for _ in range(3)]
+                    cf += [_grad_buffer(lp.gamma, b.sunk) if lp.bn else None, _grad_buffer(lp.beta, b.sunk) if lp.bn else None, _grad_buffer(lp.biases, b.sunk)]
+                cA, cB, cC, dgamma, dbeta, dbias = cf
                 a.cA, a.cB, a.cC = cA.data_ptr(), cB.data_ptr(), cC.data_ptr()
                 if li == 0 and ctx.pre is not None:
                     if known is None:
                         raise RuntimeError("mlp_stack(preagg=): the first layer's BN coefficients must be known before its backward (EARLY_R)")
                     ev = _tic()
-                    dW, dx0 = _preagg_backward(lib, ctx.pre, ctx.pre_x, lp, a, rows, cout, ctx.x_needs_grad, dev, st, sunk)
+                    dW, dx = _preagg_backward(b.lib, ctx.pre, ctx.pre_x, lp, a, b.rows, cout, ctx.x_needs_grad, dev, b.st, b.sunk)
                     # (the whole backward of the layer, both "passes": dW_feat and d(feat) on the source rows, dW_side on the output rows)
-                    _toc(ev, "bwd", rows, cin, cout, 2.0 * cout * (ctx.pre_x.shape[0] * ctx.pre["c"] * (2 if ctx.x_needs_grad else 1) + rows * ctx.pre["side_n"]))
-                    g = [dW, dbias]
-                    if lp.bn:
-                        g += [dbeta, dgamma]
-                    grads = g + grads
+                    _toc(ev, "bwd", b.rows, cin, cout, 2.0 * cout * (ctx.pre_x.shape[0] * ctx.pre["c"] * (2 if ctx.x_needs_grad else 1) + b.rows * ctx.pre["side_n"]))
+                    grads = [dW, dbias] + ([dbeta, dgamma] if lp.bn else []) + grads
                     del a
                     continue
-                dW = _grad_buffer(lp.weights, sunk)
-                wcin = int(lib.gspn_mlp_gather_cin(ctypes.byref(ctx.gargs))) if gather0 is not None else cin
-                work = torch.empty(int(lib.gspn_mlp_bwd_work_bytes(rows, wcin, cout)) // 4 + 4, dtype=torch.float32, device=dev)
+                dW = _grad_buffer(lp.weights, b.sunk)
+                grads = [dW, dbias] + ([dbeta, dgamma] if lp.bn else []) + grads
+                wcin = int(b.lib.gspn_mlp_gather_cin(ctypes.byref(ctx.gargs))) if gather0 is not None else cin
+                work = torch.empty(int(b.lib.gspn_mlp_bwd_work_bytes(b.rows, wcin, cout)) // 4 + 4, dtype=torch.float32, device=dev)
                 has_dx = li > 0 or ctx.x_needs_grad
-                # ---- both passes in one launch (known coefficients, dense dz, an inner layer of a shape the fused kernel takes) ----
-                if (FUSED_BWD and known is not None and (dz is not None or (pool_ns == 32 and POOLTOP_FUSED)) and li > 0 and not DEFER_DW
-                        and int(lib.gspn_mlp_bwd_fused_work_bytes(rows, cin, cout)) > 0):
-                    prev = layers[li - 1]
-                    want_rsum = tr_all and prev.bn
-                    (_, _, _, _, _, pY, pmean, pvar, pscale, pshift) = ctx.saved[li - 1]
-                    dx = torch.empty((rows, cin), dtype=torch.float32, device=dev)
-                    part = torch.empty(int(lib.gspn_rsum_part_floats(rows, cin)), dtype=torch.float32, device=dev) if want_rsum else None
-                    npart = ctypes.c_int(0)
-                    ev = _tic()
-                    merged = None
-                    pg = None
-                    try:
-                        if want_rsum and sw == 1 and FUSED_COEF:
-                            # the previous layer's coefficient kernel and this layer's dW reduction depend on the fused launch only: one launch
-                            pc = [torch.empty(cin, dtype=torch.float32, device=dev) for _ in range(3)]
-                            pg = [_grad_buffer(prev.gamma, sunk), _grad_buffer(prev.beta, sunk), _grad_buffer(prev.biases, sunk)]
-                            L.check(lib.gspn_mlp_bwd_fused_coef(rows, cin, cout, ctypes.byref(a), L.ptr(lp.weights), L.ptr(xin), xld, L.ptr(in_scale),
-                                                                L.ptr(in_shift), L.ptr(dx), cin, L.ptr(work), L.ptr(dW), L.ptr(pmean), L.ptr(pvar), BN_EPS,
-                                                                L.ptr(part), ctypes.byref(npart), L.ptr(prev.gamma), L.ptr(pc[0]), L.ptr(pc[1]), L.ptr(pc[2]),
-                                                                L.ptr(pg[0]), L.ptr(pg[1]), L.ptr(pg[2]), st), "mlp_bwd_fused_coef")
-                            merged = (pc[0], pc[1], pc[2], pg[0], pg[1], pg[2])
-                        else:
-                            L.check(lib.gspn_mlp_bwd_fused(rows, cin, cout, ctypes.byref(a), L.ptr(lp.weights), L.ptr(xin), xld, L.ptr(in_scale), L.ptr(in_shift),
-                                                           L.ptr(dx), cin, L.ptr(work), L.ptr(dW), L.ptr(pmean), L.ptr(pvar), BN_EPS, L.ptr(part),
-                                                           ctypes.byref(npart), st), "mlp_bwd_fused")
-                        fused = True
-                    except NotImplementedError:
-                        fused = False
-                        if pg is not None:           # the declined launch filled none of the previous layer's sinks: hand them back
-                            for prm, buf in zip((prev.gamma, prev.beta, prev.biases), pg):
-                                _grad_release(prm, buf, sunk)
-                    if fused:
-                        _toc(ev, "fused", rows, cin, cout, 4.0 * rows * cin * cout)
-                        if merged is not None:
-                            coef[li - 1] = merged
-                        elif want_rsum:
-                            coef[li - 1] = _coef_from_parts(lib, rows, cin, npart.value, part, pmean, pvar, prev, dev, st, sw, sunk)
-                        g = [dW, dbias]
-                        if lp.bn:
-                            g += [dbeta, dgamma]
-                        grads = g + grads
-                        dz, ldz = dx, cin
-                        del a
-                        continue
-                fuse_dw = FUSE_DW and has_dx and not DEFER_DW and gather0 is None     # the dW reduction rides in spare workgroups of this layer's pass B
-                # ---- pass A ----
-                ev = _tic()
-                ran_known = False
-                if known is not None:
-                    try:
-                        L.check(lib.gspn_mlp_bwd_wgrad_known(rows, cin, cout, ctypes.byref(a), L.ptr(xin), xld, L.ptr(in_scale), L.ptr(in_shift),
-                                                             ctypes.byref(ctx.gargs) if gather0 is not None else None, L.ptr(work),
-                                                             None if fuse_dw else L.ptr(dW), st), "mlp_bwd_wgrad_known")
-                        ran_known = True
-                    except NotImplementedError:
-                        ran_known = False            # a shape the one-GEMM kernels do not take: the two-product pass recomputes the same coefficients
-                if not ran_known:
-                    if gather0 is not None:
-                        L.check(lib.gspn_mlp_bwd_wgrad_gather(rows, ctypes.byref(ctx.gargs), cout, ctypes.byref(a), L.ptr(mean), L.ptr(var),
-                                                              L.ptr(lp.gamma if lp.bn else None), BN_EPS, int(lp.bn), int(is_training), L.ptr(work),
-                                                              L.ptr(cA), L.ptr(cB), L.ptr(cC), L.ptr(dgamma), L.ptr(dbeta), L.ptr(dbias), L.ptr(dW), st),
-                                "mlp_bwd_wgrad_gather")
-                    else:
-                        L.check(lib.gspn_mlp_bwd_wgrad(rows, cin, cout, ctypes.byref(a), L.ptr(xin), xld, L.ptr(in_scale), L.ptr(in_shift),
-                                                       L.ptr(mean), L.ptr(var), L.ptr(lp.gamma if lp.bn else None), BN_EPS, int(lp.bn), int(is_training),
-                                                       L.ptr(work), L.ptr(cA), L.ptr(cB), L.ptr(cC), L.ptr(dgamma), L.ptr(dbeta), L.ptr(dbias),
-                                                       None if (DEFER_DW or fuse_dw) else L.ptr(dW), st), "mlp_bwd_wgrad")
-                _toc(ev, "wgrad", rows, cin, cout, None if ran_known else 2 * 2.0 * rows * cin * cout)      # the two-product form: G1 and Gx
-                if DEFER_DW and gather0 is None:
-                    if side is None:
-                        side = _side_stream(dev)
-                        main = torch.cuda.current_stream()
-                    side.wait_event(main.record_event())            # after this layer's wgrad + channel sums
-                    L.check(lib.gspn_mlp_bwd_dw(rows, cin, cout, ctypes.byref(a), L.ptr(xin), xld, L.ptr(var), L.ptr(lp.gamma if lp.bn else None),
-                                                BN_EPS, int(lp.bn), int(is_training), L.ptr(work), L.ptr(dW),
-                                                ctypes.c_void_p(side.cuda_stream)), "mlp_bwd_dw")
-                    keep.append((work, a))                          # alive until the side stream has joined below
-                g = [dW, dbias]
-                if lp.bn:
-                    g += [dbeta, dgamma]
-                grads = g + grads
-                # ---- pass B ----
-                if has_dx and gather0 is not None:
-                    # the gathered layer: dX of the feature columns in grouped-row layout, then the gather-form gradient of the grouping
-                    # (inverse lists; atomics without them) straight into d(features)
-                    gb, gn, gm, gns = gather0["dims"]
-                    gc, xf = gather0["c"], int(gather0["xyz_first"])
-                    ldp = (3 + gc + 3) // 4 * 4
-                    dxg = torch.empty((rows, ldp), dtype=torch.float32, device=dev)
-                    ev = _tic()
-                    L.check(lib.gspn_mlp_bwd_data_cols(rows, cin, cout, ctypes.byref(a), L.ptr(lp.weights), 3 if xf else 0, gc, L.ptr(dxg), ldp, st),
-                            "mlp_bwd_data_cols")
-                    _toc(ev, "bwd", rows, cin, cout, 2.0 * rows * gc * cout)
-                    gp = torch.empty((gb, gn, gc), dtype=torch.float32, device=dev)
-                    if gather0.get("order") is not None:
-                        L.check(lib.gspn_sa_group_concat_grad_csr(gb, gn, gc, gm, gns, L.ptr(gather0["order"]), L.ptr(gather0["offsets"]), xf, ldp,
-                                                                  L.ptr(dxg), L.ptr(gp), st), "sa_group_concat_grad_csr")
-                    else:
-                        L.check(lib.gspn_sa_group_concat_grad(gb, gn, gc, gm, gns, L.ptr(gather0["idx"]), xf, ldp, L.ptr(dxg), L.ptr(gp), st),
-                                "sa_group_concat_grad")
-                    ldf = ctx.gargs.ldf
-                    dx0 = gp.view(gb * gn, gc)
-                    if ldf != gc:
-                        dx0 = torch.nn.functional.pad(dx0, (0, ldf - gc))
-                elif has_dx:
-                    dx = torch.empty((rows, xld), dtype=torch.float32, device=dev) if li == 0 else torch.empty((rows, cin), dtype=torch.float32, device=dev)
-                    if li == 0 and xld > cin and spec.get("grad_cols") is None:
-                        dx.zero_()
-                    # only grad_cols of the input feed a gradient upstream (e.g. not the xyz columns of an SA input)
-                    gc = (spec.get("grad_cols") if li == 0 else None) or (0, cin)
-                    # this dX is the dz of layer li-1: its epilogue can take that layer's BN reductions (early coefficients for its pass A)
-                    prev = layers[li - 1] if li > 0 else None
-                    want_rsum = tr_all and prev is not None and prev.bn
-                    ev = _tic()
-                    if want_rsum or fuse_dw:
-                        part = npart = None
-                        pY = pmean = pvar = pscale = pshift = None
-                        if want_rsum:
-                            (_, _, _, _, _, pY, pmean, pvar, pscale, pshift) = ctx.saved[li - 1]
-                            part = torch.empty(int(lib.gspn_rsum_part_floats(rows, cin)), dtype=torch.float32, device=dev)
-                            npart = ctypes.c_int(0)
-                        bn_dw = 0 if ran_known else int(lp.bn)           # known coefficients: the partial tiles are dW's own (plain sum)
-                        top_done = False
-                        if (POOLTOP_STREAM and dz is None and pool_ns == 32 and want_rsum and fuse_dw and known is not None and cin <= 64
-                                and cin % 4 == 0 and cout <= 128 and cout % 4 == 0 and tuple(gc) == (0, cin)):
-                            scr = torch.empty(int(lib.gspn_pooltop_scratch_floats(rows, cin, cout)), dtype=torch.float32, device=dev)
-                            try:
-                                L.check(lib.gspn_mlp_bwd_data_pooltop(rows, cin, cout, ctypes.byref(a), L.ptr(lp.weights), L.ptr(lp.biases),
-                                                                      L.ptr(ctx.saved_tensors[0]), L.ptr(scr), L.ptr(dx), dx.shape[1],
-                                                                      L.ptr(xin), xld, L.ptr(var), L.ptr(lp.gamma if lp.bn else None), BN_EPS, bn_dw,
-                                                                      int(is_training), L.ptr(work), L.ptr(dW),
-                                                                      L.ptr(pY), cin, L.ptr(pscale), L.ptr(pshift), L.ptr(pmean), L.ptr(pvar), BN_EPS,
-                                                                      L.ptr(part), ctypes.byref(npart), st), "mlp_bwd_data_pooltop")
-                                top_done = True
-                            except NotImplementedError:
-                                top_done = False
-                        if not top_done:
-                          L.check(lib.gspn_mlp_bwd_data_ex(rows, cin, cout, ctypes.byref(a), L.ptr(lp.weights), int(gc[0]), int(gc[1]), L.ptr(dx), dx.shape[1],
-                                                         L.ptr(xin), xld, L.ptr(var), L.ptr(lp.gamma if lp.bn else None), BN_EPS, bn_dw,
-                                                         int(is_training), L.ptr(work) if fuse_dw else None, L.ptr(dW) if fuse_dw else None,
-                                                         L.ptr(pY), cin, L.ptr(pscale), L.ptr(pshift), L.ptr(pmean), L.ptr(pvar), BN_EPS, L.ptr(part),
-                                                         ctypes.byref(npart) if want_rsum else None, st), "mlp_bwd_data_ex")
-                        if want_rsum:
-                            coef[li - 1] = _coef_from_parts(lib, rows, cin, npart.value, part, pmean, pvar, prev, dev, st, sw, sunk)
-                    else:
-                        L.check(lib.gspn_mlp_bwd_data_cols(rows, cin, cout, ctypes.byref(a), L.ptr(lp.weights), int(gc[0]), int(gc[1]), L.ptr(dx),
-                                                           dx.shape[1], st), "mlp_bwd_data_cols")
-                    _toc(ev, "bwd", rows, cin, cout, 2.0 * rows * int(gc[1]) * cout)
-                    if li == 0:
-                        dx0 = dx
+                dx = _fused_attempt(b, li, a, known, dz, work, dW)
+                if dx is None:
+                    fuse_dw = FUSE_DW and has_dx and not DEFER_DW and gather0 is None     # the dW reduction rides in spare workgroups of this layer's pass B
+                    later = fuse_dw or (DEFER_DW and gather0 is None)      # the sum over pass A's partial tiles is left to pass B / the side stream
+                    ran_known = _pass_a(b, li, a, known, cf, work, None if later else dW)
+                    if DEFER_DW and gather0 is None:
+                        _deferred_dw(b, li, a, work, dW)
+                    # known coefficients: the partial tiles are dW's own (plain sum)
+                    ride = _dw_args(s, lp, 0 if ran_known else int(lp.bn), is_training, work, dW) if fuse_dw else None
+                    if has_dx:
+                        dx = _pass_b_gathered(b, a, gather0) if gather0 is not None else _pass_b(b, li, a, known, dz, ride)
+                if li > 0:
                     dz, ldz = dx, dx.shape[1]
                 # keep the buffers referenced by `a` alive until the kernels are enqueued (same stream: ordered)
                 del a
-            if side is not None:
-                main.wait_event(side.record_event())                # join: the gradients (and the workspaces) are complete past here
-        del keep
-        # gradients that were written straight into their bucket slices are not handed to autograd (it would re-assign / clone them)
-        return (dx0, None, None) + tuple(None if (g is not None and g.data_ptr() in sunk) else g for g in grads)
+            if b.side is not None:
+                b.main.wait_event(b.side.record_event())            # join: the gradients (and the workspaces) are complete past here
+        del b.keep
+        # dx: layer 0's.  Gradients that were written straight into their bucket slices are not handed to autograd (it would re-assign / clone them)
+        return (dx, None, None) + tuple(None if (g is not None and g.data_ptr() in b.sunk) else g for g in grads)
+
+
+def _ref(struct):
+    return None if struct is None else ctypes.byref(struct)
+
+
+def _dw_args(s, lp, use_bn, is_training, work, dW):
+    """gspn_dw_args of a layer from its saved record: the dW reduction its pass A, run with dW = NULL, left in `work`"""
+    return L.DwArgs(L.ptr(s.x), s.ldx, L.ptr(s.var), L.ptr(lp.gamma if lp.bn else None), BN_EPS, use_bn, int(is_training), L.ptr(work), L.ptr(dW))
+
+
+def _rsum_args(b, p, c):
+    """(gspn_rsum_args, part, npart) from the saved record p of the PREVIOUS layer (c channels): its BN reductions out of this layer's pass B"""
+    part = torch.empty(int(b.lib.gspn_rsum_part_floats(b.rows, c)), dtype=torch.float32, device=b.dev)
+    npart = ctypes.c_int(0)
+    return L.RsumArgs(L.ptr(p.y), c, L.ptr(p.scale), L.ptr(p.shift), L.ptr(p.mean), L.ptr(p.var), BN_EPS, L.ptr(part), ctypes.pointer(npart)), part, npart
+
+
+def _early_top_coef(b, li, dz, ldz):
+    """early coefficients of the stack's top layer, from its upstream gradient, into b.coef[li]"""
+    lib, rows, ctx, lp, s = b.lib, b.rows, b.ctx, b.layers[li], b.ctx.saved[li]
+    cout = lp.weights.shape[1]
+    # a DENSE stack takes them in one streaming pass over (d_out, Y): worth its launch on the long layers only (the two-product pass A of a
+    # short layer costs less than the extra dependent kernels)
+    dense = dz is not None and (DENSE_TOP_RSUM or b.sw > 1) and (
+        (li > 0 and rows >= DENSE_TOP_MIN_ROWS) or (b.sw > 1 and not (li == 0 and (ctx.gather is not None or ctx.pre is not None))))
+    if not (b.tr_all and lp.bn and li not in b.coef and (dz is None or dense)):
+        return
+    part = torch.empty(int(lib.gspn_rsum_part_floats(rows, cout)), dtype=torch.float32, device=b.dev)
+    npart = ctypes.c_int(0)
+    if dz is None:
+        # ---- a pooled stack: (groups x c) work on (dPool, arg, Y) ----
+        yarg = ctx.pool_yarg           # y at the arg row, left by gspn_pool32_select (None: gather it from Y)
+        L.check(lib.gspn_pool_rsum(rows // b.pool_ns, b.pool_ns, cout, L.ptr(b.d_out), L.ptr(ctx.arg), L.ptr(s.y if yarg is None else yarg),
+                                   cout if yarg is None else 0, L.ptr(s.scale), L.ptr(s.shift),
+                                   L.ptr(s.mean), L.ptr(s.var), BN_EPS, L.ptr(part), ctypes.byref(npart), b.st), "pool_rsum")
+        b.coef[li] = _coef_from_parts(lib, rows, cout, npart.value, part, s.mean, s.var, lp, b.dev, b.st, b.sw, b.sunk)
+    else:
+        try:
+            L.check(lib.gspn_dense_rsum(rows, cout, L.ptr(dz), ldz, L.ptr(s.y), cout, L.ptr(s.scale), L.ptr(s.shift), L.ptr(s.mean), L.ptr(s.var),
+                                        BN_EPS, L.ptr(part), ctypes.byref(npart), b.st), "dense_rsum")
+            b.coef[li] = _coef_from_parts(lib, rows, cout, npart.value, part, s.mean, s.var, lp, b.dev, b.st, b.sw, b.sunk)
+        except NotImplementedError:
+            pass
+
+
+def _fused_attempt(b, li, a, known, dz, work, dW):
+    """both passes of layer li in one launch (known coefficients, an inner layer of a shape the fused kernel takes): its dX, or None when
+    the launch is not tried or the library declines it"""
+    lib, rows, layers, lp, s = b.lib, b.rows, b.layers, b.layers[li], b.ctx.saved[li]
+    cin, cout = s.cin, lp.weights.shape[1]
+    if not (FUSED_BWD and known is not None and (dz is not None or (b.pool_ns == 32 and POOLTOP_FUSED)) and li > 0 and not DEFER_DW
+            and int(lib.gspn_mlp_bwd_fused_work_bytes(rows, cin, cout)) > 0):
+        return None
+    prev, p = layers[li - 1], b.ctx.saved[li - 1]
+    want_rsum = b.tr_all and prev.bn
+    dx = torch.empty((rows, cin), dtype=torch.float32, device=b.dev)
+    part = torch.empty(int(lib.gspn_rsum_part_floats(rows, cin)), dtype=torch.float32, device=b.dev) if want_rsum else None
+    npart = ctypes.c_int(0)
+    ev = _tic()
+    merged = pg = None
+    try:
+        if want_rsum and b.sw == 1 and FUSED_COEF:
+            # the previous layer's coefficient kernel and this layer's dW reduction depend on the fused launch only: one launch
+            pc = [torch.empty(cin, dtype=torch.float32, device=b.dev) for _ in range(3)]
+            pg = [_grad_buffer(prev.gamma, b.sunk), _grad_buffer(prev.beta, b.sunk), _grad_buffer(prev.biases, b.sunk)]
+            L.check(lib.gspn_mlp_bwd_fused_coef(rows, cin, cout, ctypes.byref(a), L.ptr(lp.weights), L.ptr(s.x), s.ldx, L.ptr(s.in_scale),
+                                                L.ptr(s.in_shift), L.ptr(dx), cin, L.ptr(work), L.ptr(dW), L.ptr(p.mean), L.ptr(p.var), BN_EPS,
+                                                L.ptr(part), ctypes.byref(npart), L.ptr(prev.gamma), L.ptr(pc[0]), L.ptr(pc[1]), L.ptr(pc[2]),
+                                                L.ptr(pg[0]), L.ptr(pg[1]), L.ptr(pg[2]), b.st), "mlp_bwd_fused_coef")
+            merged = (pc[0], pc[1], pc[2], pg[0], pg[1], pg[2])
+        else:
+            L.check(lib.gspn_mlp_bwd_fused(rows, cin, cout, ctypes.byref(a), L.ptr(lp.weights), L.ptr(s.x), s.ldx, L.ptr(s.in_scale), L.ptr(s.in_shift),
+                                           L.ptr(dx), cin, L.ptr(work), L.ptr(dW), L.ptr(p.mean), L.ptr(p.var), BN_EPS, L.ptr(part),
+                                           ctypes.byref(npart), b.st), "mlp_bwd_fused")
+    except NotImplementedError:
+        if pg is not None:           # the declined launch filled none of the previous layer's sinks: hand them back
+            for prm, buf in zip((prev.gamma, prev.beta, prev.biases), pg):
+                _grad_release(prm, buf, b.sunk)
+        return None
+    _toc(ev, "fused", rows, cin, cout, 4.0 * rows * cin * cout)
+    if merged is not None:
+        b.coef[li - 1] = merged
+    elif want_rsum:
+        b.coef[li - 1] = _coef_from_parts(lib, rows, cin, npart.value, part, p.mean, p.var, prev, b.dev, b.st, b.sw, b.sunk)
+    return dx
+
+
+def _pass_a(b, li, a, known, cf, work, dW):
+    """pass A of layer li: one GEMM where the coefficients are known and the kernels take the shape (returns True), else the two-product form,
+    which writes cf = (cA, cB, cC, dgamma, dbeta, dbias) itself.  dW None: the sum over the partial tiles in `work` is left to a later launch"""
+    lib, rows, ctx, lp, s = b.lib, b.rows, b.ctx, b.layers[li], b.ctx.saved[li]
+    cin, cout = s.cin, lp.weights.shape[1]
+    gargs = ctypes.byref(ctx.gargs) if (li == 0 and ctx.gather is not None) else None
+    ev = _tic()
+    ran_known = False
+    if known is not None:
+        try:
+            L.check(lib.gspn_mlp_bwd_wgrad_known(rows, cin, cout, ctypes.byref(a), L.ptr(s.x), s.ldx, L.ptr(s.in_scale), L.ptr(s.in_shift), gargs, L.ptr(work),
+                                                 L.ptr(dW), b.st), "mlp_bwd_wgrad_known")
+            ran_known = True
+        except NotImplementedError:
+            pass                             # a shape the one-GEMM kernels do not take: the two-product pass recomputes the same coefficients
+    if not ran_known:
+        tail = (L.ptr(s.mean), L.ptr(s.var), L.ptr(lp.gamma if lp.bn else None), BN_EPS, int(lp.bn), int(b.is_training), L.ptr(work),
+                L.ptr(cf[0]), L.ptr(cf[1]), L.ptr(cf[2]), L.ptr(cf[3]), L.ptr(cf[4]), L.ptr(cf[5]))
+        if gargs is not None:
+            L.check(lib.gspn_mlp_bwd_wgrad_gather(rows, gargs, cout, ctypes.byref(a), *tail, L.ptr(dW), b.st), "mlp_bwd_wgrad_gather")
+        else:
+            L.check(lib.gspn_mlp_bwd_wgrad(rows, cin, cout, ctypes.byref(a), L.ptr(s.x), s.ldx, L.ptr(s.in_scale), L.ptr(s.in_shift), *tail,
+                                           L.ptr(dW), b.st), "mlp_bwd_wgrad")
+    _toc(ev, "wgrad", rows, cin, cout, None if ran_known else 2 * 2.0 * rows * cin * cout)      # the two-product form: G1 and Gx
+    return ran_known
+
+
+def _deferred_dw(b, li, a, work, dW):
+    """DEFER_DW: the dW reduction of layer li on the side stream, ordered after its pass A"""
+    lp, s = b.layers[li], b.ctx.saved[li]
+    if b.side is None:
+        b.side = _side_stream(b.dev)
+        b.main = torch.cuda.current_stream()
+    b.side.wait_event(b.main.record_event())            # after this layer's wgrad + channel sums
+    dw = _dw_args(s, lp, int(lp.bn), b.is_training, work, dW)
+    L.check(b.lib.gspn_mlp_bwd_dw(b.rows, s.cin, lp.weights.shape[1], ctypes.byref(a), ctypes.byref(dw), ctypes.c_void_p(b.side.cuda_stream)), "mlp_bwd_dw")
+    b.keep.append((work, a))                            # alive until the side stream has joined
+
+
+def _pass_b_gathered(b, a, gather0):
+    """pass B of a gathered first layer: dX of the feature columns in grouped-row layout, then the gather-form gradient of the grouping
+    (inverse lists; atomics without them) straight into d(features)"""
+    lib, rows, lp, s = b.lib, b.rows, b.layers[0], b.ctx.saved[0]
+    cout = lp.weights.shape[1]
+    gb, gn, gm, gns = gather0["dims"]
+    gc, xf = gather0["c"], int(gather0["xyz_first"])
+    ldp = (3 + gc + 3) // 4 * 4
+    dxg = torch.empty((rows, ldp), dtype=torch.float32, device=b.dev)
+    ev = _tic()
+    L.check(lib.gspn_mlp_bwd_data(rows, s.cin, cout, ctypes.byref(a), L.ptr(lp.weights), 3 if xf else 0, gc, L.ptr(dxg), ldp, None, None, b.st), "mlp_bwd_data")
+    _toc(ev, "bwd", rows, s.cin, cout, 2.0 * rows * gc * cout)
+    gp = torch.empty((gb, gn, gc), dtype=torch.float32, device=b.dev)
+    if gather0.get("order") is not None:
+        L.check(lib.gspn_sa_group_concat_grad_csr(gb, gn, gc, gm, gns, L.ptr(gather0["order"]), L.ptr(gather0["offsets"]), xf, ldp,
+                                                  L.ptr(dxg), L.ptr(gp), b.st), "sa_group_concat_grad_csr")
+    else:
+        L.check(lib.gspn_sa_group_concat_grad(gb, gn, gc, gm, gns, L.ptr(gather0["idx"]), xf, ldp, L.ptr(dxg), L.ptr(gp), b.st), "sa_group_concat_grad")
+    ldf = b.ctx.gargs.ldf
+    dx0 = gp.view(gb * gn, gc)
+    return dx0 if ldf == gc else torch.nn.functional.pad(dx0, (0, ldf - gc))
+
+
+def _pass_b(b, li, a, known, dz, ride):
+    """pass B of layer li -> dX.  ride: the gspn_dw_args of the layer's dW reduction when it rides in this launch, else None.  This dX is
+    the dz of layer li-1: its epilogue can take that layer's BN reductions (early coefficients for its pass A)"""
+    lib, rows, layers, lp, s = b.lib, b.rows, b.layers, b.layers[li], b.ctx.saved[li]
+    cin, cout = s.cin, lp.weights.shape[1]
+    dx = torch.empty((rows, s.ldx if li == 0 else cin), dtype=torch.float32, device=b.dev)
+    if li == 0 and s.ldx > cin and b.spec.get("grad_cols") is None:
+        dx.zero_()
+    # only grad_cols of the input feed a gradient upstream (e.g. not the xyz columns of an SA input)
+    gc = (b.spec.get("grad_cols") if li == 0 else None) or (0, cin)
+    prev = layers[li - 1] if li > 0 else None
+    want_rsum = b.tr_all and prev is not None and prev.bn
+    ev = _tic()
+    p = b.ctx.saved[li - 1] if want_rsum else None
+    rs, part, npart = _rsum_args(b, p, cin) if want_rsum else (None, None, None)
+    top_done = False
+    if (POOLTOP_STREAM and dz is None and b.pool_ns == 32 and want_rsum and ride is not None and known is not None and cin <= 64
+            and cin % 4 == 0 and cout <= 128 and cout % 4 == 0 and tuple(gc) == (0, cin)):
+        scr = torch.empty(int(lib.gspn_pooltop_scratch_floats(rows, cin, cout)), dtype=torch.float32, device=b.dev)
+        try:
+            L.check(lib.gspn_mlp_bwd_data_pooltop(rows, cin, cout, ctypes.byref(a), L.ptr(lp.weights), L.ptr(lp.biases), L.ptr(b.ctx.saved_tensors[0]),
+                                                  L.ptr(scr), L.ptr(dx), dx.shape[1], ctypes.byref(ride), ctypes.byref(rs), b.st), "mlp_bwd_data_pooltop")
+            top_done = True
+        except NotImplementedError:
+            pass
+    if not top_done:
+        L.check(lib.gspn_mlp_bwd_data(rows, cin, cout, ctypes.byref(a), L.ptr(lp.weights), int(gc[0]), int(gc[1]), L.ptr(dx), dx.shape[1],
+                                      _ref(ride), _ref(rs), b.st), "mlp_bwd_data")
+    if want_rsum:
+        b.coef[li - 1] = _coef_from_parts(lib, rows, cin, npart.value, part, p.mean, p.var, prev, b.dev, b.st, b.sw, b.sunk)
+    _toc(ev, "bwd", rows, cin, cout, 2.0 * rows * int(gc[1]) * cout)
+    return dx
 
 
 _consts = {}
@@ -582,10 +598,11 @@ def _preagg_backward(lib, pre, x, lp, a, rows, cout, need_dx, dev, st, sunk=None
     dy = torch.empty((rows, cout), dtype=torch.float32, device=dev)
     part = torch.empty(int(lib.gspn_preagg_part_floats(cout, max(side_n, 1))), dtype=torch.float32, device=dev)
     dws = dW[pre["ws0"]:pre["ws0"] + side_n]
-    ride = need_dx and FUSE_DW               # the reductions of dW_side's and dW_feat's partial tiles ride in the d(feat) launch
+    ride = need_dx and FUSE_DW               # the reductions of dW_side's and dW_feat's partial tiles ride in the d(feat) launch ...
+    dws_now = None if (ride and side_n) else dws         # ... and are then not run by the launches that leave the tiles
     nsl = ctypes.c_int(0)
     L.check(lib.gspn_preagg_bwd_dy(rows, cout, ctypes.byref(a), L.ptr(pre["side"]), pre["side_ld"], side_n, L.ptr(dy), L.ptr(part),
-                                   None if (ride and side_n) else L.ptr(dws), ctypes.byref(nsl), st), "preagg_bwd_dy")
+                                   L.ptr(dws_now), ctypes.byref(nsl), st), "preagg_bwd_dy")
     nsrc = x.shape[0]
     gsrc = pre["scatter"](dy, cout)                                 # (source rows, cout): sum over the output rows each source row fed
     one, zero = _const_vectors(dev, cout)
@@ -595,21 +612,20 @@ def _preagg_backward(lib, pre, x, lp, a, rows, cout, need_dx, dev, st, sunk=None
     a2.scale, a2.shift = zero.data_ptr(), one.data_ptr()           # always-open mask
     a2.cA, a2.cB, a2.cC = one.data_ptr(), zero.data_ptr(), zero.data_ptr()      # known coefficients: dY = dz
     dwf = dW[pre["wf0"]:pre["wf0"] + c]
+    dwf_now = None if ride else dwf
     wf = lp.weights[pre["wf0"]:pre["wf0"] + c]
     work = torch.empty(int(lib.gspn_mlp_bwd_work_bytes(nsrc, c, cout)) // 4 + 4, dtype=torch.float32, device=dev)
     L.check(lib.gspn_mlp_bwd_wgrad_known(nsrc, c, cout, ctypes.byref(a2), L.ptr(x), x.shape[1], None, None, None, L.ptr(work),
-                                         None if ride else L.ptr(dwf), st), "mlp_bwd_wgrad_known(pre-aggregation)")
+                                         L.ptr(dwf_now), st), "mlp_bwd_wgrad_known(pre-aggregation)")
     dx = None
     if need_dx:
         dx = torch.empty((nsrc, x.shape[1]), dtype=torch.float32, device=dev)
         if x.shape[1] > c:
             dx.zero_()
-        if ride:
-            L.check(lib.gspn_mlp_bwd_data_dw2(nsrc, c, cout, ctypes.byref(a2), L.ptr(wf), 0, c, L.ptr(dx), x.shape[1], L.ptr(x), x.shape[1], None, None,
-                                              BN_EPS, 0, 0, L.ptr(work), L.ptr(dwf), L.ptr(part), side_n, nsl.value if side_n else 0, L.ptr(dws), st),
-                    "mlp_bwd_data_dw2(pre-aggregation)")
-        else:
-            L.check(lib.gspn_mlp_bwd_data(nsrc, c, cout, ctypes.byref(a2), L.ptr(wf), L.ptr(dx), x.shape[1], st), "mlp_bwd_data(pre-aggregation)")
+        # riding: dW_feat's reduction, and dW_side's as the second job
+        dw = L.DwArgs(L.ptr(x), x.shape[1], None, None, BN_EPS, 0, 0, L.ptr(work), L.ptr(dwf), L.ptr(part), side_n, nsl.value if side_n else 0,
+                      L.ptr(dws)) if ride else None
+        L.check(lib.gspn_mlp_bwd_data(nsrc, c, cout, ctypes.byref(a2), L.ptr(wf), 0, c, L.ptr(dx), x.shape[1], _ref(dw), None, st), "mlp_bwd_data(pre-aggregation)")
     return dW, dx
 
 
@@ -687,7 +703,7 @@ class _Linear(torch.autograd.Function):
                 dx = torch.empty((rows, ld), dtype=torch.float32, device=dev)
                 if ld > cin:
                     dx.zero_()
-                L.check(lib.gspn_mlp_bwd_data(rows, cin, cout, ctypes.byref(a), L.ptr(w), L.ptr(dx), ld, L.stream()), "mlp_bwd_data")
+                L.check(lib.gspn_mlp_bwd_data(rows, cin, cout, ctypes.byref(a), L.ptr(w), 0, cin, L.ptr(dx), ld, None, None, L.stream()), "mlp_bwd_data")
         return dx, None, dW, dbias
 
 

@@ -48,9 +48,11 @@ extern "C" {
  *  18: gspn_fps_segments (+ _ws_bytes).
  *  19: gspn_scene_confidence / gspn_scene_rank / gspn_sem_iou_counts.
  *  20: gspn_batch_assemble / gspn_adam_tf_flat / gspn_momentum_flat / gspn_scalars_accumulate. */
-/* Additive at 20: gspn_instance_overlaps / gspn_instance_match.  Nothing that was there changed, so the number stays; a binder that wants
- * the two and finds an older library fails at the symbol lookup. */
-#define GSPN_ABI_VERSION 20
+/* Additive at 20: gspn_instance_overlaps / gspn_instance_match.  Nothing that was there changed, so the number stayed; a binder that wants
+ * the two and finds an older library fails at the symbol lookup.
+ *  21: gspn_dw_args / gspn_rsum_args; one gspn_mlp_bwd_data (gspn_mlp_bwd_data_cols / _dw / _dw2 / _ex removed); gspn_mlp_bwd_dw and
+ *      gspn_mlp_bwd_data_pooltop take the two structs. */
+#define GSPN_ABI_VERSION 21
 int gspn_dist_policy(void);
 int gspn_abi_version(void);
 
@@ -537,6 +539,38 @@ typedef struct gspn_dy_args {
     const float* cB;
     const float* cC;
 } gspn_dy_args;
+/* The dW reduction a pass A called with dW = NULL left undone: the final sum over the partial tiles in `work`, as a kernel of its own
+ * (gspn_mlp_bwd_dw) or in spare workgroups of pass B. */
+typedef struct gspn_dw_args {
+    const float* X;        /* the layer's input and its pitch as that pass A got them, so that the workspace layout is found again */
+    int ldx;               /* (in pass B X may be NULL, and only a non-NULL X needs ldx >= cin; gspn_mlp_bwd_dw needs ldx >= cin) */
+    const float* var;      /* cout: the statistics pass A normalised with (required under use_bn) */
+    const float* gamma;    /* cout, or NULL */
+    float eps;
+    int use_bn;            /* as in that pass A; 0 after gspn_mlp_bwd_wgrad_known (the partial tiles are dW's own: a plain sum) */
+    int is_training;
+    const float* work;     /* the gspn_mlp_bwd_work_bytes(rows, cin, cout) buffer pass A filled */
+    float* dW;             /* (cin, cout) */
+    /* a second, plain reduction riding along in gspn_mlp_bwd_data (no other entry point reads these four; cin2 == 0: none): dW2 (cin2, cout) =
+     * the sum of nslots2 partial tiles at part2 ([slot][2][cin2*cout], first half) -- the side-column weight gradient of gspn_preagg_bwd_dy */
+    const float* part2;
+    int cin2;
+    int nslots2;
+    float* dW2;
+} gspn_dw_args;
+/* The previous layer's BN reductions out of pass B's epilogue: this launch's dX is that layer's dz, and the sums r0 = sum(dyh), r1 = sum(dyh*xhat)
+ * it needs for early coefficients (below) are taken from the finished tiles.  Every field is required. */
+typedef struct gspn_rsum_args {
+    const float* Yp;       /* (rows, ldyp >= cin) that layer's pre-BN output = this layer's input before activation */
+    int ldyp;
+    const float* scale;    /* cin each: its forward scale / shift (relu mask) */
+    const float* shift;
+    const float* mean;     /* cin each: its batch statistics */
+    const float* var;
+    float eps;
+    float* part;           /* gspn_rsum_part_floats(rows, cin) floats: partial rows [*nparts_out][2][cin] for gspn_mlp_bwd_coef */
+    int* nparts_out;
+} gspn_rsum_args;
 
 /* Pass A -- ONE read of (X, Y, dz):  the BN reductions r0 = sum(dyh), r1 = sum(dyh*xhat) and the raw
  * weight-gradient products G1 = act(X)^T.dyh, Gx = act(X)^T.xhat, g3 = act(X)^T.1 are accumulated into
@@ -555,47 +589,40 @@ int gspn_mlp_bwd_wgrad(long rows, int cin, int cout, const gspn_dy_args* a, cons
                        float eps, int use_bn, int is_training, float* work, float* cA, float* cB, float* cC,
                        float* dgamma, float* dbeta, float* dbias, float* dW, void* stream);
 long gspn_mlp_bwd_work_bytes(long rows, int cin, int cout);
-int gspn_mlp_bwd_dw(long rows, int cin, int cout, const gspn_dy_args* a, const float* X, int ldx, const float* var, const float* gamma,
-                    float eps, int use_bn, int is_training, const float* work, float* dW, void* stream);
-/* Pass B -- dX(rows,ldx)[:, :cin] = dY . W^T with dY = cA*dyh + cB*y + cC rebuilt on the fly */
-int gspn_mlp_bwd_data(long rows, int cin, int cout, const gspn_dy_args* a, const float* W, float* dX, int ldx, void* stream);
-/* ... restricted to columns [col0, col0+ncols) of dX (the other columns are left untouched): for inputs whose leading or trailing
- * channels need no gradient -- the xyz columns of a set-abstraction input, the raw colours of the last FP level. */
-int gspn_mlp_bwd_data_cols(long rows, int cin, int cout, const gspn_dy_args* a, const float* W, int col0, int ncols, float* dX, int ldx,
-                           void* stream);
-/* gspn_mlp_bwd_data_cols + gspn_mlp_bwd_dw in one launch: the dW reduction that gspn_mlp_bwd_wgrad(..., dW = NULL) left undone runs in
- * spare workgroups of pass B instead of a kernel of its own (X / ldx_in / var / gamma / eps / use_bn / is_training / work as in that
- * call).  dX is bit-identical to gspn_mlp_bwd_data_cols'; dW is the same sum taken over 16 instead of 64 slot slices per output. */
-int gspn_mlp_bwd_data_dw(long rows, int cin, int cout, const gspn_dy_args* a, const float* W, int col0, int ncols, float* dX, int ldx,
-                         const float* X, int ldx_in, const float* var, const float* gamma, float eps, int use_bn, int is_training,
-                         const float* work, float* dW, void* stream);
-/* the same with a second, plain reduction riding along: dW2 (cin2, cout) = the sum of nslots2 partial tiles at part2 ([slot][2][cin2*cout],
- * first half) -- the side-column weight gradient gspn_preagg_bwd_dy leaves behind */
-int gspn_mlp_bwd_data_dw2(long rows, int cin, int cout, const gspn_dy_args* a, const float* W, int col0, int ncols, float* dX, int ldx,
-                          const float* X, int ldx_in, const float* var, const float* gamma, float eps, int use_bn, int is_training,
-                          const float* work, float* dW, const float* part2, int cin2, int nslots2, float* dW2, void* stream);
+int gspn_mlp_bwd_dw(long rows, int cin, int cout, const gspn_dy_args* a, const gspn_dw_args* dw, void* stream);
+/* Pass B -- dX(rows,ldx)[:, col0 : col0+ncols] = dY . W^T with dY = cA*dyh + cB*y + cC rebuilt on the fly (the whole row: col0 = 0,
+ * ncols = cin).  The other columns of dX are left untouched: for inputs whose leading or trailing channels need no gradient -- the xyz
+ * columns of a set-abstraction input, the raw colours of the last FP level.
+ *   dw (NULL: no dW job rides): gspn_mlp_bwd_dw in the same launch, in spare workgroups of pass B instead of a kernel of its own; dW is
+ *       the same sum taken over 16 instead of 64 slot slices per output.
+ *   rs (NULL: no BN reductions): the previous layer's BN reductions from the epilogue.  They need the whole row.
+ * dX is bit-identical in all four forms.  One set of argument checks, run before anything is launched.  GSPN_ERR_ARG: rows < 0, cin or
+ * cout <= 0, ldx < cin, `a` NULL or without Y / scale / shift / cA / cB / cC or an upstream gradient, a column range outside [0, cin);
+ * with dw or rs also rows == 0 (the plain form returns 0 for it: nothing to do); dw without work or dW, with use_bn and no var, with
+ * cin2 > 0 and no part2 / dW2 / nslots2, or with a non-NULL X and ldx < cin (the entry points this one replaces disagreed on a NULL X
+ * with ldx < cin: accepted, as by the one gspn_amd/mlp.py called); rs with a NULL field, ldyp < cin, or anything but the whole row.
+ * GSPN_ERR_UNSUPPORTED: cin or cout > GSPN_MLP_MAX_CHANNELS, rows >= 2^31. */
+int gspn_mlp_bwd_data(long rows, int cin, int cout, const gspn_dy_args* a, const float* W, int col0, int ncols, float* dX, int ldx,
+                      const gspn_dw_args* dw /* NULL: no dW job rides */, const gspn_rsum_args* rs /* NULL: no BN reductions */, void* stream);
 /* Pass B of a POOLED TOP layer (pool groups of 32 rows) as a streaming GEMM on the layer's input: with dY = cA*dyh + cB*y + cC and
  * y = xhat.W + b,   dX = xhat.(W diag(cB) W^T) + S.W^T + const,   S = cA*dyh (one non-zero per pool group and channel) -- the layer's own
  * (rows, cout) output is not read.  a: the layer's gspn_dy_args (dPool, pool_arg, ns = 32, cA/cB/cC); pooled: the (rows/32, cout) pooled
  * output of the forward pass; scratch: gspn_pooltop_scratch_floats(rows, cin, cout) floats.  The layer's dW reduction rides in the small
- * launch that prepares the operands; the previous layer's BN reductions come out of the epilogue (as gspn_mlp_bwd_data_ex: both required).
- * GSPN_ERR_UNSUPPORTED outside cin <= 64, cout <= 128 (multiples of 4), ns = 32, 16-byte aligned rows: call gspn_mlp_bwd_data_ex then. */
+ * launch that prepares the operands; the previous layer's BN reductions come out of the epilogue (dw and rs as gspn_mlp_bwd_data takes
+ * them, both required).
+ * GSPN_ERR_UNSUPPORTED outside cin <= 64, cout <= 128 (multiples of 4), ns = 32, 16-byte aligned rows: call gspn_mlp_bwd_data then. */
 long gspn_pooltop_scratch_floats(long rows, int cin, int cout);
 int gspn_mlp_bwd_data_pooltop(long rows, int cin, int cout, const gspn_dy_args* a, const float* W, const float* bias, const float* pooled,
-                              float* scratch, float* dX, int ldx,
-                              const float* X, int ldx_in, const float* var, const float* gamma, float eps, int use_bn, int is_training,
-                              const float* work, float* dW,
-                              const float* Yp, int ldyp, const float* scale_p, const float* shift_p, const float* mean_p, const float* var_p,
-                              float eps_p, float* part, int* nparts_out, void* stream);
+                              float* scratch, float* dX, int ldx, const gspn_dw_args* dw, const gspn_rsum_args* rs, void* stream);
 
 /* ---- early coefficients: pass A as ONE GEMM ------------------------------------------------------------------------------------
  * Training-mode BN's backward needs r0 = sum(dyh) and r1 = sum(dyh*xhat) over all rows before dY exists; gspn_mlp_bwd_wgrad side-steps
  * that with a second product (Gx) inside the GEMM -- twice the matrix work.  When the two sums are taken BEFORE pass A, the coefficients
  * cA/cB/cC are final and gspn_mlp_bwd_wgrad_known runs one GEMM dW = act(X)^T . dY (g: optional gspn_gather_args of a fused first layer,
- * defined below; dW may be NULL, the sum over partial tiles then rides in gspn_mlp_bwd_data_ex / _dw called with use_bn = 0):
+ * defined below; dW may be NULL, the sum over partial tiles then rides in gspn_mlp_bwd_data / gspn_mlp_bwd_dw called with use_bn = 0):
  *   - top layer of a pooled stack: gspn_pool_rsum takes the sums from (dPool, pool_arg, Y) -- (groups x c) work; ldy == 0 says Y is
  *     already the (groups, c) tensor of y at the arg row (vmax after gspn_pool32_select): no gather from the (rows, c) output;
- *   - any other layer l: its dz is the dX of layer l+1's pass B, whose epilogue takes them (gspn_mlp_bwd_data_ex, Yp = Y of layer l);
+ *   - any other layer l: its dz is the dX of layer l+1's pass B, whose epilogue takes them (gspn_mlp_bwd_data with rs, Yp = Y of layer l);
  *   - gspn_mlp_bwd_coef(rows, c, nparts, part, ...) sums the partial rows [nparts][2][c] in double and writes cA, cB, cC, dgamma, dbeta,
  *     dbias (the same formulas as gspn_mlp_bwd_wgrad's).  part: gspn_rsum_part_floats(rows, c) floats. */
 struct gspn_gather_args;
@@ -610,20 +637,15 @@ int gspn_mlp_bwd_coef(long rows, int c, int nparts, const float* part, const flo
                       float* cA, float* cB, float* cC, float* dgamma, float* dbeta, float* dbias, void* stream);
 int gspn_mlp_bwd_wgrad_known(long rows, int cin, int cout, const gspn_dy_args* a, const float* X, int ldx, const float* in_scale,
                              const float* in_shift, const struct gspn_gather_args* g, float* work, float* dW, void* stream);
-int gspn_mlp_bwd_data_ex(long rows, int cin, int cout, const gspn_dy_args* a, const float* W, int col0, int ncols, float* dX, int ldx,
-                         const float* X, int ldx_in, const float* var, const float* gamma, float eps, int use_bn, int is_training,
-                         const float* work, float* dW,
-                         const float* Yp, int ldyp, const float* scale_p, const float* shift_p, const float* mean_p, const float* var_p,
-                         float eps_p, float* part, int* nparts_out, void* stream);
 /* Pass A and pass B of one layer in ONE launch (r03).  With known coefficients (a->cA/cB/cC final) and either a dense upstream gradient
  * (a->dZ) or the gradient of a max-pool over groups of 32 rows (a->dZ NULL, a->dPool / a->pool_arg, a->ns == 32),
  *     dW (cin, cout)        = relu(Xp*in_scale + in_shift)^T . dY
  *     dX (rows, ldx >= cin) = dY . W^T
  * come from the same staged dY tile.  Xp (rows, ldxp) is the previous layer's raw output, in_scale / in_shift its forward scale / shift.
- * part (optional, with that layer's mean_p / var_p): its BN reductions, exactly what gspn_mlp_bwd_data_ex leaves (*nparts_out rows for
+ * part (optional, with that layer's mean_p / var_p): its BN reductions, exactly what gspn_mlp_bwd_data leaves with rs (*nparts_out rows for
  * gspn_mlp_bwd_coef).  work: the gspn_mlp_bwd_work_bytes(rows, cin, cout) buffer.
  * GSPN_ERR_UNSUPPORTED outside cin in {32, 64}, cout in {32, 64, 128}, rows >= 65536 a multiple of 128, 16-byte aligned pitches
- * (GSPN_BWD_FUSED=0: always): run gspn_mlp_bwd_wgrad_known + gspn_mlp_bwd_data_ex then. */
+ * (GSPN_BWD_FUSED=0: always): run gspn_mlp_bwd_wgrad_known + gspn_mlp_bwd_data then. */
 long gspn_mlp_bwd_fused_work_bytes(long rows, int cin, int cout);
 int gspn_mlp_bwd_fused(long rows, int cin, int cout, const gspn_dy_args* a, const float* W, const float* Xp, int ldxp, const float* in_scale,
                        const float* in_shift, float* dX, int ldx, float* work, float* dW, const float* mean_p, const float* var_p,
@@ -654,7 +676,7 @@ int gspn_preagg_fwd(long rows, int cout, int T, const float* F, const int* idx, 
 long gspn_preagg_part_floats(int cout, int side_n);
 int gspn_preagg_bwd_dy(long rows, int cout, const gspn_dy_args* a, const float* side, int side_ld, int side_n, float* dY, float* part,
                        float* dWside, int* nslots_out, void* stream);
-/* (dWside == NULL: the partial tiles stay at part, *nslots_out of them, for gspn_mlp_bwd_data_dw2 to sum in a launch that exists anyway) */
+/* (dWside == NULL: the partial tiles stay at part, *nslots_out of them, for gspn_mlp_bwd_data to sum as its second job (part2) in a launch that exists anyway) */
 
 /* ---- fused set-abstraction front end: sample_and_group's concat (pointnet_util.py:36-52) + the first conv2d (:109-113)
  * without the grouped (b, npoint, nsample, 3+c) tensor.  gspn_sa_rel writes, per grouped row r = ((i*m + j)*ns + k), its centred
@@ -666,7 +688,7 @@ int gspn_preagg_bwd_dy(long rows, int cout, const gspn_dy_args* a, const float* 
  * gspn_mlp_fwd_gather / gspn_mlp_bwd_wgrad_gather are gspn_mlp_fwd / gspn_mlp_bwd_wgrad for such a first layer (no input activation);
  * they return GSPN_ERR_UNSUPPORTED for shapes the streaming kernels do not take (the caller then materialises the rows with
  * gspn_sa_group_concat).  Workspace of the backward call: gspn_mlp_bwd_work_bytes(rows, gspn_mlp_gather_cin(g), cout).
- * Pass B of that layer is the ordinary gspn_mlp_bwd_data_cols (it does not read the layer's input). */
+ * Pass B of that layer is the ordinary gspn_mlp_bwd_data over the feature columns (it does not read the layer's input). */
 typedef struct gspn_gather_args {
     const float* feat;
     int ldf;

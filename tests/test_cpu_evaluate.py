@@ -18,7 +18,7 @@ def test_the_two_symbols_are_exported_declared_and_bound_at_abi_20():
     build.build()
     text = open(os.path.join(ROOT, "include", "gspn_hip.h")).read()
     lib = _lib.lib()
-    assert int(re.search(r"#define GSPN_ABI_VERSION (\d+)", text).group(1)) == _lib.ABI_VERSION == lib.gspn_abi_version() == 20
+    assert int(re.search(r"#define GSPN_ABI_VERSION (\d+)", text).group(1)) == _lib.ABI_VERSION == lib.gspn_abi_version() >= 20
     assert re.search(r"^/\* Additive at 20: gspn_instance_overlaps / gspn_instance_match\.", text, flags=re.M)
     assert re.search(r"^ \*\s+20: gspn_batch_assemble / gspn_adam_tf_flat / gspn_momentum_flat / gspn_scalars_accumulate\. \*/$", text, flags=re.M)
     code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)

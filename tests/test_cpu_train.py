@@ -26,7 +26,7 @@ def test_abi_20_and_the_train_symbols():
     build.build()
     text = open(os.path.join(ROOT, "include", "gspn_hip.h")).read()
     lib = _lib.lib()
-    assert int(re.search(r"#define GSPN_ABI_VERSION (\d+)", text).group(1)) == _lib.ABI_VERSION == lib.gspn_abi_version() == 20
+    assert int(re.search(r"#define GSPN_ABI_VERSION (\d+)", text).group(1)) == _lib.ABI_VERSION == lib.gspn_abi_version() >= 20
     assert re.search(r"^ \*\s+20: gspn_batch_assemble / gspn_adam_tf_flat / gspn_momentum_flat / gspn_scalars_accumulate", text, flags=re.M)
     code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     handle = ctypes.CDLL(_lib.LIB_PATH)

@@ -275,8 +275,8 @@ def test_fp_module_without_batch_norm(training):
     assert rel_err(t1.grad, p1r.grad) < 1e-4
 
 
-# --------------------------------------------------------------------------------------- g. gspn_mlp_bwd_data_cols alone
-# Which kernel a call of gspn_mlp_bwd_data_cols gets, read off bwd_data_launch, bwd_lean_try and pick_bn (csrc/mlp.hip):
+# --------------------------------------------------------------------------------------- g. gspn_mlp_bwd_data alone, on a column range
+# Which kernel a plain call of gspn_mlp_bwd_data (no dW job, no BN reductions) gets, read off bwd_data_launch, bwd_lean_try and pick_bn (csrc/mlp.hip):
 #   * bwd_lean_kernel takes the launch unless rows % 128, cout % 32, ncols % 32 or col0 % 4 is non-zero (or an operand is not 16-byte aligned);
 #     every case below has cout % 32 != 0 and ncols % 32 != 0, so mlp_bwd_data_kernel<BN, V, P, false> runs (false: no dW job rides along);
 #   * BN = pick_bn(rows, ncols): 32 up to 32 columns; 64 up to 64 columns and 128 beyond, each only while the grid still has 2 * GSPN_PLAN_CUS = 448
@@ -292,7 +292,7 @@ DATA_COLS = [  # (BN, rows, ncols, cout, pooled)
 
 @pytest.mark.parametrize("bn_tile,rows,ncols,cout,pooled", DATA_COLS)
 def test_bwd_data_cols_entry_point_against_float64(bn_tile, rows, ncols, cout, pooled):
-    """gspn_mlp_bwd_data_cols through the C ABI with a hand-built gspn_dy_args and padded pitches: columns [col0, col0 + ncols) of
+    """gspn_mlp_bwd_data (plain form, a column range) through the C ABI with a hand-built gspn_dy_args and padded pitches: columns [col0, col0 + ncols) of
     dX = dY . W^T, dY = cA*[relu open]*dz + cB*y + cC, against float64 on the device at 2e-5 of the largest element; every other column of dX
     keeps what it held.  The seven mlp_bwd_data_kernel<BN, V, P, false> instantiations no stack or module selects (see DATA_COLS)."""
     from gspn_amd import _lib as L
@@ -326,14 +326,101 @@ def test_bwd_data_cols_entry_point_against_float64(bn_tile, rows, ncols, cout, p
         dz = Zb[:, :cout].double()
     assert (Yb.data_ptr() | W.data_ptr()) % 16 == 0
     dXb = torch.full((rows, ldx), 7.0, device=dev)
-    L.check(lib.gspn_mlp_bwd_data_cols(rows, cin, cout, ctypes.byref(a), L.ptr(W), col0, ncols, L.ptr(dXb), ldx, L.stream()), "bwd_data_cols")
+    L.check(lib.gspn_mlp_bwd_data(rows, cin, cout, ctypes.byref(a), L.ptr(W), col0, ncols, L.ptr(dXb), ldx, None, None, L.stream()), "bwd_data")
     torch.cuda.synchronize()
     # the mask with the float32 expression the kernel uses, so that no element sits on the other side of the kink
     dyh = torch.where((Y * scale + shift) > 0, dz, torch.zeros_like(dz))
     dY = cA.double() * dyh + cB.double() * Y.double() + cC.double()
     rdX = dY @ W[col0:col0 + ncols].double().t()
     err = rel_err(dXb[:, col0:col0 + ncols], rdX)
-    print("gspn_mlp_bwd_data_cols %d x [%d, %d) <- %d, tile %d, %s, %s: %.3g" % (rows, col0, col0 + ncols, cout, bn_tile, "vector" if vec else "scalar",
+    print("gspn_mlp_bwd_data %d x [%d, %d) <- %d, tile %d, %s, %s: %.3g" % (rows, col0, col0 + ncols, cout, bn_tile, "vector" if vec else "scalar",
                                                                                 "pooled" if pooled else "dense", err))
     assert err < 2e-5
     assert bool((dXb[:, :col0] == 7.0).all()) and bool((dXb[:, col0 + ncols:] == 7.0).all())
+
+
+# ------------------------------------------------------------------------- h. the four forms of gspn_mlp_bwd_data on one layer
+@pytest.mark.parametrize("pooled", [False, True], ids=["dense", "pooled"])
+def test_bwd_data_four_forms_agree_and_carry_their_jobs(pooled):
+    """One layer 24 -> 20 at 2080 rows (16 full 128-row tiles and one of 32 rows), whole row, padded pitches, after gspn_mlp_bwd_wgrad(dW = NULL)
+    has filled `work`: gspn_mlp_bwd_data plain, with the dW job, with the previous layer's BN reductions, with both.  dX is the same bits in all
+    four (include/gspn_hip.h) and within test g's 2e-5 of float64; dW of the riding job within 2e-5 of float64's largest element (test g's bound,
+    the same GEMM family); the rows of `part`, summed in float64, equal sum(dyh) and sum(dyh * xhat) of the layer below at 1e-5 of the largest
+    element (check_stack_routed's bound on dbeta / dgamma, which these sums are up to gamma * rstd)."""
+    from gspn_amd import _lib as L
+    lib = L.lib()
+    dev = torch.device("cuda", 0)
+    g = torch.Generator(device=dev).manual_seed(2080 + int(pooled))
+    rows, cin, cout, ns, eps = 2080, 24, 20, 32, 1e-3
+    ldx, ldxin, ldy, ldz = cin + 4, cin + 8, cout + 4, cout + 8
+    Xb = torch.randn(rows, ldxin, device=dev, generator=g); X = Xb[:, :cin]            # the layer's input = the pre-BN output of the layer below
+    Yb = torch.randn(rows, ldy, device=dev, generator=g); Y = Yb[:, :cout]
+    W = torch.randn(cin, cout, device=dev, generator=g) * 0.1
+    rnd = lambda n, lo, hi: torch.rand(n, device=dev, generator=g) * (hi - lo) + lo
+    in_scale, in_shift = rnd(cin, 0.5, 1.5), rnd(cin, -0.3, 0.3)
+    mean_p, var_p = X.mean(0).contiguous(), X.var(0, unbiased=False).contiguous()
+    gamma, beta = rnd(cout, 0.5, 1.5), rnd(cout, -0.3, 0.3)
+    mean, var = Y.mean(0).contiguous(), Y.var(0, unbiased=False).contiguous()
+    rstd = 1.0 / torch.sqrt(var.double() + eps)
+    scale = (gamma.double() * rstd).float()
+    shift = (beta.double() - mean.double() * gamma.double() * rstd).float()
+    cA, cB, cC = (torch.empty(cout, device=dev) for _ in range(3))
+    a = L.DyArgs()
+    a.Y, a.ldy = Yb.data_ptr(), ldy
+    a.scale, a.shift, a.cA, a.cB, a.cC = scale.data_ptr(), shift.data_ptr(), cA.data_ptr(), cB.data_ptr(), cC.data_ptr()
+    if pooled:
+        dP = torch.randn(rows // ns, cout, device=dev, generator=g)
+        arg = torch.randint(0, ns, (rows // ns, cout), device=dev, dtype=torch.int32, generator=g)
+        a.dZ, a.ldz, a.dPool, a.pool_arg, a.ns = None, 0, dP.data_ptr(), arg.data_ptr(), ns
+        dz = torch.zeros(rows // ns, ns, cout, device=dev, dtype=torch.float64)
+        dz.scatter_(1, arg.long().unsqueeze(1), dP.double().unsqueeze(1))
+        dz = dz.view(rows, cout)
+    else:
+        Zb = torch.randn(rows, ldz, device=dev, generator=g)
+        a.dZ, a.ldz, a.dPool, a.pool_arg, a.ns = Zb.data_ptr(), ldz, None, None, 0
+        dz = Zb[:, :cout].double()
+    st = L.stream()
+    work = torch.empty(int(lib.gspn_mlp_bwd_work_bytes(rows, cin, cout)) // 4 + 4, device=dev)
+    L.check(lib.gspn_mlp_bwd_wgrad(rows, cin, cout, ctypes.byref(a), L.ptr(Xb), ldxin, L.ptr(in_scale), L.ptr(in_shift), L.ptr(mean), L.ptr(var), L.ptr(gamma),
+                                   eps, 1, 1, L.ptr(work), L.ptr(cA), L.ptr(cB), L.ptr(cC), None, None, None, None, st), "bwd_wgrad")
+    dX, dW, part, npart = {}, {}, {}, {}
+    for form in ("plain", "dw", "rs", "both"):
+        dX[form] = torch.full((rows, ldx), 7.0, device=dev)
+        dw = rs = None
+        if form in ("dw", "both"):
+            dW[form] = torch.full((cin, cout), 7.0, device=dev)
+            dw = L.DwArgs(L.ptr(Xb), ldxin, L.ptr(var), L.ptr(gamma), eps, 1, 1, L.ptr(work), L.ptr(dW[form]))
+        if form in ("rs", "both"):
+            part[form] = torch.zeros(int(lib.gspn_rsum_part_floats(rows, cin)), device=dev)
+            npart[form] = ctypes.c_int(0)
+            rs = L.RsumArgs(L.ptr(Xb), ldxin, L.ptr(in_scale), L.ptr(in_shift), L.ptr(mean_p), L.ptr(var_p), eps, L.ptr(part[form]), ctypes.pointer(npart[form]))
+        L.check(lib.gspn_mlp_bwd_data(rows, cin, cout, ctypes.byref(a), L.ptr(W), 0, cin, L.ptr(dX[form]), ldx, ctypes.byref(dw) if dw is not None else None,
+                                      ctypes.byref(rs) if rs is not None else None, st), "bwd_data(%s)" % form)
+    torch.cuda.synchronize()
+    for form in ("dw", "rs", "both"):
+        assert torch.equal(dX[form], dX["plain"]), form
+    assert bool((dX["plain"][:, cin:] == 7.0).all())
+    # float64, the masks with the float32 expressions the kernels use (no element on the other side of a kink)
+    dyh = torch.where((Y * scale + shift) > 0, dz, torch.zeros_like(dz))
+    rdX = (cA.double() * dyh + cB.double() * Y.double() + cC.double()) @ W.double().t()
+    err = rel_err(dX["plain"][:, :cin], rdX)
+    open_p = (X * in_scale + in_shift) > 0
+    act = torch.where(open_p, X.double() * in_scale.double() + in_shift.double(), torch.zeros_like(rdX))
+    xhat = (Y.double() - mean.double()) * rstd
+    r0, r1 = dyh.sum(0), (dyh * xhat).sum(0)
+    rdW = (gamma.double() * rstd) * (act.t() @ dyh - act.sum(0)[:, None] * (r0 / rows) - (act.t() @ xhat) * (r1 / rows))
+    dyh_p = torch.where(open_p, rdX, torch.zeros_like(rdX))
+    xhat_p = (X.double() - mean_p.double()) / torch.sqrt(var_p.double() + eps)
+    rsum = torch.stack([dyh_p.sum(0), (dyh_p * xhat_p).sum(0)])
+    errs_w = {f: rel_err(dW[f], rdW) for f in dW}
+    errs_p = {}
+    for f in part:
+        n = npart[f].value
+        assert 0 < n and n * 2 * cin <= part[f].numel()
+        got = part[f][:n * 2 * cin].view(n, 2, cin).double().sum(0)
+        errs_p[f] = (rel_err(got[0], rsum[0]), rel_err(got[1], rsum[1]))
+    print("gspn_mlp_bwd_data four forms, %s: dX %.3g; dW %s; part %s (%s rows)" % ("pooled" if pooled else "dense", err, errs_w, errs_p,
+                                                                                   {f: npart[f].value for f in npart}))
+    assert err < 2e-5
+    assert all(e < 2e-5 for e in errs_w.values())
+    assert all(e0 < 1e-5 and e1 < 1e-5 for e0, e1 in errs_p.values())

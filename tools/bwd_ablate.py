@@ -1,4 +1,4 @@
-"""pass B kernel alone (gspn_mlp_bwd_data_ex: dX = dY.W^T with dY rebuilt from (dz, Y) or the pool arg-max, the previous layer's BN reductions in
+"""pass B kernel alone (gspn_mlp_bwd_data with a gspn_rsum_args: dX = dY.W^T with dY rebuilt from (dz, Y) or the pool arg-max, the previous layer's BN reductions in
 the epilogue) at the bench's layer shapes: microseconds, TB/s of algorithmic bytes, TFLOP/s (library chosen by GSPN_HIP_LIB)"""
 import ctypes, os, sys, torch
 sys.path.insert(0, __import__('os').path.dirname(__import__('os').path.dirname(__import__('os').path.abspath(__file__))))
@@ -24,8 +24,8 @@ def run(rows, cin, cout, ns, reps=10):
     a.scale, a.shift, a.cA, a.cB, a.cC = sc.data_ptr(), sh.data_ptr(), cA.data_ptr(), cB.data_ptr(), cC.data_ptr()
     psc, psh, pm, pv = one(cin), one(cin, 0.1), one(cin, 0.0), one(cin)
     part = torch.empty(int(lib.gspn_rsum_part_floats(rows, cin)), device=dev); npart = ctypes.c_int(0)
-    f = lambda: L.check(lib.gspn_mlp_bwd_data_ex(rows, cin, cout, ctypes.byref(a), L.ptr(W), 0, cin, L.ptr(dX), cin, None, 0, None, None, 1e-3, 0, 1, None, None,
-                                                 L.ptr(Yp), cin, L.ptr(psc), L.ptr(psh), L.ptr(pm), L.ptr(pv), 1e-3, L.ptr(part), ctypes.byref(npart), L.stream()), "bwd")
+    rs = L.RsumArgs(L.ptr(Yp), cin, L.ptr(psc), L.ptr(psh), L.ptr(pm), L.ptr(pv), 1e-3, L.ptr(part), ctypes.pointer(npart))
+    f = lambda: L.check(lib.gspn_mlp_bwd_data(rows, cin, cout, ctypes.byref(a), L.ptr(W), 0, cin, L.ptr(dX), cin, None, ctypes.byref(rs), L.stream()), "bwd")
     for _ in range(3): f()
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g):

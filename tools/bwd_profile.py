@@ -14,9 +14,9 @@ for rows, cin, cout in [(262144, 64, 64), (131072, 64, 64), (32768, 128, 128), (
     a.scale, a.shift, a.cA, a.cB, a.cC = sc.data_ptr(), sh.data_ptr(), cA.data_ptr(), cB.data_ptr(), cC.data_ptr()
     psc, psh, pm, pv = one(cin), one(cin, 0.1), one(cin, 0.0), one(cin)
     part = torch.zeros(int(lib.gspn_rsum_part_floats(rows, cin)), device=dev); npart = ctypes.c_int(0)
+    rs = L.RsumArgs(L.ptr(Yp), cin, L.ptr(psc), L.ptr(psh), L.ptr(pm), L.ptr(pv), 1e-3, L.ptr(part), ctypes.pointer(npart))
     for _ in range(3):
-        L.check(lib.gspn_mlp_bwd_data_ex(rows, cin, cout, ctypes.byref(a), L.ptr(W), 0, cin, L.ptr(dX), cin, None, 0, None, None, 1e-3, 0, 1, None, None,
-                                         L.ptr(Yp), cin, L.ptr(psc), L.ptr(psh), L.ptr(pm), L.ptr(pv), 1e-3, L.ptr(part), ctypes.byref(npart), L.stream()), "bwd")
+        L.check(lib.gspn_mlp_bwd_data(rows, cin, cout, ctypes.byref(a), L.ptr(W), 0, cin, L.ptr(dX), cin, None, ctypes.byref(rs), L.stream()), "bwd")
     torch.cuda.synchronize()
     n = min(npart.value, 64)
     v = part[512 * 2 * cin:].view(torch.int64)[:64 * 4 * 8].view(64, 4, 8)[:n].double()

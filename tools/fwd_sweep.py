@@ -28,7 +28,7 @@ for name, rows, ldx, cin, cout in shapes:
     a.scale, a.shift = sc.data_ptr(), sh.data_ptr(); a.cA, a.cB, a.cC = cA.data_ptr(), cB.data_ptr(), cC.data_ptr()
     dX = torch.empty(rows, ldx, device=dev)
     def bwd():
-        return lib.gspn_mlp_bwd_data(rows, cin, cout, ctypes.byref(a), L.ptr(W), L.ptr(dX), ldx, st)
+        return lib.gspn_mlp_bwd_data(rows, cin, cout, ctypes.byref(a), L.ptr(W), 0, cin, L.ptr(dX), ldx, None, None, st)
     out = []
     for env, fn, ref_t in (("GSPN_FWD_FORCE_BN", fwd, Y), ("GSPN_BWD_FORCE_BN", bwd, dX)):
         os.environ.pop(env, None)

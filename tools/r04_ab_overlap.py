@@ -46,7 +46,7 @@ for (rows, cin, cout) in ((4096, 384, 256), (16384, 192, 128), (32768, 128, 128)
         L.check(lib.gspn_mlp_bwd_wgrad_known(rows, cin, cout, ctypes.byref(a), L.ptr(X), cin, L.ptr(vec[5]), L.ptr(vec[6]), None, L.ptr(work), None, L.stream()), "A")
 
     def passB():
-        L.check(lib.gspn_mlp_bwd_data_cols(rows, cin, cout, ctypes.byref(a), L.ptr(W), 0, cin, L.ptr(dX), cin, L.stream()), "B")
+        L.check(lib.gspn_mlp_bwd_data(rows, cin, cout, ctypes.byref(a), L.ptr(W), 0, cin, L.ptr(dX), cin, None, None, L.stream()), "B")
 
     try:
         gA, gB = graph_of(passA, s1), graph_of(passB, s2)

@@ -153,6 +153,7 @@ SIGNATURES = {
     "gspn_scalars_accumulate": [_I, _P, _P, _P, _P],
     "gspn_instance_overlaps": [_I, _I, _I, _I, _I] + [_P] * 8 + [_P],
     "gspn_instance_match": [_I, _I, _I, _I, _I, _I] + [_P] * 13 + [_P],
+    "gspn_segment_labels": [_I, _I, _I] + [_P] * 6 + [_P],
 }
 
 # entry points that do not return an int status: symbol -> (argtypes, restype)
@@ -181,6 +182,7 @@ SPECIAL = {
     "gspn_crop_linear_part_floats": ([_I, _I, _I, _I], _L),
     "gspn_tile_sum_part_floats": ([_L, _I, _I], _L),
     "gspn_fps_segments_ws_bytes": ([_I, _I, _I], _L),
+    "gspn_segment_labels_ws_bytes": ([_I], _L),
 }
 
 ABI_VERSION = 21       # == GSPN_ABI_VERSION of include/gspn_hip.h this binding was written against

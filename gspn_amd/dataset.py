@@ -10,8 +10,9 @@ group_indicator -- without its per-instance session.run loop.
 The reference compacts curpc[curgroup == j] on the host and runs its FPS kernel once per instance at b = 1; here the compaction is the
 stable partition of gspn_inverse_lists and the picks are those of that kernel on each compacted instance (ties on the compacted position).
 Where the reference draws with np.random (the duplicates of :101, :117) the stream is gspn_roi_rand32 (include/gspn_hip.h) read from a
-one-element int64 device tensor, as in roi.py: a captured call draws afresh once the caller has added to that tensor.  Reading PLY / txt
-files and the .npz cache (:28-36, 57-63, 125) stay outside this library.  No CPU fallback for the kernel-backed ops."""
+one-element int64 device tensor, as in roi.py: a captured call draws afresh once the caller has added to that tensor.  Reading the PLY / txt
+files (:28-36, 57-63) and composing these functions into the cache of :38-125 is gspn_amd/data_prep.py (build_cache) over
+gspn_amd/io_util.py.  No CPU fallback for the kernel-backed ops."""
 import math
 
 import torch

@@ -52,6 +52,8 @@ extern "C" {
  * the two and finds an older library fails at the symbol lookup.
  *  21: gspn_dw_args / gspn_rsum_args; one gspn_mlp_bwd_data (gspn_mlp_bwd_data_cols / _dw / _dw2 / _ex removed); gspn_mlp_bwd_dw and
  *      gspn_mlp_bwd_data_pooltop take the two structs. */
+/* Additive at 21: gspn_segment_labels (+ _ws_bytes).  Nothing that was there changed, so the number stayed; a binder that wants the two and
+ * finds an older library fails at the symbol lookup. */
 #define GSPN_ABI_VERSION 21
 int gspn_dist_policy(void);
 int gspn_abi_version(void);
@@ -777,6 +779,26 @@ int gspn_instance_overlaps(int b, int r, int n, int c, int g, const unsigned cha
 int gspn_instance_match(int b, int r, int c, int g, int t, int min_region, const int* inter, const int* void_count, const int* pred_count,
                         const int* pred_class, const float* confidence, const int* count, const int* gt_count, const double* thresholds,
                         int* n_true, int* n_false, int* hard_fn, int* n_gt, int* n_pred, void* stream);
+
+/* ---------------- data_prep.py: segments to instance labels (gspn_amd/csrc/data_prep.hip, additive at ABI 21) ------------ */
+
+/* collect_label's double loop (data_prep.py:25-40) as a table and a gather.  seg_indices (n,) i32: the segment of every vertex;
+ * pair_segment, pair_object (p,) i32: the (segment, objectId) pairs of segGroups flattened in file order, group by group and segment by
+ * segment; s: one more than the largest segment id of seg_indices.
+ *   out_label[v]   = the objectId of the LAST pair whose segment is seg_indices[v], or -1 when there is none          (n,) i32
+ *   *out_conflicts = the number of times the reference prints Error!: the sum, over the segments that have a vertex, of (pairs naming the
+ *                    segment - 1), a repeat inside one group included                                                  one i32
+ * A pair whose segment no vertex has -- one that is negative or >= s included -- does nothing and is no conflict.  A vertex whose entry is
+ * negative or >= s gets -1.  p == 0 is legal (every label -1; the two pair pointers must still be non-null).  Integer max and sums only:
+ * the same result in any thread order.  ws: gspn_segment_labels_ws_bytes(s) bytes (three words per segment), 4-byte aligned; the call
+ * initialises it.  No array needs more than its element's alignment.  GSPN_ERR_ARG for a null pointer, n < 1, s < 1 or p < 0;
+ * GSPN_ERR_UNSUPPORTED for n > GSPN_SEGMENT_LABELS_MAX_N or s > GSPN_SEGMENT_LABELS_MAX_S, all before anything is launched.  No host
+ * synchronisation and static shapes: the call captures in a graph. */
+#define GSPN_SEGMENT_LABELS_MAX_N (1 << 24)
+#define GSPN_SEGMENT_LABELS_MAX_S (1 << 26)
+int gspn_segment_labels(int n, int p, int s, const int* seg_indices, const int* pair_segment, const int* pair_object, void* ws, int* out_label,
+                        int* out_conflicts, void* stream);
+long gspn_segment_labels_ws_bytes(int s);
 
 /* ---------------- train.py: the per-step batch, the reference's optimisers, the running loss sums (gspn_amd/csrc/train.hip, ABI 20) -------
  *

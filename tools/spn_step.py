@@ -40,6 +40,10 @@
             groups, 19 categories, the benchmark's 10 thresholds: instance_overlaps against the same counts written in torch on the device
             (masks.float() against a one-hot of seg * G + group), each alone and in front of instance_match, alternating in one process,
             and the two kernels replayed from a captured graph; whether the counts are equal
+  data_prep the two computations of data_prep.py (gspn_amd/data_prep.py) at the reference's sizes, whatever --shapes says: segment_labels on
+            150000 vertices against the reference's host loop (wall clock), and downsample_scans at batch 1, 2, 4, 8 over eight synthetic
+            scans of 100000-200000 points down to 30000 against eight single farthest_point_sample calls, alternating in one process;
+            whether the labels and the picks are equal
 
 Prints one JSON line per (shape, measurement): median / min milliseconds over --iters timed runs after --warmup runs.
     python tools/spn_step.py --shapes 2x18000,8x32768
@@ -53,6 +57,7 @@ Prints one JSON line per (shape, measurement): median / min milliseconds over --
     python tools/spn_step.py --shapes 2x18000 --measures predict --iters 30
     python tools/spn_step.py --shapes 2x18000,8x32768 --measures train --iters 20
     python tools/spn_step.py --shapes 2x18000 --measures evaluate --iters 30
+    python tools/spn_step.py --shapes 1x150000 --measures data_prep --iters 9
 """
 import argparse
 import json
@@ -765,6 +770,76 @@ def measure_train(a, shape, b, n, dev):
                          for k, v in ts.items()}}), flush=True)
 
 
+DATA_PREP_SCANS = 8
+DATA_PREP_NSAMPLE = 30000           # data_prep.py:65
+
+
+def measure_data_prep(a, shape, b, n, dev):
+    """data_prep.py's two computations (gspn_amd/data_prep.py); the shape is not used: the inputs have the reference's sizes.
+    segment_labels at one scan-sized input (150000 vertices, 3000 segments, 40 groups) against the reference's host loop restated in numpy
+    (wall clock, it runs on the host), and downsample_scans at batch 1, 2, 4, 8 over eight synthetic scans of 100000-200000 points against
+    eight single farthest_point_sample calls with their gathers -- the form the library offered before -- alternating in one process."""
+    import time
+    from gspn_amd import data_prep
+    rng = np.random.default_rng(17)
+    nv, nseg, ngroup = 150000, 3000, 40
+    seg = rng.integers(0, nseg, nv)
+    owner = rng.integers(0, ngroup + 4, nseg)                                     # >= ngroup: in no group
+    groups = [(g, np.nonzero(owner == g)[0]) for g in range(ngroup)]
+
+    def host_loop():
+        out = np.zeros(seg.shape) - 1
+        errors = 0
+        for object_id, segments in groups:
+            for segment in segments:
+                at = np.where(seg == segment)
+                if not all(out[at] == -1):
+                    errors += 1
+                out[at] = object_id
+        return out.astype(np.int64), errors
+
+    host_ms = []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        want, errors = host_loop()
+        host_ms.append((time.perf_counter() - t0) * 1e3)
+    d_seg = torch.from_numpy(seg.astype(np.int32)).to(dev)
+    d_ps = torch.from_numpy(np.concatenate([s for _, s in groups]).astype(np.int32)).to(dev)
+    d_po = torch.from_numpy(np.concatenate([np.full(len(s), g) for g, s in groups]).astype(np.int32)).to(dev)
+    label, conflicts = data_prep.segment_labels(d_seg, d_ps, d_po, nseg)
+    labels_equal = bool(np.array_equal(label.cpu().numpy(), want)) and int(conflicts.item()) == errors
+    res = timed_alternating({"segment_labels": lambda: data_prep.segment_labels(d_seg, d_ps, d_po, nseg)}, a.warmup, a.iters)
+    res["host_loop"] = {"median_ms": round(sorted(host_ms)[1], 2), "min_ms": round(min(host_ms), 2), "max_ms": round(max(host_ms), 2)}
+
+    sizes = [100000 + (100000 * i) // (DATA_PREP_SCANS - 1) for i in range(DATA_PREP_SCANS)]
+    order = np.random.default_rng(3).permutation(DATA_PREP_SCANS)                  # the caller's order is not the order of size
+    scans = []
+    for i in order:
+        xyz = synth.cloud_d(sizes[i], 50 + int(i)) * np.array([8.0, 6.0, 3.0], np.float32)          # a metre-scale room
+        r = np.random.default_rng(60 + int(i))
+        scans.append(tuple(torch.from_numpy(v).to(dev) for v in (xyz, r.integers(0, 256, (sizes[i], 3)).astype(np.uint8),
+                                                                  r.integers(0, 40, sizes[i]).astype(np.int32), r.integers(-1, 30, sizes[i]).astype(np.int32))))
+
+    def single_calls():
+        out = []
+        for scan in scans:
+            pick = farthest_point_sample(DATA_PREP_NSAMPLE, scan[0][None])[0].long()
+            out.append(tuple(t[pick] for t in scan))
+        return out
+
+    base = single_calls()
+    torch.cuda.synchronize()
+    fns, same = {"eight_single_calls": single_calls}, {}
+    for batch in (1, 2, 4, 8):
+        got = data_prep.downsample_scans(scans, DATA_PREP_NSAMPLE, batch)
+        same["batch_%d" % batch] = all(bool(torch.equal(x, y)) for p, q in zip(base, got) for x, y in zip(p, q))
+        fns["downsample_scans_batch_%d" % batch] = (lambda k: lambda: data_prep.downsample_scans(scans, DATA_PREP_NSAMPLE, k))(batch)
+    res.update(timed_alternating(fns, a.warmup, a.iters))
+    print(json.dumps({"measure": "data_prep", "vertices": nv, "segments": nseg, "pairs": int(d_ps.shape[0]), "conflicts": errors,
+                      "labels_equal_the_host_loop": labels_equal, "scan_sizes": [sizes[i] for i in order], "nsample": DATA_PREP_NSAMPLE,
+                      "picks_equal_the_single_calls": same, "iters": a.iters, **res}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points-per-instance", type=int, default=512)  # npoint_ins of --measures dataset (dataset.py:14)
@@ -804,6 +879,8 @@ def main():
             measure_train(a, shape, b, n, dev)
         if "evaluate" in measures:
             measure_evaluate(a, shape, b, n, dev)
+        if "data_prep" in measures:
+            measure_data_prep(a, shape, b, n, dev)
         if not set(measures) & {"step", "full_fwd", "nn"}:
             continue
         xyz = torch.from_numpy(synth.batch(a.kind, b, n)).to(dev)

@@ -1,12 +1,17 @@
 """The reference's train.py on this library: its flags (train.py:18-38), gspn_amd.train.Trainer underneath.
 
-The reference reads ScanNet meshes and labels and builds an .npz cache (dataset.py:28-125); here the cache is handed over ready:
+The reference reads ScanNet meshes and labels and builds an .npz cache (dataset.py:28-125); here the cache is a file of its own, made
+from a ScanNet download by tools/data_prep.py and then tools/make_cache.py:
   --cache FILE       a torch.save'd dict of the six cache tensors of gspn_amd.train.DeviceDataset -- pc, color (S, N, 3) float32,
-                     group_label, seg_label (S, N) int, pc_ins (S, G, M, 3) float32, ngroup (S,) int -- built with gspn_amd.dataset
-                     (sections N and O); --val_cache FILE likewise (default: the last tenth of --cache, at least one batch)
+                     group_label, seg_label (S, N) int, pc_ins (S, G, M, 3) float32, ngroup (S,) int -- as tools/make_cache.py writes it
+                     (gspn_amd.data_prep.build_cache over gspn_amd.dataset; INTEGRATION.md, sections N, O and Q); --val_cache FILE likewise
+                     (default: the last tenth of --cache, at least one batch)
   --synthetic S      S scenes from gspn_amd.synth.spn_batch instead, the last tenth (at least one batch) held out for evaluation
 
     python tools/train.py --synthetic 8 --num_point 4096 --num_sample 64 --num_category 9 --max_epoch 2 --log_dir /tmp/log
+    python tools/data_prep.py ./data/scannet ./data/scannet_preprocessed
+    python tools/make_cache.py --mesh_path ./data/scannet_preprocessed/mesh/scans --label_path ./data/scannet_preprocessed/label/scans \\
+        --list train.txt --out train.pt
     python tools/train.py --cache train.pt --val_cache val.pt --log_dir log_spn
     python tools/train.py --cache train.pt --val_cache val.pt --train_module RPOINTNET --restore_model_path log_spn/model.ckpt \\
         --restore_scope shape_proposal_net --log_dir log_heads

@@ -112,16 +112,12 @@ static inline hipError_t gspn_dyn_lds_optin(int bytes) {
 }
 
 // Straggler experiment: a geometry kernel that leaves part of its CU's 160 KiB of LDS free lets a workgroup of the
-// layers' persistent grids land on that CU, where it shares the SIMDs with the geometry waves and finishes last.  GSPN_GEOM_CLAIM_LDS is a
-// bit mask (1 = fps_cell_kernel, 2 = fps_small_kernel, 4 = csr_build_lds_kernel, 8 = fps_resident_kernel) of kernels that then ask for
-// the whole CU's LDS.  Read once.  Returns the dynamic LDS size to launch with (>= dyn), or dyn if the bit is not set / on any error.
+// layers' persistent grids land on that CU, where it shares the SIMDs with the geometry waves and finishes last.  GSPN_GEOM_CLAIM_LDS_DEFAULT
+// (a build-time constant) is a bit mask (1 = fps_cell_kernel, 2 = fps_small_kernel, 4 = csr_build_lds_kernel, 8 = fps_resident_kernel) of kernels
+// that then ask for the whole CU's LDS.  Returns the dynamic LDS size to launch with (>= dyn), or dyn if the bit is not set / on any error.
 #include <stdlib.h>
-static inline int gspn_claim_lds_mask() {
-    static const int v = getenv("GSPN_GEOM_CLAIM_LDS") ? atoi(getenv("GSPN_GEOM_CLAIM_LDS")) : GSPN_GEOM_CLAIM_LDS_DEFAULT;
-    return v;
-}
 static inline size_t gspn_claim_lds(int bit, const void* fn, size_t dyn) {
-    if (!(gspn_claim_lds_mask() & bit)) return dyn;
+    if (!(GSPN_GEOM_CLAIM_LDS_DEFAULT & bit)) return dyn;
     hipFuncAttributes a;
     if (hipFuncGetAttributes(&a, fn) != hipSuccess) return dyn;
     const size_t full = (size_t)160 * 1024;

@@ -187,14 +187,11 @@ __global__ __launch_bounds__(256) void csr_gather16_kernel(int nt, int L, long s
 // then takes the wave-per-target kernel)
 static int csr_gather16(bool weighted, int b, int nt, int L, long src_rows_per_scene, int c, int ld, int col0, const float* src, const int* order,
                         const int* offsets, const float* weight, float* out, const CsrCopy& cp, hipStream_t st, int split_t = 0) {
-    static const bool off = getenv("GSPN_CSR_GATHER16") && atoi(getenv("GSPN_CSR_GATHER16")) == 0;      // comparison switch, read once
-    if (off) return GSPN_ERR_UNSUPPORTED;
     if (c != 64 && c != 128 && c != 256) return GSPN_ERR_UNSUPPORTED;
     if ((ld & 3) || (col0 & 3) || ((uintptr_t)src % 16) || ((uintptr_t)out % 16)) return GSPN_ERR_UNSUPPORTED;
     if (src_rows_per_scene * (long)ld * 4 >= (1L << 31)) return GSPN_ERR_UNSUPPORTED;
     const long ntot = (long)b * nt;
-    static const int wide = getenv("GSPN_CSR_WIDE") ? atoi(getenv("GSPN_CSR_WIDE")) : 0;      // (A/B hook: 1 = one 16-lane row per target whatever its width)
-    const int chunks = (!wide && c == 128) ? 2 : 1;              // measured (tools/r04_gather_family.py): 128 channels as two rows 13.5 -> 9.0 us; 256 as four 7.8 -> 9.7
+    const int chunks = c == 128 ? 2 : 1;                         // measured (tools/r04_gather_family.py): 128 channels as two rows 13.5 -> 9.0 us; 256 as four 7.8 -> 9.7
     const long part = ((ntot * chunks + 7) / 8 + 15) / 16 * 16;   // work items per XCD slice, whole workgroups
     const long gb = 8 * (part / 16);
     long cb = 0;
@@ -206,13 +203,13 @@ static int csr_gather16(bool weighted, int b, int nt, int L, long src_rows_per_s
     const dim3 grid((unsigned)(gb + cb));
     const long ssf = src_rows_per_scene * (long)ld;
 #define CSR_GO(CPL_, W_) hipLaunchKernelGGL((csr_gather16_kernel<CPL_, W_>), grid, dim3(256), 0, st, nt, L, ssf, ld, col0, src, order, offsets, weight, out, ntot, part, (unsigned)gb, cp, chunks)
-    if (split_t > 0 && (c == 64 || chunks > 1)) {                // long lists shared out inside the workgroup (callers without a pinned summation order)
-        if (weighted) hipLaunchKernelGGL((csr_gather16_kernel<1, true, true>), grid, dim3(256), 0, st, nt, L, ssf, ld, col0, src, order, offsets, weight, out, ntot, part, (unsigned)gb, cp, chunks, split_t);
-        else hipLaunchKernelGGL((csr_gather16_kernel<1, false, true>), grid, dim3(256), 0, st, nt, L, ssf, ld, col0, src, order, offsets, weight, out, ntot, part, (unsigned)gb, cp, chunks, split_t);
+    // (64 and 128 channels: one float4 per lane, CPL = 1 -- 128 as two 16-lane rows; 256: CPL = 4)
+    if (weighted && split_t > 0 && c != 256) {                   // long lists shared out inside the workgroup (weighted callers without a pinned summation order)
+        hipLaunchKernelGGL((csr_gather16_kernel<1, true, true>), grid, dim3(256), 0, st, nt, L, ssf, ld, col0, src, order, offsets, weight, out, ntot, part, (unsigned)gb, cp, chunks, split_t);
         return gspn_launch_status();
     }
-    if (weighted) { if (c == 64 || chunks > 1) CSR_GO(1, true); else if (c == 128) CSR_GO(2, true); else CSR_GO(4, true); }
-    else { if (c == 64 || chunks > 1) CSR_GO(1, false); else if (c == 128) CSR_GO(2, false); else CSR_GO(4, false); }
+    if (weighted) { if (c != 256) CSR_GO(1, true); else CSR_GO(4, true); }
+    else { if (c != 256) CSR_GO(1, false); else CSR_GO(4, false); }
 #undef CSR_GO
     return gspn_launch_status();
 }

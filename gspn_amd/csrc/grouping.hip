@@ -849,7 +849,7 @@ __global__ void csr_fill_kernel(long total, int L, int n, const int* __restrict_
     }
 }
 // count + scan + fill of ONE scene in one workgroup, the histogram and the cursors in LDS (n <= CSR_LDS_MAX_N): no global atomics, one
-// launch instead of a memset and three kernels (the default; GSPN_CSR_GLOBAL=1 selects the kernels above for comparison).  Beside the
+// launch instead of a memset and three kernels (the kernels above take the clouds beyond that; the A/B between the two forms is closed).  Beside the
 // captured layers both forms cost about the same (0.07 ms per step for the five lists of a batch, whatever the grid size).
 #define CSR_LDS_MAX_N 32768
 __global__ __launch_bounds__(1024) void csr_build_lds_kernel(int L, int n, const int* __restrict__ idx, int* __restrict__ offsets, int* __restrict__ tmp) {
@@ -969,9 +969,7 @@ __global__ __launch_bounds__(1024) void csr_slice_fill_kernel(int L, int n, int 
 }
 // slices per scene of the spread-out build: about 4096 positions each, at most 32, and the G x n histogram no larger than 2 L ints; 1 = the one-workgroup kernel
 static inline int csr_slices(int L, int n) {
-    static const int on = getenv("GSPN_CSR_SLICES") ? atoi(getenv("GSPN_CSR_SLICES")) : -1;      // tuning hook: 0 / 1 = off, k > 1 = force k
-    if (on == 0 || on == 1) return 1;
-    long G = on > 1 ? on : L / 4096;
+    long G = L / 4096;
     if (G > 32) G = 32;
     while (G > 1 && G * (long)n > 2L * L) --G;
     return G < 8 ? 1 : (int)G;                   // (a few slices do not pay for the two extra launches: measured 24.9 -> 24.0 us with 4 at SA level 2, 108 -> 122 at SA level 1 where n = 32768)
@@ -1070,8 +1068,7 @@ extern "C" int gspn_inverse_lists(int b, int L, int n, const int* idx, int* work
     if (!idx || !work || !order || !offsets) return GSPN_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     const long total = (long)b * L;
-    static const bool global_atomics = getenv("GSPN_CSR_GLOBAL") != nullptr;          // comparison switch, read once
-    if (n <= CSR_LDS_MAX_N && !global_atomics) {
+    if (n <= CSR_LDS_MAX_N) {
         int* tmp = work + (size_t)b * n;
         const long nwaves = (long)b * n;
         if ((nwaves + 3) / 4 > 0x7FFFFFFFl) return GSPN_ERR_UNSUPPORTED;

@@ -27,7 +27,7 @@ __global__ __launch_bounds__(NN_BLOCK) void three_nn_kernel(int b, int n, int m,
                                                             float* __restrict__ dist, int* __restrict__ idx, const int* __restrict__ order, unsigned nblocks) {
     __shared__ float4 tile[NN_TILE + NN_B];
     __shared__ float tile_pm[NN_BLOCK / 64];
-    for (unsigned blk = blockIdx.x; blk < nblocks; blk += gridDim.x) {      // (a capped grid walks the query tiles: GSPN_NN_GRID)
+    for (unsigned blk = blockIdx.x; blk < nblocks; blk += gridDim.x) {      // (a grid smaller than nblocks walks the query tiles; the launcher sends one workgroup per tile)
     const int scene = blk % b;                      // scene <-> XCD affinity for the sparse cloud
     const int j0 = (blk / b) * (NN_BLOCK * NN_Q) + threadIdx.x;      // queries j0 + u*NN_BLOCK
     float x1[NN_Q], y1[NN_Q], z1[NN_Q];
@@ -204,8 +204,7 @@ __global__ __launch_bounds__(256) void three_nn_wave_kernel(int b, int n, int m,
     }
 }
 static bool nn_wave_ok(int n, int m) {
-    static const int on = [] { const char* e = getenv("GSPN_NN_WAVE"); return e ? atoi(e) : 1; }();     // (tuning / A-B hook)
-    return on && m >= 1 && m <= NN_WAVE_MAX_M && n >= 1;
+    return m >= 1 && m <= NN_WAVE_MAX_M && n >= 1;
 }
 static int launch_three_nn_wave(int b, int n, int m, const float* xyz1, const float* xyz2, float* dist, int* idx, hipStream_t st) {
     const int wpscene = (n + NN_WAVE_QPW - 1) / NN_WAVE_QPW;
@@ -392,13 +391,19 @@ __global__ __launch_bounds__(NNG_T) void three_nn_grid_kernel(int b, int n, int 
         oi[0] = s.i1; oi[1] = s.i2; oi[2] = s.i3;
     }
 }
+// build-time constants of the cell grid's launch: target points per cell, queries per thread
+#ifndef GSPN_NN_CELL_POINTS
+#define GSPN_NN_CELL_POINTS 4
+#endif
+#ifndef GSPN_NN_CELL_QPW
+#define GSPN_NN_CELL_QPW 1
+#endif
+static_assert(GSPN_NN_CELL_POINTS > 0 && GSPN_NN_CELL_QPW > 0, "cell-grid constants are positive");
 static bool nn_grid_ok(int n, int m) {
-    static const int on = [] { const char* e = getenv("GSPN_NN_CELLS"); return e ? atoi(e) : 1; }();     // (A/B hook: 0 = the all-pairs kernel)
-    return on && m > NN_WAVE_MAX_M && m <= NNG_MAX_M && n >= 1;
+    return m > NN_WAVE_MAX_M && m <= NNG_MAX_M && n >= 1;
 }
 static int launch_three_nn_grid(int b, int n, int m, const float* xyz1, const float* xyz2, float* dist, int* idx, const int* order, hipStream_t st) {
-    static const int ppc = [] { const char* e = getenv("GSPN_NN_CELL_POINTS"); const int v = e ? atoi(e) : 4; return v > 0 ? v : 4; }();       // target points per cell
-    static const int qpw = [] { const char* e = getenv("GSPN_NN_CELL_QPW"); const int v = e ? atoi(e) : 1; return v > 0 ? v : 1; }();          // queries per thread
+    constexpr int ppc = GSPN_NN_CELL_POINTS, qpw = GSPN_NN_CELL_QPW;
     int G = (int)floor(cbrt((double)m / ppc) + 0.5);
     G = G < 2 ? 2 : (G > NNG_MAX_G ? NNG_MAX_G : G);
     const size_t dyn = sizeof(float4) * (size_t)m + sizeof(int) * (2 * (size_t)G * G * G + 1);
@@ -419,10 +424,6 @@ static int launch_three_nn_grid(int b, int n, int m, const float* xyz1, const fl
     return gspn_launch_status();
 }
 
-static unsigned nn_grid(long long blocks) {
-    static const long long cap = [] { const char* e = getenv("GSPN_NN_GRID"); const long long v = e ? atoll(e) : 0; return v > 0 ? v : (1ll << 31); }();
-    return (unsigned)(blocks < cap ? blocks : cap);
-}
 extern "C" int gspn_threenn(int b, int n, int m, const float* xyz1, const float* xyz2, float* dist, int* idx, void* stream) {
     if (b < 0 || n < 0 || m < 0) return GSPN_ERR_ARG;
     if (b == 0 || n == 0) return 0;
@@ -430,7 +431,7 @@ extern "C" int gspn_threenn(int b, int n, int m, const float* xyz1, const float*
     if (nn_grid_ok(n, m)) return launch_three_nn_grid(b, n, m, xyz1, xyz2, dist, idx, nullptr, (hipStream_t)stream);
     const long long blocks = (long long)b * ((n + NN_BLOCK * NN_Q - 1) / (NN_BLOCK * NN_Q));
     if (blocks > 0x7FFFFFFFll) return GSPN_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(three_nn_kernel, dim3(nn_grid(blocks)), dim3(NN_BLOCK), 0, (hipStream_t)stream, b, n, m, xyz1, xyz2, dist, idx, (const int*)nullptr, (unsigned)blocks);
+    hipLaunchKernelGGL(three_nn_kernel, dim3((unsigned)blocks), dim3(NN_BLOCK), 0, (hipStream_t)stream, b, n, m, xyz1, xyz2, dist, idx, (const int*)nullptr, (unsigned)blocks);
     return gspn_launch_status();
 }
 extern "C" int gspn_threenn_ordered(int b, int n, int m, const float* xyz1, const float* xyz2, const int* order, float* dist, int* idx, void* stream) {
@@ -440,7 +441,7 @@ extern "C" int gspn_threenn_ordered(int b, int n, int m, const float* xyz1, cons
     if (nn_grid_ok(n, m)) return launch_three_nn_grid(b, n, m, xyz1, xyz2, dist, idx, order, (hipStream_t)stream);
     const long long blocks = (long long)b * ((n + NN_BLOCK * NN_Q - 1) / (NN_BLOCK * NN_Q));
     if (blocks > 0x7FFFFFFFll) return GSPN_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(three_nn_kernel, dim3(nn_grid(blocks)), dim3(NN_BLOCK), 0, (hipStream_t)stream, b, n, m, xyz1, xyz2, dist, idx, order, (unsigned)blocks);
+    hipLaunchKernelGGL(three_nn_kernel, dim3((unsigned)blocks), dim3(NN_BLOCK), 0, (hipStream_t)stream, b, n, m, xyz1, xyz2, dist, idx, order, (unsigned)blocks);
     return gspn_launch_status();
 }
 

@@ -805,34 +805,40 @@ static inline unsigned row_grid(long rows, int ytiles, int per_cu) {
 // Column-tile width of the register-staged GEMM kernels (forward fallback, pass B) for `cols` output columns: the widest of 128/64/32
 // that still gives the chip one workgroup per CU, unless a narrower one wastes markedly fewer padded columns (131 columns: 3 x 64
 // instead of 2 x 128).  Short layers (<= 16384 rows) thus run 32-wide tiles in 4-8 column blocks instead of a quarter of the CUs
-// (tools/fwd_sweep.py on MI355X: 4096 x 384 -> 256 forward 44 -> 27 us, pass B 33 -> 26 us).  GSPN_FWD_FORCE_BN / GSPN_BWD_FORCE_BN
-// override it (tuning hooks).
-static inline int pick_bn(long rows, int cols, const char* env) {
-    {
-        const char* e = getenv(env);
-        const int f = e ? atoi(e) : 0;
-        if (f == 32 || f == 64 || f == 128) return f;
-    }
+// (measured on MI355X, sweep closed: 4096 x 384 -> 256 forward 44 -> 27 us, pass B 33 -> 26 us).
+// GSPN_BN_FILL: the number of workgroups below which a tile width counts as not filling the chip (build-time constant).
+#ifndef GSPN_BN_FILL
+#define GSPN_BN_FILL (2 * GSPN_PLAN_CUS)
+#endif
+static inline int pick_bn(long rows, int cols) {
     const long ntiles = (rows + TM - 1) / TM;
     auto nblk = [&](int bn) { return ntiles * ((cols + bn - 1) / bn); };
     auto pad = [&](int bn) { return (cols + bn - 1) / bn * bn; };
     int bn = cols <= 32 ? 32 : (cols <= 64 ? 64 : 128);
-    static int fill = 0;
-    if (!fill) { const char* e = getenv("GSPN_BN_FILL"); fill = e ? atoi(e) : 2 * GSPN_PLAN_CUS; if (fill <= 0) fill = 2 * GSPN_PLAN_CUS; }
-    while (bn > 32 && (nblk(bn) < fill || 4 * pad(bn) > 5 * pad(bn / 2))) bn /= 2;
+    while (bn > 32 && (nblk(bn) < GSPN_BN_FILL || 4 * pad(bn) > 5 * pad(bn / 2))) bn /= 2;
     return bn;
 }
 // number of row-blocks (= partial-statistics rows) the forward launch of a (rows, cout) layer uses
 // (workgroups per CU = what the kernel's LDS footprint lets reside at once: a persistent grid larger than that runs a second wave)
-static inline int bwd_bpc_narrow() { static const int v = env_int("GSPN_BWD_BPC", 4); return v < 1 ? 1 : v; }
-static inline bool fwd_short_rows(long rows) { static const int on = env_int("GSPN_FWD_SHORT", 1); return on && rows >= 64 && rows <= GSPN_SHORT_ROWS && !(rows & 63); }
+// build-time constants: workgroups per CU of pass B's narrow (<= 64-column) tiles, of the streaming forward, and of the forward's 128-column tiles
+#ifndef GSPN_BWD_BPC
+#define GSPN_BWD_BPC 4
+#endif
+#ifndef GSPN_FWD_BPC
+#define GSPN_FWD_BPC 4
+#endif
+#ifndef GSPN_FWD_WIDE_BPC
+#define GSPN_FWD_WIDE_BPC 3
+#endif
+static_assert(GSPN_BN_FILL > 0 && GSPN_BWD_BPC >= 1 && GSPN_FWD_BPC >= 1 && GSPN_FWD_WIDE_BPC >= 1, "grid constants are positive");
+static inline bool fwd_short_rows(long rows) { return rows >= 64 && rows <= GSPN_SHORT_ROWS && !(rows & 63); }
 // (the count depends on (rows, cout) only -- it sizes a caller-allocated buffer through gspn_mlp_fwd_stats_bytes, which has no cin / pointer
 //  arguments -- so a layer of <= 8192 rows that the split-K kernel then DECLINES (cin not one of its instances, an unaligned operand, a gathered source)
 //  still gets one partial row per 32 rows: the 128-row-tile kernels below are launched with up to 4x more workgroups than tiles; the extra ones write their
 //  zero statistics row and leave.  Correct, and bounded at 256 workgroups of a few hundred cycles on layers of <= 8192 rows.)
 static inline unsigned fwd_blocks(long rows, int cout) {
     if (fwd_short_rows(rows)) return (unsigned)short_fwd_parts(rows);      // short layers (mlp_short.hip): one partial row per 32-row tile, at most 512
-    return row_grid(rows, cout <= 64 ? 1 : (cout + 127) / 128, cout <= 64 ? 4 : env_int("GSPN_FWD_WIDE_BPC", 3));
+    return row_grid(rows, cout <= 64 ? 1 : (cout + 127) / 128, cout <= 64 ? 4 : GSPN_FWD_WIDE_BPC);
 }
 extern "C" long gspn_mlp_fwd_stats_bytes(long rows, int cout) {
     if (rows < 0 || cout <= 0) return GSPN_ERR_ARG;
@@ -1211,7 +1217,6 @@ static int mlp_fwd_impl(long rows, int cin, int cout, const float* X, int ldx, c
         // short layers (<= GSPN_SHORT_ROWS = 8192 rows): split-K over the waves of a workgroup, operands straight from global memory (mlp_short.hip, r05)
         if (!gsrc && fwd_short_rows(rows) && gspn_fwd_short_go(rows, cin, cout, X, ldx, in_scale, in_shift, W, bias, Y, ldy, stats, fwd_blocks(rows, cout), po, st))
             return gspn_launch_status();
-        static const int lean_on = env_int("GSPN_FWD_LEAN", 1);             // (A/B hook)
         static const int lean_bn = env_int("GSPN_FWD_LEAN_BN", 0);          // (tuning hook)
         // (beyond ~0.75 M rows the eight 32-column blocks of a 256-column layer re-read X from beyond the L2s: 1 M x 128 -> 256 946 us against
         //  874 for the 128-column register-staged kernel, 1 M x 64 -> 128 274 against 259 for the streaming kernel; 0.5 M rows: 431 / 437, 137 / 151)
@@ -1223,7 +1228,7 @@ static int mlp_fwd_impl(long rows, int cin, int cout, const float* X, int ldx, c
             const unsigned nb = fwd_blocks(rows, cout);
             if (nb % nsplit || rows % ((long)nsplit * 128)) nsplit = 0;
         } else if (rows > 786432) nsplit = 0;
-        if (lean_on && !gsrc && nsplit >= 1 && vec_ok(X, ldx) && vec_ok(W, cout) && !(rows & 127) && !(cin & 31) && !(cout & 31) && rows * (long)std::max(ldx, ldy) < (1L << 30) && (long)cin * cout < (1L << 30) &&
+        if (!gsrc && nsplit >= 1 && vec_ok(X, ldx) && vec_ok(W, cout) && !(rows & 127) && !(cin & 31) && !(cout & 31) && rows * (long)std::max(ldx, ldy) < (1L << 30) && (long)cin * cout < (1L << 30) &&
             (!po.vmax || !(rows & 31))) {
             // 32-column blocks: measured best on every layer shape of the benchmark and of the configs[3] shard (tools/fwd_ablate.py with
             // GSPN_FWD_LEAN_BN = 32 / 64): 131072 x 64 -> 128 35 us against 39 (and 44 for the LDS-DMA streaming kernel), 32768 x 128 -> 256 30 against 40
@@ -1255,13 +1260,11 @@ static int mlp_fwd_impl(long rows, int cin, int cout, const float* X, int ldx, c
         const int trg = sp.trg;
         const bool src_ok = gsrc ? true : (vec_ok(X, ldx) && ldx >= 4 && rows * (long)ldx < (1L << 31));
         if (gsrc && !trg) return GSPN_ERR_UNSUPPORTED;
-        if (trg && src_ok && rows < (1L << 31) && rows * (long)ldy < (1L << 31) && (gsrc || getenv("GSPN_FWD_NO_STREAM") == nullptr)) {
+        if (trg && src_ok && rows < (1L << 31) && rows * (long)ldy < (1L << 31)) {
             const size_t dyn = sp.dyn;
             const long ntiles = (rows + 32 * trg - 1) / (32 * trg);
             long bpc = (160L * 1024) / (long)(dyn + 2 * trg * BNs * 4 + 512);
-            static int bpc_cap = 0;
-            if (!bpc_cap) { const char* e = getenv("GSPN_FWD_BPC"); bpc_cap = e ? atoi(e) : 4; if (bpc_cap < 1) bpc_cap = 4; }
-            if (bpc > bpc_cap) bpc = bpc_cap;
+            if (bpc > GSPN_FWD_BPC) bpc = GSPN_FWD_BPC;
             if (bpc < 1) bpc = 1;
             const unsigned nparts = fwd_blocks(rows, cout);
             long gx = (long)GSPN_PLAN_CUS * bpc / yt;
@@ -1283,7 +1286,7 @@ static int mlp_fwd_impl(long rows, int cin, int cout, const float* X, int ldx, c
 #define FWD_LAUNCH(BN_)                                                                                                            \
     hipLaunchKernelGGL((mlp_fwd_kernel<BN_, decltype(V)::value>), dim3(fwd_blocks(rows, cout), yt), dim3(256), sizeof(float) * 2 * chan_pad(cin), st, rows, cin, cout, X, ldx, \
                        in_scale, in_shift, W, bias, Y, ldy, stats, po)
-    const int bn = pick_bn(rows, cout, "GSPN_FWD_FORCE_BN");
+    const int bn = pick_bn(rows, cout);
     const int yt = (cout + bn - 1) / bn;
     with_bool(v, [&](auto V) { if (bn == 32) FWD_LAUNCH(32); else if (bn == 64) FWD_LAUNCH(64); else FWD_LAUNCH(128); });
 #undef FWD_LAUNCH
@@ -2151,37 +2154,21 @@ static WgradPlan wgrad_plan(long rows, int cin, int cout, bool generic = false, 
     WgradPlan p;
     const int mt = (cin + 31) / 32, nt = (cout + 31) / 32;
     if (generic) {
-        p.nrow = (mt + 3) / 4; p.ncol = (nt + 3) / 4;
-        p.MTs = (mt + p.nrow - 1) / p.nrow;
-        p.NTs = (nt + p.ncol - 1) / p.ncol;
-        if (p.NTs == 3) p.NTs = 4;
+        p.nrow = (cin + 127) / 128; p.ncol = (cout + 127) / 128; p.MTs = 4; p.NTs = 4; p.TKW = 32;
     } else {
         // Small tiles: one 32-row strip of dW per workgroup, 1-4 column tiles.  More tiles per layer means fewer row chunks for the same
         // number of workgroups, i.e. fewer partial tiles to write and sum (that traffic rivals the inputs of the small-row layers), and
-        // a re-read input tile is an L2 hit.  Swept on MI355X over all 16 layers of the benchmark stack (tools/wgrad_sweep.py): MT = 1
+        // a re-read input tile is an L2 hit.  Swept on MI355X over all 16 layers of the benchmark stack (sweep closed, rounds 3-5): MT = 1
         // wins everywhere (by 10-25 % below 131072 rows); NT = 4 for the pooled kernel, 2 for the long layers, 1 for the short ones.
+        // INVARIANT: MTs == 1 in every streaming plan, and NTs == 4 only in a pooled one: wgrad_impl's streaming launches are
+        // instantiated for exactly these shapes and test neither again.
         p.MTs = 1; p.nrow = mt;
         int want = pooled ? 4 : (rows >= 131072 ? 2 : 1);
         while (want > 1 && want / 2 >= nt) want /= 2;
         p.NTs = want; p.ncol = (nt + want - 1) / want;
+        // rows staged per iteration (streaming kernel): one stage is 14-24 KB of LDS, two stages per workgroup, 3 workgroups per CU
+        p.TKW = p.NTs == 1 ? 64 : (p.NTs == 2 ? 32 : 16);
     }
-    // rows staged per iteration (streaming kernel): one stage is 14-24 KB of LDS, two stages per workgroup, 3 workgroups per CU
-    static const int tkw[4][3] = {{64, 32, 16}, {32, 32, 16}, {32, 16, 16}, {32, 16, 16}};      // [MT-1][NT: 1,2,4]
-    p.TKW = tkw[p.MTs - 1][p.NTs == 1 ? 0 : (p.NTs == 2 ? 1 : 2)];
-    // tuning hook (tools/wgrad_sweep.py): GSPN_WGRAD_FORCE="MTs,NTs,chunks" overrides the tile shape / the number of row chunks (0 = keep)
-    long forced_chunks = 0;
-    if (!generic) {
-        const char* e = getenv("GSPN_WGRAD_FORCE");
-        int fm = 0, fn = 0;
-        long fc = 0;
-        if (e && sscanf(e, "%d,%d,%ld", &fm, &fn, &fc) >= 2) {
-            if (fm >= 1 && fm <= 4) { p.MTs = fm; p.nrow = (mt + fm - 1) / fm; }
-            if (fn == 1 || fn == 2 || fn == 4) { p.NTs = fn; p.ncol = (nt + fn - 1) / fn; }
-            p.TKW = tkw[p.MTs - 1][p.NTs == 1 ? 0 : (p.NTs == 2 ? 1 : 2)];
-            forced_chunks = fc;
-        }
-    }
-    if (generic) { p.nrow = (cin + 127) / 128; p.ncol = (cout + 127) / 128; p.MTs = 4; p.NTs = 4; p.TKW = 32; }
     const int T = p.MTs * p.NTs;
     p.WK = generic ? 1 : ((T % 4 == 0) ? 1 : ((T % 2 == 0) ? 2 : 4));
     const long ntile = (long)p.ncol * p.nrow;
@@ -2208,7 +2195,6 @@ static WgradPlan wgrad_plan(long rows, int cin, int cout, bool generic = false, 
     long floor_ch = GSPN_PLAN_CUS / ntile;                            // but never fewer than one workgroup per CU (if the layer has the rows)
     if (floor_ch < 1) floor_ch = 1;
     if (chunks > by_size) chunks = by_size > floor_ch ? by_size : floor_ch;
-    if (forced_chunks > 0) chunks = forced_chunks;
     long rpc = (rows + chunks - 1) / chunks;
     if (rpc < 4L * p.TKW) rpc = 4L * p.TKW;
     const long rq = p.TKW > 32 ? p.TKW : 32;              // (r03) whole stages of the lean kernel (32 rows) as well as of the streaming one (TKW)
@@ -2588,26 +2574,21 @@ __global__ __launch_bounds__(256) void wgrad_lean_kernel(int rows, int cin, int 
                 *reinterpret_cast<float*>(reinterpret_cast<char*>(P1 + (size_t)(mrow + (r & 3) + 8 * (r >> 2)) * cout) + lo) = acc[x][y][r];
         }
 }
-// the lean kernel takes a known-coefficient pass A when its shape assumptions hold (GSPN_WGRAD_LEAN=0: never); false otherwise
+// the lean kernel takes a known-coefficient pass A of a pooled layer when its shape assumptions hold; false otherwise
 static bool wgrad_lean_try(long rows, int cin, int cout, const gspn_dy_args* a, const float* X, int ldx, const float* in_scale, const float* in_shift,
                            float* PP, const WgradPlan& p, hipStream_t st) {
-    static const int on = env_int("GSPN_WGRAD_LEAN", 1);
-    if (!on || p.shared || (rows & 31) || (p.rpc & 31) || (cin & 31) || (cout & 63)) return false;
-    const bool pooled = a->dZ == nullptr;
+    if (p.shared || (rows & 31) || (p.rpc & 31) || (cin & 31) || (cout & 63)) return false;
     // Measured against the LDS-DMA streaming kernel on MI355X (tools/wgrad_ablate.py, us lean / streaming): it wins where the streaming
     // kernel's on-read operand construction is most expensive -- the pooled top layers with >= 128 output channels (131072 x 64^T x 128:
     // 42 / 52, 32768 x 128^T x 256: 56 / 59, 1 M x 128^T x 256: 1021 / 1126) -- and loses on the dense layers (262144 x 64^T x 64: 54 / 48,
     // 32768 x 128^T x 128: 56 / 33, 4096 x 384^T x 256: 39 / 24): two barriers per 32-row stage and the chunk count planned for the streaming
-    // kernel's finer tiles leave it short of workgroups there.  GSPN_WGRAD_LEAN=2 takes every eligible shape (A/B hook).
-    if (on != 2 && !(pooled && cout >= 128)) return false;
-    int pool_sh = 0;
-    if (pooled) {
-        if (a->ns < 32 || (a->ns & (a->ns - 1)) || rows % a->ns) return false;
-        // (dPool, pool_arg) are fetched as one quad each per stage; wgrad_choose -- whose use_stream let us in -- looks at X, Y and a dense dZ only
-        if (((uintptr_t)a->dPool % 16) || ((uintptr_t)a->pool_arg % 16)) return false;
-        pool_sh = __builtin_ctz(a->ns);
-    }
-    const long ldmax = std::max(std::max((long)ldx, (long)a->ldy), (long)(pooled ? 0 : a->ldz));
+    // kernel's finer tiles leave it short of workgroups there.  (The A/B sweep that ran the dense layers through it is closed.)
+    if (a->dZ != nullptr || cout < 128) return false;
+    if (a->ns < 32 || (a->ns & (a->ns - 1)) || rows % a->ns) return false;
+    // (dPool, pool_arg) are fetched as one quad each per stage; wgrad_choose -- whose use_stream let us in -- looks at X, Y and a dense dZ only
+    if (((uintptr_t)a->dPool % 16) || ((uintptr_t)a->pool_arg % 16)) return false;
+    const int pool_sh = __builtin_ctz(a->ns);
+    const long ldmax = std::max((long)ldx, (long)a->ldy);
     if (p.rpc * ldmax >= (1L << 30) || rows * ldmax >= (1L << 40)) return false;
     const int mt = cin / 32, nt = cout / 32;
     const int MBs = (mt % 4 == 0) ? 4 : ((mt % 2 == 0) ? 2 : 0);
@@ -2617,9 +2598,9 @@ static bool wgrad_lean_try(long rows, int cin, int cout, const gspn_dy_args* a, 
     const dim3 g((unsigned)((p.nch + 7) / 8 * 8 * nbm * nbn));
     const size_t dyn = sizeof(float) * (2 * chan_pad(cin) + 5 * chan_pad(cout));
     const bool act = in_scale != nullptr;
-#define WL_GO(MB_) hipLaunchKernelGGL((wgrad_lean_kernel<MB_, 2, decltype(P)::value ? 1 : 0, decltype(A)::value>), g, dim3(256), dyn, st, (int)rows, cin, cout, *a, X, ldx, \
+#define WL_GO(MB_) hipLaunchKernelGGL((wgrad_lean_kernel<MB_, 2, 1, decltype(A)::value>), g, dim3(256), dyn, st, (int)rows, cin, cout, *a, X, ldx, \
                                       in_scale, in_shift, PP, (int)p.rpc, (int)p.nch, nbm, nbn, pool_sh)
-    with_bool(pooled, [&](auto P) { with_bool(act, [&](auto A) { if (MBs == 4) WL_GO(4); else WL_GO(2); }); });
+    with_bool(act, [&](auto A) { if (MBs == 4) WL_GO(4); else WL_GO(2); });
 #undef WL_GO
     return true;
 }
@@ -2669,12 +2650,12 @@ static int wgrad_impl(long rows, int cin, int cout, const gspn_dy_args* a, const
         if (pooled || !vec_ok(a->Y, a->ldy) || !vec_ok(a->dZ, a->ldz) || cout < 4) return GSPN_ERR_UNSUPPORTED;
         p = wgrad_plan(rows, cin, cout, false, false);
         const long ldmax = a->ldy > a->ldz ? a->ldy : a->ldz;
-        if (p.rpc * ldmax >= (1L << 31) || p.MTs != 1 || !(p.NTs == 1 || p.NTs == 2)) return GSPN_ERR_UNSUPPORTED;
+        if (p.rpc * ldmax >= (1L << 31)) return GSPN_ERR_UNSUPPORTED;
         use_stream = true;
     } else {
         p = wgrad_choose(rows, cin, cout, a, X, ldx, &use_stream);
     }
-    if (known && (!use_stream || p.MTs != 1 || !a->cA || !a->cB || !a->cC)) return GSPN_ERR_UNSUPPORTED;
+    if (known && (!use_stream || !a->cA || !a->cB || !a->cC)) return GSPN_ERR_UNSUPPORTED;
     char* wb = reinterpret_cast<char*>(work);
     if (reinterpret_cast<uintptr_t>(wb) % 16) return GSPN_ERR_ARG;
     double* red = reinterpret_cast<double*>(wb);
@@ -2695,22 +2676,21 @@ static int wgrad_impl(long rows, int cin, int cout, const gspn_dy_args* a, const
 #define WS_ARGS (int)rows, cin, cout, *a, X, ldx, in_scale, in_shift, mu, vr, eps, RP, GP, PP, (int)p.rpc, (int)p.nslots, p.shared, (int)p.nch, p.nrow, p.ncol
 #define WS_GO(MT_, NT_, TKW_, G_, P_) hipLaunchKernelGGL((wgrad_stream_kernel<MT_, NT_, TKW_, G_, P_>), grid, dim3(256), 0, st, WS_ARGS, GatherSrc{})
 #define WS_GATHER(MT_, NT_, TKW_)                                                                \
-        if (!launched && gsrc && p.MTs == MT_ && p.NTs == NT_ && p.TKW == TKW_) {               \
+        if (!launched && gsrc && p.NTs == NT_ && p.TKW == TKW_) {                               \
             if (tr) hipLaunchKernelGGL((wgrad_stream_kernel<MT_, NT_, TKW_, true, false, true>), grid, dim3(256), 0, st, WS_ARGS, *gsrc);    \
             else hipLaunchKernelGGL((wgrad_stream_kernel<MT_, NT_, TKW_, false, false, true>), grid, dim3(256), 0, st, WS_ARGS, *gsrc);      \
             launched = 1;                                                                       \
         }
 #define WS_KNOWN(MT_, NT_, TKW_)                                                                 \
-        if (!launched && known && p.MTs == MT_ && p.NTs == NT_ && p.TKW == TKW_) {              \
+        if (!launched && known && p.NTs == NT_ && p.TKW == TKW_) {                              \
             if (gsrc) hipLaunchKernelGGL((wgrad_stream_kernel<MT_, NT_, TKW_, false, false, true, true>), grid, dim3(256), 0, st, WS_ARGS, *gsrc);          \
             else if (pooled) hipLaunchKernelGGL((wgrad_stream_kernel<MT_, NT_, TKW_, false, true, false, true>), grid, dim3(256), 0, st, WS_ARGS, GatherSrc{}); \
             else hipLaunchKernelGGL((wgrad_stream_kernel<MT_, NT_, TKW_, false, false, false, true>), grid, dim3(256), 0, st, WS_ARGS, GatherSrc{});        \
             launched = 1;                                                                       \
         }
         if (!launched) { WS_KNOWN(1, 1, 64) WS_KNOWN(1, 2, 32) }
-        if (!launched && known && !gsrc && p.MTs == 1 && p.NTs == 4 && p.TKW == 16) {
-            if (pooled) hipLaunchKernelGGL((wgrad_stream_kernel<1, 4, 16, false, true, false, true>), grid, dim3(256), 0, st, WS_ARGS, GatherSrc{});
-            else hipLaunchKernelGGL((wgrad_stream_kernel<1, 4, 16, false, false, false, true>), grid, dim3(256), 0, st, WS_ARGS, GatherSrc{});
+        if (!launched && known && pooled && p.NTs == 4 && p.TKW == 16) {                        // (NTs == 4: pooled layers only)
+            hipLaunchKernelGGL((wgrad_stream_kernel<1, 4, 16, false, true, false, true>), grid, dim3(256), 0, st, WS_ARGS, GatherSrc{});
             launched = 1;
         }
         if (known && !launched) return GSPN_ERR_UNSUPPORTED;
@@ -2719,16 +2699,17 @@ static int wgrad_impl(long rows, int cin, int cout, const gspn_dy_args* a, const
         if (gsrc && !launched) return GSPN_ERR_UNSUPPORTED;
 #undef WS_GATHER
 #define WS_TRY(MT_, NT_, TKW_)                                                                   \
-        if (!launched && p.MTs == MT_ && p.NTs == NT_ && p.TKW == TKW_) {                       \
+        if (!launched && p.NTs == NT_ && p.TKW == TKW_) {                                       \
             if (tr) { if (pooled) WS_GO(MT_, NT_, TKW_, true, true); else WS_GO(MT_, NT_, TKW_, true, false); }     \
             else    { if (pooled) WS_GO(MT_, NT_, TKW_, false, true); else WS_GO(MT_, NT_, TKW_, false, false); }   \
             launched = 1;                                                                       \
         }
-        WS_TRY(1, 1, 64) WS_TRY(1, 2, 32) WS_TRY(1, 4, 16)
-        WS_TRY(2, 1, 32) WS_TRY(2, 2, 32) WS_TRY(2, 4, 16)
-        WS_TRY(3, 1, 32) WS_TRY(3, 2, 16)
-        WS_TRY(4, 1, 32) WS_TRY(4, 2, 16)
+        WS_TRY(1, 1, 64) WS_TRY(1, 2, 32)
 #undef WS_TRY
+        if (!launched && pooled && p.NTs == 4 && p.TKW == 16) {                                 // (NTs == 4: pooled layers only)
+            if (tr) WS_GO(1, 4, 16, true, true); else WS_GO(1, 4, 16, false, true);
+            launched = 1;
+        }
 #undef WS_GO
 #undef WS_ARGS
         if (!launched) return GSPN_ERR_UNSUPPORTED;
@@ -2808,9 +2789,9 @@ __global__ __launch_bounds__(256) void pool_rsum_kernel(long groups, int ns, int
 // floats of a partial-sum buffer [nparts][2][c] large enough for gspn_pool_rsum and for pass B's epilogue (one row per workgroup)
 extern "C" long gspn_rsum_part_floats(long rows, int c) {
     if (c <= 0) return GSPN_ERR_ARG;
-    // pass B writes one partial row per workgroup of row_grid(rows, yt, bpc), bpc = bwd_bpc_narrow() (or 2 for 128-column tiles): size the
-    // buffer from the same value, so the GSPN_BWD_BPC tuning hook cannot push the epilogue past it
-    const int bpc = bwd_bpc_narrow() > 4 ? bwd_bpc_narrow() : 4;
+    // pass B writes one partial row per workgroup of row_grid(rows, yt, bpc), bpc = GSPN_BWD_BPC (or 2 for 128-column tiles): size the
+    // buffer from the same value, so a build with a larger GSPN_BWD_BPC cannot push the epilogue past it
+    const int bpc = GSPN_BWD_BPC > 4 ? GSPN_BWD_BPC : 4;
     long n = row_grid(rows > 0 ? rows : 1, 1, bpc);
     if (n < RSUM_POOL_BLOCKS) n = RSUM_POOL_BLOCKS;
     return n * 2 * c;
@@ -3253,8 +3234,7 @@ extern "C" int gspn_preagg_ok(int cout) { return preagg_shape_ok(cout) ? 1 : 0; 
 static unsigned preagg_fwd_blocks(long rows, int cout) {
     const long rpi = 256 / (cout >> 2);
     long nb = (rows + 4 * rpi - 1) / (4 * rpi);
-    static const int cap = env_int("GSPN_PREAGG_BLOCKS", PREAGG_FWD_BLOCKS);
-    if (nb > cap) nb = cap;
+    if (nb > PREAGG_FWD_BLOCKS) nb = PREAGG_FWD_BLOCKS;
     if (nb >= 64) nb = nb / 8 * 8;                       // a multiple of the 8 XCDs: the kernel then gives each XCD its own eighth of the rows
     return (unsigned)(nb < 1 ? 1 : nb);
 }
@@ -3267,10 +3247,8 @@ extern "C" int gspn_preagg_fwd(long rows, int cout, int T, const float* F, const
     const PreaggSrc ps{F, idx, w, per_scene_rows, per_scene_src, side, side_ld, side_n};
     const unsigned nb = preagg_fwd_blocks(rows, cout);   // = the number of partial rows: gspn_bn_finalize_parts(..., gspn_preagg_fwd_parts(rows, cout), ...)
     const size_t sh = sizeof(float) * 2 * 256 * 4;       // 2 * rpi * cout floats, rpi * cout = 1024
-    static const int rows16 = env_int("GSPN_PREAGG_FWD16", 1);          // (A/B hook: 0 = round 3's kernel)
     const long fsrc_bytes = (long)(per_scene_rows > 0 ? ((rows + per_scene_rows - 1) / per_scene_rows) * (long)per_scene_src : 0) * cout * 4;
-    if (rows16 && (cout == 64 || cout == 128 || cout == 256) && fsrc_bytes < (1L << 31) && (side_n == 0 || side_ld != 4 || ((uintptr_t)side % 16) == 0)
-        && (per_scene_rows > 0 || true)) {
+    if ((cout == 64 || cout == 128 || cout == 256) && fsrc_bytes < (1L << 31) && (side_n == 0 || side_ld != 4 || ((uintptr_t)side % 16) == 0)) {
         // (global idx, per_scene_rows == 0: the kernel forms 32-bit byte offsets into F.  per_scene_src then carries the TOTAL number of source rows
         //  (r05, ADVICE r04: with m*nsample < n the source table is larger than `rows`); 0 = not given, the caller's F is taken to have at
         //  most `rows` source rows, as round 4 assumed.  Beyond 2^31 bytes the general kernel below runs.)
@@ -3283,10 +3261,9 @@ extern "C" int gspn_preagg_fwd(long rows, int cout, int T, const float* F, const
             return gspn_launch_status();
         }
     }
-    static const int uu = env_int("GSPN_PREAGG_U", 2);
-#define PA_GO(T_, U_) hipLaunchKernelGGL((preagg_fwd_kernel<T_, U_>), dim3(nb), dim3(256), sh, (hipStream_t)stream, rows, cout, ps, Wside, bias, Y, stats)
-    if (T == 1) { if (uu == 1) PA_GO(1, 1); else if (uu == 2) PA_GO(1, 2); else PA_GO(1, 4); }
-    else { if (uu == 1) PA_GO(3, 1); else if (uu == 2) PA_GO(3, 2); else PA_GO(3, 4); }
+    // (two rows in flight per thread: U = 2; the sweep over U = 1 / 2 / 4 is closed)
+#define PA_GO(T_) hipLaunchKernelGGL((preagg_fwd_kernel<T_, 2>), dim3(nb), dim3(256), sh, (hipStream_t)stream, rows, cout, ps, Wside, bias, Y, stats)
+    if (T == 1) PA_GO(1); else PA_GO(3);
 #undef PA_GO
     return gspn_launch_status();
 }
@@ -3823,11 +3800,9 @@ __global__ __launch_bounds__(256) void bwd_lean_kernel(int rows, int cout, gspn_
         }
     }
 }
-// the lean kernel takes the launch if every one of its shape assumptions holds (GSPN_BWD_LEAN=0: never -- A/B hook); returns false otherwise
+// the lean kernel takes the launch if every one of its shape assumptions holds; returns false otherwise
 static bool bwd_lean_try(long rows, int cin, int cout, const gspn_dy_args* a, const float* W, int col0, int ncols, float* dX, int ldx, const DwJob* dwj,
                          hipStream_t st, const RsumArgs& rs, int* nparts_out, const DwJob& none) {
-    static const int on = env_int("GSPN_BWD_LEAN", 1);
-    if (!on) return false;
     const bool pooled = a->dZ == nullptr;
     if ((rows & 127) || rows <= 0 || (cout & 31) || (ncols & 31) || (col0 & 3)) return false;
     if (!vec_ok(a->Y, a->ldy) || !vec_ok(W, cout) || !vec_ok(dX, ldx)) return false;
@@ -3840,15 +3815,13 @@ static bool bwd_lean_try(long rows, int cin, int cout, const gspn_dy_args* a, co
         pool_sh = __builtin_ctz(a->ns);
     } else if (!vec_ok(a->dZ, a->ldz)) return false;
     if (rs.Yp && (rs.ldyp & 3)) return false;
-    static const int force_bn = env_int("GSPN_BWD_LEAN_BN", 0);          // (tuning hook)
-    // measured on MI355X (tools/bwd_ablate.py, GSPN_BWD_LEAN_BN sweep): 64-column blocks everywhere they divide the range -- also for 128
+    // measured on MI355X (sweep over the block width, closed): 64-column blocks everywhere they divide the range -- also for 128
     // columns, where a 128-wide block would read dY once instead of twice but leaves one wave per SIMD (1 M x 128 <- 256 pooled: 934 us
     // against 1165) -- and 32-column blocks for the short layers (<= 16384 rows), which need the workgroups
-    int bn = (ncols % 64 == 0 && rows > 16384) ? 64 : 32;
-    if (force_bn && ncols % force_bn == 0 && force_bn <= 64) bn = force_bn;
+    const int bn = (ncols % 64 == 0 && rows > 16384) ? 64 : 32;
     const int yt = ncols / bn;
     const unsigned extra = dwj ? (unsigned)(dwj->nblk + dwj->nblk2) : 0u;
-    const unsigned rg = row_grid(rows, yt, bwd_bpc_narrow());
+    const unsigned rg = row_grid(rows, yt, GSPN_BWD_BPC);
     if (nparts_out) *nparts_out = (int)rg;
     DwJob dj = dwj ? *dwj : none;
     dj.rowgrid = (int)rg;
@@ -4115,7 +4088,7 @@ __global__ __launch_bounds__(256) void bwd_fused_kernel(int rows, gspn_dy_args a
 }
 // workgroups of the fused kernel for (rows, cin, cout); 0 = the shape is not one of its own.  The grid is what the chip holds AT ONCE
 // (the kernel's measured occupancy x the planned CUs): 672 workgroups of the two-per-CU 64 x 64 instance ran as one and a half rounds
-// -- 90 us against 73 for 448 (tools/fused_ablate.py, GSPN_BWD_FUSED_BPC sweep).
+// -- 90 us against 73 for 448 (tools/fused_ablate.py; the sweep over workgroups per CU is closed).
 template <int CI, int CO> static int fused_occupancy() {
     static int occ = 0;
     if (!occ) {
@@ -4126,15 +4099,11 @@ template <int CI, int CO> static int fused_occupancy() {
     return occ;
 }
 static unsigned fused_grid(long rows, int cin, int cout) {
-    static const int on = env_int("GSPN_BWD_FUSED", 1);
-    if (!on) return 0;
     if (!((cin == 32 || cin == 64) && (cout == 32 || cout == 64 || cout == 128))) return 0;
     const int tr = 128 / (cin / 32);
     if (rows < 65536 || rows % tr || rows % 128) return 0;        // (short layers: their launches are latency chains, two kernels overlap better)
-    static const int bpc_env = env_int("GSPN_BWD_FUSED_BPC", 0);
-    int bpc = cin == 32 ? (cout == 32 ? fused_occupancy<1, 1>() : (cout == 64 ? fused_occupancy<1, 2>() : fused_occupancy<1, 4>()))
+    const int bpc = cin == 32 ? (cout == 32 ? fused_occupancy<1, 1>() : (cout == 64 ? fused_occupancy<1, 2>() : fused_occupancy<1, 4>()))
                         : (cout == 32 ? fused_occupancy<2, 1>() : (cout == 64 ? fused_occupancy<2, 2>() : fused_occupancy<2, 4>()));
-    if (bpc_env > 0) bpc = bpc_env > 4 ? 4 : bpc_env;
     // never more workgroups than 128-row tiles: the BN-reduction buffer (gspn_rsum_part_floats) holds one row per such tile at most
     const long ntiles = rows / 128, cap = (long)GSPN_PLAN_CUS * bpc;
     return (unsigned)(ntiles < cap ? ntiles : cap);
@@ -4217,12 +4186,11 @@ static int bwd_data_launch(long rows, int cin, int cout, const gspn_dy_args* a, 
     const unsigned extra = dwj ? (unsigned)(dwj->nblk + dwj->nblk2) : 0u;
     // workgroups per CU the grid is sized for.  3 reside (waves per SIMD: the amdgpu_waves_per_eu attribute of the kernel keeps the 32- and
     // 64-column tiles under 168 VGPRs; 2 for 128), yet 4 measures best (pass B of the bench step: 648 / 596 / 581 us at 2 / 3 / 4):
-    // the fourth quarter of the workgroups fills the slots the first finishers free.  GSPN_BWD_BPC overrides (tuning hook).
-    const int bpc_narrow = bwd_bpc_narrow();
+    // the fourth quarter of the workgroups fills the slots the first finishers free.  (GSPN_BWD_BPC, a build-time constant.)
     if (bwd_lean_try(rows, cin, cout, a, W, col0, ncols, dX, ldx, dwj, st, rs, nparts_out, none)) return gspn_launch_status();
-    const int bn = pick_bn(rows, ncols, "GSPN_BWD_FORCE_BN");
+    const int bn = pick_bn(rows, ncols);
     const int yt = (ncols + bn - 1) / bn;
-    const unsigned rg = row_grid(rows, yt, bn >= 128 ? 2 : bpc_narrow);
+    const unsigned rg = row_grid(rows, yt, bn >= 128 ? 2 : GSPN_BWD_BPC);
     const dim3 g(dwj ? rg * (unsigned)yt + extra : rg, dwj ? 1 : yt);
     if (nparts_out) *nparts_out = (int)rg;
     DwJob dj = none;                                      // (with no job to carry, the kernel is handed the empty one as it is)

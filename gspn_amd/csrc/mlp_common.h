@@ -31,7 +31,7 @@ static inline bool vec_ok(const void* p, int ld) { return (ld % 4 == 0) && (((ui
 // without an if / else ladder of launches; both branches are instantiated, like the rungs of a ladder
 template <class F> static inline void with_bool(bool c, F&& f) { if (c) f(std::true_type{}); else f(std::false_type{}); }
 
-// rows at or below which the FORWARD of a layer takes the split-K kernel of mlp_short.hip.  Measured (tools/r05_short_ab.sh, graph-timed,
+// rows at or below which the FORWARD of a layer takes the split-K kernel of mlp_short.hip.  Measured (round-5 A/B, closed; graph-timed,
 // us, round-4 kernel -> split-K): 4096 x 256 -> 128 9.9 -> 7.1, 4096 x 128 -> 128 6.0 -> 4.4, 4096 x 384 -> 256 13.4 -> 13.3; at 16384 rows
 // 12.4 -> 13.9 / 6.9 -> 7.4 and at 32768 rows 17.5 -> 19.3 / 32.4 -> 38.4: with K = 128 a 32-row tile is 16 MFMAs per wave behind a full
 // global-load round trip, and the LDS footprint (partials + staged A) keeps 4 workgroups per CU -- not enough to cover it.  (A trivial

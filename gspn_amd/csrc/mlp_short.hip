@@ -19,7 +19,7 @@
 //     ds_read_b128 of 8 consecutive rows cover the 32 banks), one barrier; every wave then reads ITS k range as float4s.
 //     (First cut, measured and dropped: A straight from global memory too, lane = row, KW/2 consecutive floats each -- every lane of a
 //     load instruction touches its own cache line, 16 bytes of 128, and the vector L1's tag rate then costs more than the MFMAs:
-//     4096 x 384 -> 256 18.1 us against 13.5 for the round-4 kernel; tools/r05_short_ab.sh.)
+//     4096 x 384 -> 256 18.1 us against 13.5 for the round-4 kernel; round-5 A/B, closed.)
 //   * the four partial tiles meet in LDS once: every wave writes its accumulators, and wave q sums (((p0 + p1) + p2) + p3, a fixed
 //     order) the four accumulator registers 4q..4q+3 of every MFMA tile -- rows 8q + {0..3} + 4 (l >> 5) -- adds the bias, stores,
 //     and keeps the column sums / the 32-row pool extrema the long kernels' epilogues keep.
@@ -232,13 +232,12 @@ static bool fwd_short_launch(dim3 g, hipStream_t st, int rows, int cin, int cout
 using namespace gspn_k;
 
 // Tile shape per layer shape: enough workgroups to give every SIMD several waves (>= ~4 x 224 CUs), MFMA tiles per k step as large as that
-// allows (an A value feeds NT MFMAs, a B vector MT).  GSPN_FWD_SHORT_MT / _NT force a shape (tools/short_sweep.py), GSPN_FWD_SHORT=0 turns
-// the path off (the long layers' kernels then run these layers as in round 4).
+// allows (an A value feeds NT MFMAs, a B vector MT).  GSPN_FWD_SHORT_MT / GSPN_FWD_SHORT_NT force a shape (runtime
+// switches, read once: tests/test_gpu_mlp_instances.py reaches the instances the rule below does not pick through them).
 bool gspn_fwd_short_go(long rows, int cin, int cout, const float* X, int ldx, const float* in_scale, const float* in_shift, const float* W, const float* bias,
                        float* Y, int ldy, float* stats, unsigned nparts, PoolOut po, hipStream_t st) {
-    static const int on = env_int("GSPN_FWD_SHORT", 1);
     static const int f_mt = env_int("GSPN_FWD_SHORT_MT", 0), f_nt = env_int("GSPN_FWD_SHORT_NT", 0);
-    if (!on || rows > GSPN_SHORT_ROWS || rows < 64 || (rows & 63) || !vec_ok(X, ldx) || !vec_ok(W, cout) || (ldy & 3) || (((uintptr_t)Y) & 15)) return false;
+    if (rows > GSPN_SHORT_ROWS || rows < 64 || (rows & 63) || !vec_ok(X, ldx) || !vec_ok(W, cout) || (ldy & 3) || (((uintptr_t)Y) & 15)) return false;
     if (!(cin == 64 || cin == 128 || cin == 192 || cin == 256 || cin == 384) || (cout & 31)) return false;
     if (rows * (long)std::max(ldx, ldy) >= (1L << 30) || (long)cin * cout >= (1L << 28)) return false;
     if (nparts != (unsigned)short_fwd_parts(rows)) return false;

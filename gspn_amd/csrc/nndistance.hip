@@ -167,12 +167,9 @@ extern "C" int gspn_nmdistance_grad(int b, int n, const float* xyz1, int m, cons
     hipStream_t st = (hipStream_t)stream;
     hipError_t e;
     if (n > 0 && m > 0 && n + m <= NMG_MAX_PTS) {
-        static const int lds_on = [] { const char* ev = getenv("GSPN_NMGRAD_LDS"); return ev ? atoi(ev) : 1; }();      // (A/B hook)
-        if (lds_on) {
-            hipLaunchKernelGGL(nm_distance_grad_lds_kernel, dim3((unsigned)b), dim3(256), sizeof(float) * 3 * (size_t)(n + m), st, n, xyz1, m, xyz2, grad_dist1, idx1,
-                               grad_dist2, idx2, grad_xyz1, grad_xyz2);
-            return gspn_launch_status();
-        }
+        hipLaunchKernelGGL(nm_distance_grad_lds_kernel, dim3((unsigned)b), dim3(256), sizeof(float) * 3 * (size_t)(n + m), st, n, xyz1, m, xyz2, grad_dist1, idx1,
+                           grad_dist2, idx2, grad_xyz1, grad_xyz2);
+        return gspn_launch_status();
     }
     if (n > 0 && (e = hipMemsetAsync(grad_xyz1, 0, sizeof(float) * (size_t)b * n * 3, st)) != hipSuccess) return (int)e;   // :153
     if (m > 0 && (e = hipMemsetAsync(grad_xyz2, 0, sizeof(float) * (size_t)b * m * 3, st)) != hipSuccess) return (int)e;   // :154

@@ -783,9 +783,7 @@ __global__ __launch_bounds__(1024) void fps_vfill_kernel(int n, int G, const flo
 // slices per scene of the spread-out pre-pass (1 = fps_bin_kernel); scratch: G x (4096 ints + 6 floats) per scene, taken from the front of the scene's
 // slice of sxyz (n x 3 floats, written only by the cell sort that follows)
 static inline int fps_bin_slices(int n) {
-    static const int on = getenv("GSPN_FPS_BIN_SLICES") ? atoi(getenv("GSPN_FPS_BIN_SLICES")) : -1;      // tuning hook: 0 / 1 = off, k > 1 = force k
-    if (on == 0 || on == 1) return 1;
-    long G = on > 1 ? on : n / 4096;
+    long G = n / 4096;
     if (G > 32) G = 32;
     while (G > 1 && G * (4096L + 8) * 4 > (long)n * 12) --G;
     return G < 4 ? 1 : (int)G;

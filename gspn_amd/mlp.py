@@ -40,7 +40,7 @@ POOLTOP_STREAM = os.environ.get("GSPN_POOLTOP_STREAM", "1") != "0"
 # one launch for pass B + the dW reduction of the same layer (gspn_mlp_bwd_data with a gspn_dw_args) instead of two
 FUSE_DW = os.environ.get("GSPN_FUSE_DW", "1") != "0"
 # pass A and pass B of a layer in one launch where the library has the kernel for the shape (gspn_mlp_bwd_fused: both products from one staged
-# dY tile); the library's own switch is GSPN_BWD_FUSED
+# dY tile)
 FUSED_BWD = os.environ.get("GSPN_FUSED_BWD", "1") != "0"
 POOLTOP_FUSED = os.environ.get("GSPN_POOLTOP_FUSED", "1") != "0"
 FUSED_COEF = os.environ.get("GSPN_FUSED_COEF", "1") != "0"          # r04: the coefficient kernel after a fused launch carries that launch's dW reduction       # the pooled (nsample = 32) top layer through the fused launch as well

@@ -646,8 +646,8 @@ int gspn_mlp_bwd_wgrad_known(long rows, int cin, int cout, const gspn_dy_args* a
  * come from the same staged dY tile.  Xp (rows, ldxp) is the previous layer's raw output, in_scale / in_shift its forward scale / shift.
  * part (optional, with that layer's mean_p / var_p): its BN reductions, exactly what gspn_mlp_bwd_data leaves with rs (*nparts_out rows for
  * gspn_mlp_bwd_coef).  work: the gspn_mlp_bwd_work_bytes(rows, cin, cout) buffer.
- * GSPN_ERR_UNSUPPORTED outside cin in {32, 64}, cout in {32, 64, 128}, rows >= 65536 a multiple of 128, 16-byte aligned pitches
- * (GSPN_BWD_FUSED=0: always): run gspn_mlp_bwd_wgrad_known + gspn_mlp_bwd_data then. */
+ * GSPN_ERR_UNSUPPORTED outside cin in {32, 64}, cout in {32, 64, 128}, rows >= 65536 a multiple of 128, 16-byte aligned pitches:
+ * run gspn_mlp_bwd_wgrad_known + gspn_mlp_bwd_data then. */
 long gspn_mlp_bwd_fused_work_bytes(long rows, int cin, int cout);
 int gspn_mlp_bwd_fused(long rows, int cin, int cout, const gspn_dy_args* a, const float* W, const float* Xp, int ldxp, const float* in_scale,
                        const float* in_shift, float* dX, int ldx, float* work, float* dW, const float* mean_p, const float* var_p,

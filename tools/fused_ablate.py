@@ -1,5 +1,5 @@
 """gspn_mlp_bwd_fused alone (dW and dX of a layer in one launch + the dW reduction kernel) at the bench's shapes: microseconds, TB/s of the four
-row streams (Y, dZ, previous Y, dX), TFLOP/s of both products (library chosen by GSPN_HIP_LIB; GSPN_BWD_FUSED_BPC sets workgroups per CU)"""
+row streams (Y, dZ, previous Y, dX), TFLOP/s of both products (library chosen by GSPN_HIP_LIB)"""
 import ctypes, os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gspn_amd import _lib as L
@@ -27,7 +27,7 @@ def run(rows, cin, cout, reps=10):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record(); g.replay(); e1.record(); torch.cuda.synchronize()
     return e0.elapsed_time(e1) / reps * 1e3
-print("lib:", os.path.basename(L.LIB_PATH), "bpc", os.environ.get("GSPN_BWD_FUSED_BPC", "default"))
+print("lib:", os.path.basename(L.LIB_PATH))
 for rows, cin, cout in shapes:
     us = run(rows, cin, cout)
     by = 4.0 * rows * (2 * cout + 2 * cin); fl = 4.0 * rows * cin * cout

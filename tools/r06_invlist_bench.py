@@ -1,5 +1,5 @@
-"""gspn_inverse_lists at the five shapes of a bench batch (+ the group_point gradient's at SA level 1), graph-timed: GSPN_CSR_SLICES=1 (one workgroup per scene, r02-r05)
-against the default (r06: position slices over several workgroups per scene).  Output checked against a stable argsort."""
+"""gspn_inverse_lists at the five shapes of a bench batch (+ the group_point gradient's at SA level 1), graph-timed (r06: position slices over several
+workgroups per scene where the list is long enough, one workgroup per scene otherwise).  Output checked against a stable argsort."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

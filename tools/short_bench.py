@@ -1,5 +1,5 @@
 """The short layers' GEMM launches one by one (r05): correctness against an fp64 product and graph-timed microseconds, for the library as
-the environment configures it (GSPN_FWD_SHORT=0/1, GSPN_FWD_SHORT_MT/_NT, GSPN_BWD_SHORT..., GSPN_WGRAD_SHORT...).
+the environment configures it (GSPN_FWD_SHORT_MT / GSPN_FWD_SHORT_NT force a tile shape of the forward).
 usage: short_bench.py [fwd|bwd|wgrad|all]"""
 import ctypes, os, sys
 import numpy as np, torch

@@ -1,5 +1,5 @@
 """pass A with known coefficients (gspn_mlp_bwd_wgrad_known, incl. its dW reduction) at the bench's layer shapes: microseconds, TB/s of algorithmic
-bytes, TFLOP/s.  GSPN_WGRAD_LEAN=0 selects the streaming kernel."""
+bytes, TFLOP/s."""
 import ctypes, os, sys, torch
 sys.path.insert(0, __import__('os').path.dirname(__import__('os').path.dirname(__import__('os').path.abspath(__file__))))
 from gspn_amd import _lib as L

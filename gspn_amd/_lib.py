@@ -134,6 +134,7 @@ SIGNATURES = {
     "gspn_nms3d": [_I, _I, _I, _I, _F, _F, _P, _P, _P, _P],
     "gspn_box_point_count": [_I, _I, _I, _F, _P, _P, _P, _P],
     "gspn_sample_points_in_boxes": [_I, _I, _I, _I, _F, _P, _P, _P, _P, _P],
+    "gspn_sample_points_in_boxes_seeds": [_I, _I, _I, _I, _F, _P, _P, _P, _P, _P],
     "gspn_detection_target_select": [_I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P],
     "gspn_crop_gather_grad": [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
     "gspn_class_nms3d": [_I, _I, _I, _I, _F, _P, _P, _P, _P, _P],

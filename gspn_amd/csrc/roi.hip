@@ -5,6 +5,7 @@
 //   gspn_sample_points_in_boxes   sample_points_within_box (:584-597) without its (boxes, points) mask matrix: a workgroup per box, every wave
 //                                 compacts the inside indices of a contiguous quarter of the points, ascending, into its own LDS region
 //                                 (ballot + mbcnt), then draw j looks up rank (rand32 * count) >> 32 across the four regions.
+//   gspn_sample_points_in_boxes_seeds  the same kernel with a seed per scene (b of them on the device) in place of one seed and the scene's slot.
 //   gspn_detection_target_select  the decisions of detection_target_gen (:662-720) for the whole batch, one workgroup per scene, one lane per
 //                                 proposal: IoU against the ground-truth boxes, positive / negative, a random subsample of each by ranking
 //                                 32-bit keys.  Integer outputs only; padding rows are skipped in place, so no shape depends on data.
@@ -83,7 +84,9 @@ __global__ __launch_bounds__(BOX_SCAN_THREADS) void box_point_count_kernel(int s
 }
 
 // grid (r, b), SM_THREADS lanes.  Dynamic LDS: SM_WAVES regions of q = ceil(n / SM_WAVES) ints.
-__global__ __launch_bounds__(SM_THREADS) void sample_points_kernel(int r, int n, int nsmp, int q, float margin,
+// seed_stride 0: one seed for the batch, scene bi draws from the stream (seed_dev[0], bi).  1: a seed per scene, scene bi draws from
+// (seed_dev[bi], 0) -- what the scene draws when it is run alone with that seed, whichever slot of the batch it sits in.
+__global__ __launch_bounds__(SM_THREADS) void sample_points_kernel(int r, int n, int nsmp, int q, float margin, int seed_stride,
                                                                    const long long* __restrict__ seed_dev, const float* __restrict__ boxes,
                                                                    const float* __restrict__ pc, int* __restrict__ idx_out) {
     extern __shared__ __align__(16) int sm_list[];                   // [SM_WAVES][q]
@@ -126,7 +129,7 @@ __global__ __launch_bounds__(SM_THREADS) void sample_points_kernel(int r, int n,
         c[w] = wcnt[w];
         total += c[w];
     }
-    const unsigned long long st = roi_rand_scene(seed_dev[0], bi);
+    const unsigned long long st = roi_rand_scene(seed_dev[(long)bi * seed_stride], seed_stride ? 0 : bi);
     for (int j = tid; j < nsmp; j += SM_THREADS) {
         int v = 0;                                                   // no inside point, or an all-zero box: a row of zeros (:595)
         if (total > 0) {
@@ -277,16 +280,27 @@ extern "C" int gspn_box_point_count(int b, int s, int n, float margin, const flo
     return gspn_launch_status();
 }
 
-extern "C" int gspn_sample_points_in_boxes(int b, int r, int n, int nsmp, float margin, const long long* seed_dev, const float* boxes,
-                                           const float* pc, int* idx_out, void* stream) {
+static int sample_points_launch(int b, int r, int n, int nsmp, float margin, int seed_stride, const long long* seed_dev, const float* boxes,
+                                const float* pc, int* idx_out, void* stream) {
     if (b <= 0 || r <= 0 || n <= 0 || nsmp <= 0) return GSPN_ERR_ARG;
     if (n > SM_MAX_N || b > 65535) return GSPN_ERR_UNSUPPORTED;
     const int q = (n + SM_WAVES - 1) / SM_WAVES;
     const size_t lds = (size_t)SM_WAVES * q * sizeof(int);
     const hipError_t e = lds > 64 * 1024 ? gspn_dyn_lds_optin<&sample_points_kernel>(SM_MAX_N * (int)sizeof(int)) : hipSuccess;
     if (e != hipSuccess) return (int)e;
-    sample_points_kernel<<<dim3(r, b), SM_THREADS, lds, (hipStream_t)stream>>>(r, n, nsmp, q, margin, seed_dev, boxes, pc, idx_out);
+    sample_points_kernel<<<dim3(r, b), SM_THREADS, lds, (hipStream_t)stream>>>(r, n, nsmp, q, margin, seed_stride, seed_dev, boxes, pc,
+                                                                               idx_out);
     return gspn_launch_status();
+}
+
+extern "C" int gspn_sample_points_in_boxes(int b, int r, int n, int nsmp, float margin, const long long* seed_dev, const float* boxes,
+                                           const float* pc, int* idx_out, void* stream) {
+    return sample_points_launch(b, r, n, nsmp, margin, 0, seed_dev, boxes, pc, idx_out, stream);
+}
+
+extern "C" int gspn_sample_points_in_boxes_seeds(int b, int r, int n, int nsmp, float margin, const long long* seeds, const float* boxes,
+                                                 const float* pc, int* idx_out, void* stream) {
+    return sample_points_launch(b, r, n, nsmp, margin, 1, seeds, boxes, pc, idx_out, stream);
 }
 
 extern "C" int gspn_detection_target_select(int b, int s, int g, int rois_per_image, int max_positive, float inv_ratio, const long long* seed_dev,

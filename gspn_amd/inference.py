@@ -15,7 +15,7 @@ import torch
 from . import _lib as L
 from .detect import first_max_column, nearest_in_sets, refine_detections_batch, select_segmentation
 from .heads import classification_head, fpn_features, segmentation_head
-from .roi import mask_selection_gen_batch, nms_3d, points_cropping, seed_tensor
+from .roi import mask_selection_gen_batch, nms_3d, points_cropping, scene_seed_tensor, seed_tensor
 from .shape_proposal import shape_proposal_net
 from .spn_boxes import box_shrink
 from .tf_grouping import group_point
@@ -57,7 +57,7 @@ def _point_probabilities(pc, end_points):
 
 
 def rpointnet_inference(pc, color, pc_ins, group_label, group_indicator, seg_label, bbox_ins, config, is_training=False, bn_decay=None, *,
-                        geometry=None, valid_idx=None, seed=0, fused_crop=False):
+                        geometry=None, valid_idx=None, seed=0, fused_crop=False, scene_seeds=None):
     """:1064-1221 for mode='inference'.  pc, color (B, N, 3), pc_ins (B, NUM_GROUP, NUM_POINT_INS, 3), group_label, seg_label (B, N),
     group_indicator (B, NUM_GROUP), bbox_ins (B, NUM_GROUP, 6) -> end_points: shape_proposal_net's (with return_fullfea) plus
       group_label, seg_label, seg_label_per_group, bbox_ins                                                       (:1194-1197)
@@ -71,9 +71,13 @@ def rpointnet_inference(pc, color, pc_ins, group_label, group_indicator, seg_lab
     and the heads, as in the reference.  Extensions: geometry -- spn_geometry(pc, NUM_SAMPLE, 1024, True, points=color) -- and valid_idx
     -- valid_instances(group_indicator) -- as in shape_proposal_net; seed -- a Python int or a one-element int64 device tensor, the first
     crop draws with seed, the second with seed + 1 (added on the device); fused_crop -- the heads' first layer as crop_linear instead of
-    over the materialised crop (off until it is measured).
+    over the materialised crop (off until it is measured); scene_seeds -- a contiguous (B,) int64 device tensor, a seed per
+    scene: the first crop draws with scene_seeds, the second with scene_seeds + 1 (added on the device), seed is ignored, and a scene's
+    crops no longer depend on the batch it is run in or on its slot there (tester.py batches test scenes on this).
     Variables are created in the reference's order: shape_proposal_net/..., fpn1..fpn4, classification_head/..., segmentation_head/...."""
     from .rpointnet import gather_selection, seg_label_per_group
+    if scene_seeds is not None:
+        scene_seeds = scene_seed_tensor(scene_seeds, pc, "rpointnet_inference")
     with torch.no_grad():
         if not config.USE_COLOR:
             color = None
@@ -90,11 +94,15 @@ def rpointnet_inference(pc, color, pc_ins, group_label, group_indicator, seg_lab
         nroi_final = int(config.DETECTION_MAX_INSTANCES)
         npoint = int(config.NUM_POINT_INS_MASK)
         normalize = bool(config.NORMALIZE_CROP_REGION)
-        seed = seed_tensor(seed, pc.device)
+        if scene_seeds is None:
+            seed = seed_tensor(seed, pc.device)
+            seed_final, scene_seeds_final = seed + 1, None
+        else:
+            seed_final, scene_seeds_final = seed, scene_seeds + 1
         selected_indices = nms_3d(end_points['bbox_ins_pred'], end_points['fb_prob'][:, :, 1], config.SPN_PRE_NMS_LIMIT, m,
                                   config.SPN_IOU_THRESHOLD, config.SPN_SCORE_THRESHOLD)
         spn_rois = gather_selection(end_points['bbox_ins_pred'], selected_indices, m)
-        rois, mask_selection_idx = mask_selection_gen_batch(spn_rois, pc, m, config, True, seed)
+        rois, mask_selection_idx = mask_selection_gen_batch(spn_rois, pc, m, config, True, seed, scene_seeds)
 
         # features (:1129-1132) and the per-ROI probabilities (:1136-1150)
         fea = fpn_features(end_points, is_training, bn_decay)
@@ -123,7 +131,8 @@ def rpointnet_inference(pc, color, pc_ins, group_label, group_indicator, seg_lab
         detections = refine_detections_batch(rois, rpointnet_class, rpointnet_bbox, pc, fb_prob_cropped, sem_prob_cropped, config)
 
         # the second crop (:1172-1183) and the mask head (:1186-1191)
-        rois_final, mask_selection_idx_final = mask_selection_gen_batch(detections[:, :, :6], pc, nroi_final, config, False, seed + 1)
+        rois_final, mask_selection_idx_final = mask_selection_gen_batch(detections[:, :, :6], pc, nroi_final, config, False, seed_final,
+                                                                        scene_seeds_final)
         if fused_crop:
             crop = dict(pc=pc, pc_fea=fea, pc_center=center_pos, rois=rois_final, idx=mask_selection_idx_final, normalize=normalize)
             coord, head_fea = None, None

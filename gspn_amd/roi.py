@@ -8,7 +8,8 @@ The chain nms_3d -> gather_selection -> detection_target_gen_batch -> points_cro
 
 Random numbers come from the stateless generator gspn_roi_rand32 (include/gspn_hip.h).  `seed` is a one-element int64 tensor on the
 device, or a Python int (copied to the device, which a stream capture does not allow: pass a tensor there).  A captured step draws
-afresh on every replay once the caller has added to that tensor.  No CPU fallback."""
+afresh on every replay once the caller has added to that tensor.  The inference crops also take `scene_seeds`, a (B,) int64 device tensor
+with a seed per scene: a scene then draws what it draws alone, whichever batch and slot it is run in (tester.py).  No CPU fallback."""
 import torch
 
 from . import _lib as L
@@ -17,7 +18,7 @@ from .tf_grouping import group_point
 
 __all__ = ["nms_3d", "box_point_count", "sample_points_in_boxes", "detection_target_select", "detection_target_gen_batch",
            "detection_target_gen", "mask_selection_gen_batch", "mask_selection_gen", "points_cropping", "box_refinement", "apply_box_delta",
-           "seed_tensor"]
+           "seed_tensor", "scene_seed_tensor"]
 
 MASK_SELECTION_MARGIN = 1e-3          # :764-765
 
@@ -31,6 +32,21 @@ def seed_tensor(seed, device):
             raise L.GspnHipError("seed is on %s: gspn_amd runs on ROCm devices only (no CPU fallback)" % seed.device)
         return seed.contiguous()
     return torch.tensor([int(seed)], dtype=torch.int64, device=device)
+
+
+def scene_seed_tensor(scene_seeds, batched, what):
+    """the (B,) int64 device tensor the per-scene form of the crop sampler reads its seeds from, one per scene of `batched` (B, ...).
+    Checked before anything else, so that a tensor that does not fit raises ValueError wherever the others live."""
+    if not isinstance(scene_seeds, torch.Tensor):
+        raise TypeError("scene_seeds must be a torch.Tensor")
+    b = batched.shape[0] if isinstance(batched, torch.Tensor) and batched.dim() else 0
+    if scene_seeds.dtype != torch.int64 or scene_seeds.dim() != 1 or scene_seeds.shape[0] != int(b):
+        raise ValueError("%s: scene_seeds must be a (B,) = (%d,) int64 tensor, got %s %s" % (what, b, scene_seeds.dtype, tuple(scene_seeds.shape)))
+    if not scene_seeds.is_cuda:
+        raise L.GspnHipError("scene_seeds is on %s: gspn_amd runs on ROCm devices only (no CPU fallback)" % scene_seeds.device)
+    if not scene_seeds.is_contiguous():
+        raise ValueError("%s: scene_seeds must be contiguous" % what)
+    return scene_seeds.detach()
 
 
 def _boxes_and_points(boxes, pc, what):
@@ -69,17 +85,25 @@ def box_point_count(boxes, pc, margin=0.0):
     return out
 
 
-def sample_points_in_boxes(boxes, pc, nsmp, seed, margin=0.0):
+def sample_points_in_boxes(boxes, pc, nsmp, seed, margin=0.0, scene_seeds=None):
     """sample_points_within_box (:584-597) from the boxes themselves; the reference's (boxes, points) mask matrix is never built.
     boxes (B, R, 6), pc (B, N, 3) -> (B, R, nsmp) int32: nsmp draws with replacement, uniform over the points inside each box (the test of
-    box_point_count); a row of zeros for a box with no inside point and for an all-zero box.  N <= 32768."""
+    box_point_count); a row of zeros for a box with no inside point and for an all-zero box.  N <= 32768.
+    scene_seeds: None, or a contiguous (B,) int64 device tensor, one seed per scene (gspn_sample_points_in_boxes_seeds).  Row s is then
+    what this call gives for scene s alone with the one seed scene_seeds[s] -- whichever batch and slot the scene is run in -- and `seed`
+    is ignored."""
+    if scene_seeds is not None:
+        scene_seeds = scene_seed_tensor(scene_seeds, boxes, "sample_points_in_boxes")
     boxes, pc = _boxes_and_points(boxes, pc, "sample_points_in_boxes")
     b, r, _ = boxes.shape
-    seed = seed_tensor(seed, boxes.device)
+    if scene_seeds is None:
+        entry, seeds = L.lib().gspn_sample_points_in_boxes, seed_tensor(seed, boxes.device)
+    else:
+        entry, seeds = L.lib().gspn_sample_points_in_boxes_seeds, scene_seeds
     out = torch.empty((b, r, int(nsmp)), dtype=torch.int32, device=boxes.device)
     with torch.cuda.device(boxes.device):
-        L.check(L.lib().gspn_sample_points_in_boxes(b, r, pc.shape[1], int(nsmp), float(margin), L.ptr(seed), L.ptr(boxes), L.ptr(pc), L.ptr(out),
-                                                    L.stream()), "sample_points_in_boxes")
+        L.check(entry(b, r, pc.shape[1], int(nsmp), float(margin), L.ptr(seeds), L.ptr(boxes), L.ptr(pc), L.ptr(out), L.stream()),
+                "sample_points_in_boxes")
     return out
 
 
@@ -187,11 +211,14 @@ def detection_target_gen(proposals, gt_class_ids, gt_boxes, gt_masks, pc, config
     return rois[0], target_class_ids[0], target_bbox[0], idx[0], masks
 
 
-def mask_selection_gen_batch(proposals, pc, num_rois, config, empty_removal=True, seed=0):
+def mask_selection_gen_batch(proposals, pc, num_rois, config, empty_removal=True, seed=0, scene_seeds=None):
     """:749-783 for the whole batch.  proposals (B, S, 6) zero padded, pc (B, N, 3) -> rois (B, num_rois, 6), mask_selection_idx
     (B, num_rois, NUM_POINT_INS_MASK) int32.  The kept rows -- not all-zero and, with empty_removal, holding a point within the 1e-3
     margin -- move to the front in their original order (a prefix sum and a scatter on (B, S), no nonzero), then nsmp points are drawn
-    inside each with the same margin.  Rows past num_rois are dropped (the reference would return a longer tensor)."""
+    inside each with the same margin.  Rows past num_rois are dropped (the reference would return a longer tensor).
+    scene_seeds: as in sample_points_in_boxes -- a seed per scene, `seed` ignored."""
+    if scene_seeds is not None:
+        scene_seeds = scene_seed_tensor(scene_seeds, proposals, "mask_selection_gen")
     proposals, pc = _boxes_and_points(proposals, pc, "mask_selection_gen")
     b, s, _ = proposals.shape
     num_rois = int(num_rois)
@@ -205,7 +232,7 @@ def mask_selection_gen_batch(proposals, pc, num_rois, config, empty_removal=True
     if num_rois > s:
         src = torch.nn.functional.pad(src, (0, num_rois - s), value=-1)
     rois = _take_rows(proposals, src)
-    idx = sample_points_in_boxes(rois, pc, config.NUM_POINT_INS_MASK, seed, MASK_SELECTION_MARGIN)
+    idx = sample_points_in_boxes(rois, pc, config.NUM_POINT_INS_MASK, seed, MASK_SELECTION_MARGIN, scene_seeds)
     return rois, idx
 
 

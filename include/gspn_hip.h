@@ -53,7 +53,8 @@ extern "C" {
  *  21: gspn_dw_args / gspn_rsum_args; one gspn_mlp_bwd_data (gspn_mlp_bwd_data_cols / _dw / _dw2 / _ex removed); gspn_mlp_bwd_dw and
  *      gspn_mlp_bwd_data_pooltop take the two structs. */
 /* Additive at 21: gspn_segment_labels (+ _ws_bytes).  Nothing that was there changed, so the number stayed; a binder that wants the two and
- * finds an older library fails at the symbol lookup. */
+ * finds an older library fails at the symbol lookup.
+ * Additive at 21: gspn_sample_points_in_boxes_seeds (a seed per scene; gspn_sample_points_in_boxes keeps its draws bit for bit). */
 #define GSPN_ABI_VERSION 21
 int gspn_dist_policy(void);
 int gspn_abi_version(void);
@@ -328,6 +329,12 @@ int gspn_box_point_count(int b, int s, int n, float margin, const float* boxes, 
  * inside point and an all-zero box give a row of zeros.  n <= 32768. */
 int gspn_sample_points_in_boxes(int b, int r, int n, int nsmp, float margin, const long long* seed_dev, const float* boxes, const float* pc,
                                 int* idx_out, void* stream);
+/* The same with a seed per scene: seeds (b) i64 on the device, and draw j of box (scene, roi) uses gspn_roi_rand32(seeds[scene], 0, roi, j).
+ * Row `scene` is therefore what gspn_sample_points_in_boxes gives for that scene alone (b = 1) with the one seed seeds[scene]: a scene's
+ * draws do not depend on the batch it is run in or on its slot there (gspn_amd/tester.py batches test scenes on this).  Same kernel, same
+ * argument checks and limits. */
+int gspn_sample_points_in_boxes_seeds(int b, int r, int n, int nsmp, float margin, const long long* seeds, const float* boxes, const float* pc,
+                                      int* idx_out, void* stream);
 
 /* The decisions of detection_target_gen (:662-720) for a whole batch, one workgroup per scene.  proposals (b,s,6), count (b,s) i32 (of
  * gspn_box_point_count, margin 0), gt_cls (b,g) f32 (not read: the reference trims its ground truth by all-zero boxes alone, :664; the

@@ -1,0 +1,118 @@
+"""The reference's test.py on this library: its flags (test.py:23-29), gspn_amd.tester.Tester underneath.  From a checkpoint of
+tools/train.py and a validation cache to <out>/gt, <out>/pred (the ScanNet benchmark's layout) and the AP figures.
+
+The reference reads ScanNet meshes and labels through dataset.py's cache (test.py:40-44); here, as in tools/train.py:
+  --cache FILE       a torch.save'd dict of the six cache tensors of gspn_amd.train.DeviceDataset, as tools/make_cache.py writes it
+  --synthetic S      S scenes from gspn_amd.synth.spn_batch instead
+and, not in the reference:
+  --list FILE        one scan name per line, one per scene of the cache, the stems of the files written (test.py:42; default scene_%04d)
+  --out DIR          where gt/ and pred/ go [default: eva, test.py:210]
+  --batch_size B     scenes per step [default: 1, test.py:213]; a scene's predictions do not depend on it beyond the GEMMs' rounding
+  --test_sizes       the sizes models/config.py names for testing and never sets (its constructor assigns them to locals): NUM_SAMPLE 2048,
+                     SPN_PRE_NMS_LIMIT 1536, SPN_NMS_MAX_SIZE_INFERENCE 384, NUM_POINT_INS_MASK 1024.  Without it the run has the sizes the
+                     reference's test.py really runs with, the training ones.  --num_sample, when it is not the default, still wins.
+  --seed, --eager (no graph capture), --no_files (AP only, nothing written)
+
+    python tools/test.py --synthetic 5 --num_point 4096 --num_sample 64 --num_category 9 --batch_size 2 --model_path log/model.ckpt
+    python tools/test.py --cache val.pt --list scannet_val.txt --model_path log_heads/model.ckpt --batch_size 8
+"""
+import argparse
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from gspn_amd import synth  # noqa: E402
+from gspn_amd.rpointnet import Config  # noqa: E402
+
+CACHE_KEYS = ("pc", "color", "group_label", "seg_label", "pc_ins", "ngroup")
+
+
+def parser():
+    cfg = Config()
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument('--gpu', type=int, default=0, help='GPU to use [default: GPU 0]')
+    ap.add_argument('--num_point', type=int, default=cfg.NUM_POINT, help='Point Number in a Scene [default: 18000]')
+    ap.add_argument('--num_point_ins', type=int, default=cfg.NUM_POINT_INS, help='Point Number of an Instance [default: 512]')
+    ap.add_argument('--num_category', type=int, default=cfg.NUM_CATEGORY, help='Maximum Number of Categories [default: 19]')
+    ap.add_argument('--num_sample', type=int, default=cfg.NUM_SAMPLE, help='Number of Sampled Seed Points [default: 256]')
+    ap.add_argument('--model', default='model_rpointnet', help='Model name [default: model_rpointnet]')
+    ap.add_argument('--model_path', default='log/model.ckpt', help='model checkpoint file path [default: log/model.ckpt]')
+    # not in the reference
+    ap.add_argument('--cache', default=None, help='torch.save file of the six cache tensors of the scenes to test')
+    ap.add_argument('--synthetic', type=int, default=0, help='number of synthetic scenes to test on instead of --cache')
+    ap.add_argument('--num_group', type=int, default=12, help='groups per synthetic scene [default: 12]')
+    ap.add_argument('--list', default=None, help='file of scan names, one per scene [default: scene_%%04d]')
+    ap.add_argument('--out', default='eva', help='output directory [default: eva]')
+    ap.add_argument('--batch_size', type=int, default=1, help='scenes per step [default: 1]')
+    ap.add_argument('--restore_scope', default=None, help='restore only the variables under this scope')
+    ap.add_argument('--test_sizes', action='store_true', help="Config(istrain=False): the test sizes models/config.py names")
+    ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--eager', action='store_true', help='do not capture the step in a graph')
+    ap.add_argument('--no_files', action='store_true', help='write nothing, print the figures only')
+    return ap
+
+
+def parse(argv=None):
+    return parser().parse_args(argv)
+
+
+def load_cache(path):
+    d = torch.load(path, map_location="cpu")
+    missing = [k for k in CACHE_KEYS if k not in d]
+    if missing:
+        raise KeyError("%s: the cache lacks %s (it must hold %s)" % (path, missing, list(CACHE_KEYS)))
+    return {k: d[k] for k in CACHE_KEYS}
+
+
+def synthetic_cache(a):
+    d = synth.spn_batch("S", a.synthetic, a.num_point, a.num_group, a.num_point_ins, a.num_category, a.seed)
+    out = {k: torch.from_numpy(d[k]) for k in ("pc", "color", "group_label", "seg_label", "pc_ins")}
+    out["ngroup"] = torch.full((a.synthetic,), a.num_group, dtype=torch.int32)
+    return out
+
+
+def read_list(path):
+    with open(path) as f:
+        return [line.strip() for line in f if line.strip()]
+
+
+def config_of(a):
+    cfg = Config(istrain=not a.test_sizes)
+    if not a.test_sizes or a.num_sample != Config.NUM_SAMPLE:
+        cfg.NUM_SAMPLE = a.num_sample
+    cfg.NUM_CATEGORY = a.num_category
+    return cfg
+
+
+def main(argv=None):
+    a = parse(argv)
+    if (a.cache is None) == (a.synthetic <= 0):
+        raise SystemExit("give exactly one of --cache FILE and --synthetic S")
+    from gspn_amd.predict import SCANNET_LABEL_MAP
+    from gspn_amd.tester import Tester
+    from gspn_amd.train import DeviceDataset
+    if not 2 <= a.num_category <= len(SCANNET_LABEL_MAP):
+        raise SystemExit("--num_category must lie in [2, %d], the classes of the ScanNet label map" % len(SCANNET_LABEL_MAP))
+    dev = torch.device("cuda", a.gpu)
+    torch.cuda.set_device(dev)
+    cache = load_cache(a.cache) if a.cache else synthetic_cache(a)
+    data = DeviceDataset(*[cache[k].to(dev) for k in CACHE_KEYS], is_augment=False, permute_points=False)          # test.py:44
+    if data.pc.shape[1] != a.num_point or data.pc_ins.shape[2] != a.num_point_ins:
+        raise SystemExit("the cache holds %d points per scene and %d per instance, the flags say %d and %d"
+                         % (data.pc.shape[1], data.pc_ins.shape[2], a.num_point, a.num_point_ins))
+    scans = read_list(a.list) if a.list else None
+    if scans is not None and len(scans) != len(data):
+        raise SystemExit("%s names %d scans, the cache holds %d scenes" % (a.list, len(scans), len(data)))
+    tester = Tester(config_of(a), data, scans=scans, batch_size=a.batch_size, seed=a.seed, captured=not a.eager,
+                    label_map=SCANNET_LABEL_MAP[:a.num_category])
+    tester.restore(a.model_path, scope=a.restore_scope)
+    result = tester.run(out_dir=None if a.no_files else a.out, evaluate=True)
+    print("AP: %.3f  AP_50%%: %.3f  AP_25%%: %.3f  mean IoU: %.3f" % (result["all_ap"], result["all_ap_50%"], result["all_ap_25%"], result["iou"]))
+    return result
+
+
+if __name__ == "__main__":
+    main()

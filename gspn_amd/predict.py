@@ -221,9 +221,39 @@ def semantic_iou_counts(logits, labels, inter=None, union=None):
     return inter, union
 
 
+def _numpy_sum(v):
+    """The sum of a 1-D float64 tensor in the order np.add.reduce adds a contiguous vector (numpy's pairwise summation): below 8
+    elements one after the other; up to 128, eight running sums over strides of 8, combined as ((0 + 1) + (2 + 3)) + ((4 + 5) + (6 + 7)),
+    then the n % 8 last elements one after the other; above 128, the two halves (the first a multiple of 8) summed so and added.
+    Element-wise IEEE adds on slices: the same bits on the host and on the device, nothing read back, every shape static."""
+    n = v.shape[0]
+    if n < 8:
+        res = v[0]
+        for i in range(1, n):
+            res = res + v[i]
+        return res
+    if n <= 128:
+        r = v[:8]
+        for i in range(8, n - n % 8, 8):
+            r = r + v[i:i + 8]
+        res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]))
+        for i in range(n - n % 8, n):
+            res = res + v[i]
+        return res
+    half = n // 2
+    half -= half % 8
+    return _numpy_sum(v[:half]) + _numpy_sum(v[half:])
+
+
 def mean_iou(inter, union):
-    """train.py:385-386: mean(inter / (union + 1e-8)) in float64 (a class that never occurs contributes 0 / 1e-8 = 0) -> a 0-d tensor"""
-    return (inter.double() / (union.double() + 1e-8)).mean()
+    """train.py:385-386: mean(inter / (union + 1e-8)) in float64 (a class that never occurs contributes 0 / 1e-8 = 0) -> a 0-d tensor.
+    The quotients are added in np.mean's order (_numpy_sum) and the sum is divided, not multiplied by 1 / n, so the result is the
+    reference's double bit for bit; torch's own mean on the device is one step of a double away from it on some inputs
+    (tests/golden/predict/iou_ref.npz is one: sum * (1 / 18) is not sum / 18 there)."""
+    iou = inter.double() / (union.double() + 1e-8)
+    total = _numpy_sum(iou.reshape(-1))
+    # divided by a TENSOR: by a Python number torch's device kernel multiplies by the rounded reciprocal, which loses the last bit
+    return total / torch.full_like(total, float(iou.numel()))
 
 
 # ---- host IO (test.py:96-114, :128-129), plain Python ---------------------------------------------------------------------------------

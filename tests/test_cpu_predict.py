@@ -244,6 +244,12 @@ def test_mean_iou_matches_the_restatement():
     got = mean_iou(torch.from_numpy(inter), torch.from_numpy(union))
     # 18 non-negative quotients, each the same double in both; the two means may add them in another order: the bound of the sums, n = 18
     assert got.dtype == torch.float64 and PR.within_bound(np.float64(float(got)), PR.mean_iou(inter, union), 18)
+    # since golden/predict/iou_ref.npz: mean_iou adds in np.mean's order, so the double is the same one, at every length
+    assert float(got) == float(PR.mean_iou(inter, union))
+    for n in (1, 7, 8, 17, 127, 128, 129, 255):
+        i = rng.integers(0, 1000, n)
+        u = i + rng.integers(0, 1000, n)
+        assert float(mean_iou(torch.from_numpy(i), torch.from_numpy(u))) == float(PR.mean_iou(i, u)), n
     assert torch.equal(torch.from_numpy(inter).double() / (torch.from_numpy(union).double() + 1e-8), torch.from_numpy(inter / (union + 1e-8)))
     again = PR.iou_counts(logits, labels, 19, inter.copy(), union.copy())           # a second batch adds
     assert np.array_equal(again[0], 2 * inter) and np.array_equal(again[1], 2 * union)

@@ -387,3 +387,4 @@ def test_semantic_iou_counts_against_the_loop(rows, c):
     want = PR.iou_counts(*batches[1], c, want[0].copy(), want[1].copy())
     assert np.array_equal(inter.cpu().numpy(), want[0]) and np.array_equal(union.cpu().numpy(), want[1])
     assert PR.within_bound(np.float64(float(mean_iou(inter, union))), PR.mean_iou(want[0], want[1]), c - 1)
+    assert float(mean_iou(inter, union)) == float(PR.mean_iou(want[0], want[1]))     # np.mean's order of adding: the same double

@@ -55,7 +55,9 @@ def invalidate(idx):
 
 def inverse_lists(idx2d, n):
     """idx2d (b, L) int32 with values in [0, n) -> order (b, L) int32 (positions sorted by value, ties ascending), offsets (b, n+1) int32
-    -- a stable sort + searchsorted, done by gspn_inverse_lists (count / scan / fill in one workgroup per scene, then a per-value sort)."""
+    -- a stable sort + searchsorted, done by gspn_inverse_lists (count / scan / fill in one workgroup per scene, then a per-value sort).
+    Positions whose value lies outside [0, n) are dropped: offsets[:, n] counts the kept ones and order[s, offsets[s, n]:] is left
+    unwritten (torch.empty's content; include/gspn_hip.h, gspn_inverse_lists)."""
     idx2d = L.need(idx2d, torch.int32, 2, "idx")
     b, ln = idx2d.shape
     order = torch.empty((b, ln), dtype=torch.int32, device=idx2d.device)

@@ -370,7 +370,7 @@ class _MlpStack(torch.autograd.Function):
                 dW = _grad_buffer(lp.weights, b.sunk)
                 grads = [dW, dbias] + ([dbeta, dgamma] if lp.bn else []) + grads
                 wcin = int(b.lib.gspn_mlp_gather_cin(ctypes.byref(ctx.gargs))) if gather0 is not None else cin
-                work = torch.empty(int(b.lib.gspn_mlp_bwd_work_bytes(b.rows, wcin, cout)) // 4 + 4, dtype=torch.float32, device=dev)
+                work = torch.empty(int(b.lib.gspn_mlp_bwd_work_bytes(b.rows, wcin, cout)) // 4, dtype=torch.float32, device=dev)
                 has_dx = li > 0 or ctx.x_needs_grad
                 dx = _fused_attempt(b, li, a, known, dz, work, dW)
                 if dx is None:
@@ -614,7 +614,7 @@ def _preagg_backward(lib, pre, x, lp, a, rows, cout, need_dx, dev, st, sunk=None
     dwf = dW[pre["wf0"]:pre["wf0"] + c]
     dwf_now = None if ride else dwf
     wf = lp.weights[pre["wf0"]:pre["wf0"] + c]
-    work = torch.empty(int(lib.gspn_mlp_bwd_work_bytes(nsrc, c, cout)) // 4 + 4, dtype=torch.float32, device=dev)
+    work = torch.empty(int(lib.gspn_mlp_bwd_work_bytes(nsrc, c, cout)) // 4, dtype=torch.float32, device=dev)
     L.check(lib.gspn_mlp_bwd_wgrad_known(nsrc, c, cout, ctypes.byref(a2), L.ptr(x), x.shape[1], None, None, None, L.ptr(work),
                                          L.ptr(dwf_now), st), "mlp_bwd_wgrad_known(pre-aggregation)")
     dx = None
@@ -696,7 +696,7 @@ class _Linear(torch.autograd.Function):
         dbias = torch.empty(cout, dtype=torch.float32, device=dev)
         dx = None
         with torch.cuda.device(dev):
-            work = torch.empty(int(lib.gspn_mlp_bwd_work_bytes(rows, cin, cout)) // 4 + 4, dtype=torch.float32, device=dev)
+            work = torch.empty(int(lib.gspn_mlp_bwd_work_bytes(rows, cin, cout)) // 4, dtype=torch.float32, device=dev)
             L.check(lib.gspn_mlp_bwd_wgrad(rows, cin, cout, ctypes.byref(a), L.ptr(x), ld, None, None, None, None, None, BN_EPS, 0, 0,
                                            L.ptr(work), L.ptr(cA), L.ptr(cB), L.ptr(cC), None, None, L.ptr(dbias), L.ptr(dW), L.stream()), "mlp_bwd_wgrad")
             if ctx.needs_input_grad[0]:

@@ -59,7 +59,8 @@ def farthest_point_sample(npoint, inp, return_order=False):
     Non-differentiable (ops.NoGradient('FarthestPointSample')).
     return_order (extension): also return the spatial order the pre-pass sorted the scene into -- (batch, ndataset) int32, a
     permutation of the point indices in which neighbours in space sit together (16 cells), or None when the launch had no pre-pass.
-    three_nn(..., order=) runs markedly faster on it (geometry.py)."""
+    three_nn(..., order=) runs markedly faster on it (geometry.py).  The order of the points of one voxel is open (the pre-pass places
+    them with LDS atomics), so the permutation may differ from call to call there; the samples do not depend on it."""
     npoint = int(npoint)
     if npoint <= 0:
         raise ValueError("FarthestPointSample expects positive npoint")               # tf_sampling.cpp:99

@@ -79,7 +79,10 @@ int gspn_fps_cells(int b, int n, int m, int csz, const float* sxyz, const int* p
 long gspn_fps_cells_ws_bytes(int b, int n);
 int gspn_farthestpointsampling_cells(int b, int n, int m, const float* inp, void* ws, int* out, void* stream);
 /* The two halves of gspn_farthestpointsampling_cells on the same workspace: the spatial pre-pass (counting sort into 16 cells + rank
- * sort inside each cell) and the sampling kernel proper.  Calling them one after the other on one stream equals the combined call. */
+ * sort inside each cell) and the sampling kernel proper.  Calling them one after the other on one stream equals the combined call.
+ * The counting sort places the points of one 16^3 voxel with LDS atomics, so which of them fall on which side of a cell boundary is
+ * arbitrary: perm (the first b*n words of ws: sorted position -> original index) is a permutation of 0..n-1 per scene that may differ
+ * from call to call between points of one voxel.  `out` does not depend on it (the sampling kernel is exact for every assignment). */
 int gspn_fps_cells_prepass(int b, int n, const float* inp, void* ws, void* stream);
 /* the same, also leaving the scene's points in 16^3-voxel Morton order in vorder (b, n) int32 (original indices; arbitrary order inside
  * a voxel): a finer spatial order than the 16 cells of ws, for gspn_threenn_ordered. */
@@ -721,7 +724,9 @@ int gspn_mlp_bwd_wgrad_gather(long rows, const gspn_gather_args* g, int cout, co
 /* Inverse lists (CSR) of an index tensor -- what the gather-form gradients walk.  idx (b,L) int32 with values in [0,n):
  * order (b,L) = positions 0..L-1 grouped by value, ascending inside a group; offsets (b,n+1) = start of every group (offsets[n] = L).
  * Same result as a stable sort of idx + searchsorted.  work: gspn_inverse_lists_work_ints(b,L,n) ints.  Positions with a value
- * outside [0,n) are dropped.
+ * outside [0,n) are dropped: offsets[s][n] is then the number of positions of scene s that were kept, smaller than L, and the tail
+ * order[s][offsets[s][n] .. L) is NOT WRITTEN -- it keeps what the caller's buffer held.  Every consumer in this library walks order
+ * through offsets alone and never reads the tail; a caller that looks at it must fill it first.
  * (Extension: the reference scatters with atomicAdd -- tf_grouping_g.cu:78-86, tf_interpolate.cpp:119-143 -- and needs no such lists.) */
 long gspn_inverse_lists_work_ints(int b, int L, int n);
 int gspn_inverse_lists(int b, int L, int n, const int* idx, int* work, int* order, int* offsets, void* stream);

@@ -690,7 +690,7 @@ def test_fused_backward_entry_point_with_padded_pitches(cin, cout, pooled, with_
         dz = Zb[:, :cout].double()
     dXb = torch.full((rows, ldx), 7.0, device=dev)
     dW = torch.empty(cin, cout, device=dev)
-    work = torch.empty(int(lib.gspn_mlp_bwd_work_bytes(rows, cin, cout)) // 4 + 4, device=dev)
+    work = torch.empty(int(lib.gspn_mlp_bwd_work_bytes(rows, cin, cout)) // 4, device=dev)
     part = torch.empty(int(lib.gspn_rsum_part_floats(rows, cin)), device=dev) if with_part else None
     npart = ctypes.c_int(0)
     L.check(lib.gspn_mlp_bwd_fused(rows, cin, cout, ctypes.byref(a), L.ptr(W), L.ptr(Xb), ldxp, L.ptr(isc), L.ptr(ish), L.ptr(dXb), ldx, L.ptr(work),

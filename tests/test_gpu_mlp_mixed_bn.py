@@ -380,7 +380,7 @@ def test_bwd_data_four_forms_agree_and_carry_their_jobs(pooled):
         a.dZ, a.ldz, a.dPool, a.pool_arg, a.ns = Zb.data_ptr(), ldz, None, None, 0
         dz = Zb[:, :cout].double()
     st = L.stream()
-    work = torch.empty(int(lib.gspn_mlp_bwd_work_bytes(rows, cin, cout)) // 4 + 4, device=dev)
+    work = torch.empty(int(lib.gspn_mlp_bwd_work_bytes(rows, cin, cout)) // 4, device=dev)
     L.check(lib.gspn_mlp_bwd_wgrad(rows, cin, cout, ctypes.byref(a), L.ptr(Xb), ldxin, L.ptr(in_scale), L.ptr(in_shift), L.ptr(mean), L.ptr(var), L.ptr(gamma),
                                    eps, 1, 1, L.ptr(work), L.ptr(cA), L.ptr(cB), L.ptr(cC), None, None, None, None, st), "bwd_wgrad")
     dX, dW, part, npart = {}, {}, {}, {}

@@ -16,7 +16,7 @@ def run(rows, cin, cout, reps=10):
     a.scale, a.shift, a.cA, a.cB, a.cC = sc.data_ptr(), sh.data_ptr(), cA.data_ptr(), cB.data_ptr(), cC.data_ptr()
     psc, psh, pm, pv = one(cin), one(cin, 0.1), one(cin, 0.0), one(cin)
     part = torch.empty(int(lib.gspn_rsum_part_floats(rows, cin)), device=dev); npart = ctypes.c_int(0)
-    work = torch.empty(int(lib.gspn_mlp_bwd_work_bytes(rows, cin, cout)) // 4 + 4, device=dev)
+    work = torch.empty(int(lib.gspn_mlp_bwd_work_bytes(rows, cin, cout)) // 4, device=dev)
     f = lambda: L.check(lib.gspn_mlp_bwd_fused(rows, cin, cout, ctypes.byref(a), L.ptr(W), L.ptr(Yp), cin, L.ptr(psc), L.ptr(psh), L.ptr(dX), cin, L.ptr(work),
                                                L.ptr(dW), L.ptr(pm), L.ptr(pv), 1e-3, L.ptr(part), ctypes.byref(npart), L.stream()), "fused")
     for _ in range(3): f()

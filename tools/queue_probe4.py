@@ -45,7 +45,7 @@ cA = torch.ones(cout, device=dev); cB = torch.zeros(cout, device=dev); cC = torc
 a = L.DyArgs(); a.Y, a.ldy = Y.data_ptr(), cout
 a.dZ, a.ldz, a.dPool, a.pool_arg, a.ns = dZ.data_ptr(), cout, None, None, 0
 a.scale, a.shift, a.cA, a.cB, a.cC = scale.data_ptr(), shift.data_ptr(), cA.data_ptr(), cB.data_ptr(), cC.data_ptr()
-work = torch.empty(int(lib.gspn_mlp_bwd_work_bytes(rows, cin, cout)) // 4 + 4, device=dev)
+work = torch.empty(int(lib.gspn_mlp_bwd_work_bytes(rows, cin, cout)) // 4, device=dev)
 dW = torch.empty(cin, cout, device=dev); dX = torch.empty(rows, ldx, device=dev)
 stats = torch.empty(int(lib.gspn_mlp_fwd_stats_bytes(rows, cout)) // 4, device=dev)
 st = lambda: L.stream()

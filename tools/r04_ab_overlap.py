@@ -37,7 +37,7 @@ for (rows, cin, cout) in ((4096, 384, 256), (16384, 192, 128), (32768, 128, 128)
     a = L.DyArgs()
     a.Y, a.ldy, a.dZ, a.ldz, a.dPool, a.pool_arg, a.ns = Y.data_ptr(), cout, dZ.data_ptr(), cout, None, None, 0
     a.scale, a.shift, a.cA, a.cB, a.cC = (v.data_ptr() for v in vec[:5])
-    work = torch.empty(int(lib.gspn_mlp_bwd_work_bytes(rows, cin, cout)) // 4 + 4, device=dev)
+    work = torch.empty(int(lib.gspn_mlp_bwd_work_bytes(rows, cin, cout)) // 4, device=dev)
     dW = torch.empty(cin, cout, device=dev)
     dX = torch.empty(rows, cin, device=dev)
     s1, s2 = torch.cuda.Stream(dev), torch.cuda.Stream(dev)

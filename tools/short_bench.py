@@ -106,7 +106,7 @@ def run_wgrad():
             a.dZ, a.ldz, a.dPool, a.pool_arg, a.ns = dz.data_ptr(), cout, None, None, 0
         a.scale, a.shift = scale.data_ptr(), shift.data_ptr()
         a.cA, a.cB, a.cC = cA.data_ptr(), cB.data_ptr(), cC.data_ptr()
-        work = torch.empty(int(lib.gspn_mlp_bwd_work_bytes(rows, cin, cout)) // 4 + 4, device=dev)
+        work = torch.empty(int(lib.gspn_mlp_bwd_work_bytes(rows, cin, cout)) // 4, device=dev)
         dW = torch.empty(cin, cout, device=dev)
         def fn():
             L.check(lib.gspn_mlp_bwd_wgrad_known(rows, cin, cout, ctypes.byref(a), L.ptr(X), cin, L.ptr(sc), L.ptr(sh), None, L.ptr(work), L.ptr(dW), L.stream()), "wgrad_known")

@@ -21,7 +21,7 @@ def run(rows, cin, cout, ns, reps=10):
     sc, sh, cA, cB, cC = one(cout), one(cout, 0.1), one(cout), one(cout, 0.01), one(cout, 0.0)
     a.scale, a.shift, a.cA, a.cB, a.cC = sc.data_ptr(), sh.data_ptr(), cA.data_ptr(), cB.data_ptr(), cC.data_ptr()
     isc, ish = one(cin), one(cin, 0.1)
-    work = torch.empty(int(lib.gspn_mlp_bwd_work_bytes(rows, cin, cout)) // 4 + 4, device=dev)
+    work = torch.empty(int(lib.gspn_mlp_bwd_work_bytes(rows, cin, cout)) // 4, device=dev)
     dW = torch.empty(cin, cout, device=dev)
     f = lambda: L.check(lib.gspn_mlp_bwd_wgrad_known(rows, cin, cout, ctypes.byref(a), L.ptr(X), cin, L.ptr(isc), L.ptr(ish), None, L.ptr(work), L.ptr(dW), L.stream()), "wgrad")
     for _ in range(3): f()

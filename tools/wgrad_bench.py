@@ -26,7 +26,7 @@ for name, rows, ldx, cin, cout, pooled in shapes:
         dZ = torch.randn(rows, cout, device=dev); a.dZ, a.ldz, a.dPool, a.pool_arg, a.ns = dZ.data_ptr(), cout, None, None, 0
         dzb = rows * cout * 4
     a.scale, a.shift, a.cA, a.cB, a.cC = scale.data_ptr(), shift.data_ptr(), cA.data_ptr(), cB.data_ptr(), cC.data_ptr()
-    work = torch.empty(int(lib.gspn_mlp_bwd_work_bytes(rows, cin, cout)) // 4 + 4, device=dev)
+    work = torch.empty(int(lib.gspn_mlp_bwd_work_bytes(rows, cin, cout)) // 4, device=dev)
     dW = torch.empty(cin, cout, device=dev); dX = torch.empty(rows, ldx, device=dev)
     TR = int(__import__("os").environ.get("WB_TRAIN", "1"))
     def run_w():

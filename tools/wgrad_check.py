@@ -27,7 +27,7 @@ def run(rows, ldx, cin, cout, ns, act, training=1):
         dZ = torch.randn(rows, cout, device=dev); a.dZ, a.ldz, a.dPool, a.pool_arg, a.ns = dZ.data_ptr(), cout, None, None, 0
         dz = dZ.double()
     a.scale, a.shift, a.cA, a.cB, a.cC = scale.data_ptr(), shift.data_ptr(), cA.data_ptr(), cB.data_ptr(), cC.data_ptr()
-    nw = int(lib.gspn_mlp_bwd_work_bytes(rows, cin, cout)) // 4 + 4
+    nw = int(lib.gspn_mlp_bwd_work_bytes(rows, cin, cout)) // 4
     work = torch.empty(nw, device=dev)
     dW = torch.empty(cin, cout, device=dev); dg = torch.empty(cout, device=dev); db = torch.empty(cout, device=dev); dbias = torch.empty(cout, device=dev)
     L.check(lib.gspn_mlp_bwd_wgrad(rows, cin, cout, ctypes.byref(a), L.ptr(X), ldx, L.ptr(isc), L.ptr(ish), L.ptr(mean), L.ptr(var), L.ptr(gamma), eps, 1, training,

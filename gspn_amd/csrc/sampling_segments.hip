@@ -9,10 +9,10 @@
 //
 // The size c of an instance is known on the device alone and nothing is read back, so every launch covers all b*g instances and a
 // workgroup with nothing to do in it returns at once (before any barrier).  The size classes are the instantiations of the two on-chip
-// schemes of sampling.hip, restated here with the (order, c) indirection in their load phase -- sampling.hip is not touched, so the
-// kernels of gspn_farthestpointsampling compile to the code they had:
-//   fps_seg_small_rounds<C>           256 threads, c <= 512 C,  C = 1..4           (fps_small_kernel)
-//   fps_seg_resident_rounds<P, ZLDS>  1024 threads, c <= 1024 P, P = 4, 8, 16, 32  (fps_resident_kernel; z plane in LDS at P = 32)
+// round loops of fps_rounds.h, the very code fps_small_kernel and fps_resident_kernel (sampling.hip) run on a dense scene; here they read
+// their points through the point source Segment, whose index(k) is the clamped order[k], and that is the only difference:
+//   fps_small_rounds<C>           256 threads, c <= 512 C,  C = 1..4
+//   fps_resident_rounds<P, ZLDS>  1024 threads, c <= 1024 P, P = 4, 8, 16, 32  (z plane in LDS at P = 32)
 // Launches on one stream run one after the other, each for as long as its largest instance, so a launch per class costs the SUM of the
 // classes' m - 1 rounds: measured 2.40 ms at 2 x 18000, m = 512.  There is instead one launch per workgroup shape -- 256 threads;
 // 1024 threads; 1024 threads with the 129 KiB z plane -- and inside it the workgroup's own c selects the instantiation by a scalar branch
@@ -20,23 +20,25 @@
 // a launch no instance can be in (c > m and c <= n), and fps_seg_fill_kernel writes the rows that need no sampling: the background
 // (j = 0), empty groups, and c <= m (all members, then draws with replacement from gspn_roi_rand32).
 //
-// Inside the round loop a pick is stored as its position k, exactly as in sampling.hip; the look-up order[k] would put a global load on the
+// Inside the round loop a pick is stored as its position k, for a segment as for a dense scene; the look-up order[k] would put a global load on the
 // serial path of every round.  After the last round the whole workgroup translates the m picks in place and gathers their coordinates.
 // Every squared distance goes through dist2_cuda / dist2_cuda_v2 (GSPN_DIST_POLICY).
 #include <limits.h>
 
-#include "fps_common.h"
+#include "fps_rounds.h"
 #include "rand32.h"
 
 namespace {
 
-// the instance of workgroup blockIdx.x = scene * g + group
+// the instance of workgroup blockIdx.x = scene * g + group; a point source of the round loops (fps_rounds.h)
 struct Segment {
     const float* xyz;     // the scene's points
     const int* ord;       // L: c scene indices, ascending
     int c;
+    int n;                // points in the scene
     int* idx;             // m picks of this instance
     float* pts;           // m x 3
+    __device__ __forceinline__ int index(int k) const;      // seg_point
 };
 
 // c = 0 for a run that does not lie inside the scene's n positions (lists not built by gspn_inverse_lists): such a row is written as empty
@@ -49,6 +51,7 @@ __device__ __forceinline__ Segment seg_open(int n, int g, int m, const float* pc
     Segment sg;
     sg.xyz = pc + (size_t)s * n * 3;
     sg.ord = order + (size_t)s * n + (c > 0 ? base : 0);
+    sg.n = n;
     sg.c = __builtin_amdgcn_readfirstlane(c);          // the same for the whole workgroup: branches on it are scalar
     sg.idx = idx_out + (size_t)blockIdx.x * m;
     sg.pts = pts_out + (size_t)blockIdx.x * m * 3;
@@ -63,6 +66,7 @@ __device__ __forceinline__ int seg_point(const Segment& sg, int n, int k) {
     const int a = sg.ord[k];
     return a < 0 ? 0 : (a < n ? a : n - 1);
 }
+__device__ __forceinline__ int Segment::index(int k) const { return seg_point(*this, n, k); }
 // positions -> scene indices and coordinates, by the whole workgroup, after the last round
 __device__ __forceinline__ void seg_finish(const Segment& sg, int n, int m) {
     __syncthreads();                                        // thread 0's picks are visible to the workgroup
@@ -77,61 +81,6 @@ __device__ __forceinline__ void seg_finish(const Segment& sg, int n, int m) {
     }
 }
 
-// ---- c <= 2048: fps_small_kernel<C> of sampling.hip on a segment.  Thread t, slot p hold the position of tie rank q = t*2C + p, i.e.
-//      k = (q % C)*512 + q / C, so "lowest (wave, lane, slot)" is (k mod 512 asc, k asc).
-template <int C>
-__device__ __forceinline__ void fps_seg_small_rounds(const Segment& sg, int n, int m, int4 (*s_cand)[4], int (*s_k)[4]) {
-    constexpr int P = 2 * C;
-    const int c = sg.c;
-    const int t = threadIdx.x, lane = t & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-    const float* xyz = sg.xyz;
-    int* o = sg.idx;
-    float x[P], y[P], z[P], td[P];
-    int kk[P];
-#pragma unroll
-    for (int p = 0; p < P; ++p) {
-        const int q = t * P + p;
-        const int k = (q % C) * 512 + q / C;
-        const int a = seg_point(sg, n, k < c ? k : c - 1);
-        kk[p] = k;
-        x[p] = xyz[a * 3 + 0]; y[p] = xyz[a * 3 + 1]; z[p] = xyz[a * 3 + 2];
-        td[p] = k < c ? 1e38f : -1.0f;        // tf_sampling_g.cu:117-119; padding never wins (real candidates are >= 0)
-    }
-    if (t == 0) o[0] = 0;                      // :114-116
-    const int a0 = seg_point(sg, n, 0);
-    float cx = xyz[a0 * 3 + 0], cy = xyz[a0 * 3 + 1], cz = xyz[a0 * 3 + 2];
-    for (int j = 1; j < m; ++j) {
-        int best = NEG_ONE_BITS, bk = 0;
-        float bx = 0.f, by = 0.f, bz = 0.f;
-#pragma unroll
-        for (int p = 0; p < P; ++p) {
-            const float d = dist2_cuda(x[p] - cx, y[p] - cy, z[p] - cz);          // :139-142
-            td[p] = vmin_f32(d, td[p]);                                          // :143
-            const int v = __float_as_int(td[p]);
-            const bool up = v > best;                                             // strict: the lowest slot keeps a tie (:146-149)
-            best = up ? v : best;
-            bx = up ? x[p] : bx; by = up ? y[p] : by; bz = up ? z[p] : bz;
-            bk = up ? kk[p] : bk;
-        }
-        const int wmax = wave_max_i32(best);
-        const int lw = __builtin_ctzll(__ballot(best == wmax));                  // lowest lane on ties
-        const int buf = j & 1;
-        if (lane == lw) {
-            s_cand[buf][wave] = make_int4(wmax, __float_as_int(bx), __float_as_int(by), __float_as_int(bz));
-            s_k[buf][wave] = bk;
-        }
-        __syncthreads();
-        const int4 c0 = s_cand[buf][0], c1 = s_cand[buf][1], c2 = s_cand[buf][2], c3 = s_cand[buf][3];
-        int w = 0, mv = c0.x;
-        if (c1.x > mv) { mv = c1.x; w = 1; }                                      // lowest wave on ties
-        if (c2.x > mv) { mv = c2.x; w = 2; }
-        if (c3.x > mv) { mv = c3.x; w = 3; }
-        const int4 cw = w == 0 ? c0 : (w == 1 ? c1 : (w == 2 ? c2 : c3));
-        cx = __int_as_float(cw.y); cy = __int_as_float(cw.z); cz = __int_as_float(cw.w);
-        if (t == 0) o[j] = s_k[buf][w];                                          // :166-168
-    }
-}
 // one launch for the four classes: the workgroup's own c picks the instantiation (a wave-uniform branch on a scalar)
 __global__ __launch_bounds__(256) void fps_seg_small_kernel(int n, int g, int m, const float* __restrict__ pc, const int* __restrict__ order,
                                                             const int* __restrict__ offsets, int* idx_out, float* __restrict__ pts_out) {
@@ -139,153 +88,13 @@ __global__ __launch_bounds__(256) void fps_seg_small_kernel(int n, int g, int m,
     __shared__ int s_k[2][4];
     const Segment sg = seg_open(n, g, m, pc, order, offsets, idx_out, pts_out);
     if (!seg_samples(sg, g, m, 0, 2048)) return;
-    if (sg.c <= 512) fps_seg_small_rounds<1>(sg, n, m, s_cand, s_k);
-    else if (sg.c <= 1024) fps_seg_small_rounds<2>(sg, n, m, s_cand, s_k);
-    else if (sg.c <= 1536) fps_seg_small_rounds<3>(sg, n, m, s_cand, s_k);
-    else fps_seg_small_rounds<4>(sg, n, m, s_cand, s_k);
+    if (sg.c <= 512) fps_small_rounds<1>(sg, sg.idx, m, s_cand, s_k);
+    else if (sg.c <= 1024) fps_small_rounds<2>(sg, sg.idx, m, s_cand, s_k);
+    else if (sg.c <= 1536) fps_small_rounds<3>(sg, sg.idx, m, s_cand, s_k);
+    else fps_small_rounds<4>(sg, sg.idx, m, s_cand, s_k);
     seg_finish(sg, n, m);
 }
 
-// ---- c <= 32768: fps_resident_kernel<P, ZLDS> of sampling.hip on a segment (its header explains the scheme).  Thread t = 2*rho + half
-//      owns the positions k = (half*P + p)*512 + rho, so the reference tie order (d desc, k mod 512 asc, k asc) is (d desc, t asc, p asc).
-template <int P, bool ZLDS>
-__device__ __forceinline__ void fps_seg_resident_rounds(const Segment& sg, int n, int m, char* smem) {
-    // [0,512)    : candidates, 2 buffers x 16 waves x int4 {max bits, x, y, z}
-    // [512,640)  : candidate positions, 2 buffers x 16 waves x int
-    // [1024,..)  : z plane, float4 [P/4][1024]   (ZLDS only)
-    int4* s_cand = reinterpret_cast<int4*>(smem);
-    int* s_k = reinterpret_cast<int*>(smem + 512);
-    v4f* s_z = reinterpret_cast<v4f*>(smem + 1024);
-
-    constexpr int G = FpsGroup<P>::G;
-    constexpr int NG = FpsGroup<P>::NG;
-    static_assert(P % 2 == 0 && (!ZLDS || P % 4 == 0), "P must be even (multiple of 4 with ZLDS)");
-
-    const int c = sg.c;
-    const int t = threadIdx.x;
-    const int lane = t & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);     // provably wave-uniform (keeps loop state in SGPRs)
-    const int rho = t >> 1;                       // residue class k mod 512 of this thread
-    const int kbase = (t & 1) * P * 512 + rho;    // slot p holds position kbase + p*512
-    const float* xyz = sg.xyz;
-    int* o = sg.idx;
-
-    v2f x[P / 2], y[P / 2], z[ZLDS ? 1 : P / 2], td[P / 2];
-    // clamped, unconditional loads first (all in flight together), masking afterwards
-#pragma unroll
-    for (int p = 0; p < P; ++p) {
-        const int k = kbase + p * 512;
-        const int a = seg_point(sg, n, k < c ? k : c - 1);
-        float px = xyz[a * 3 + 0], py = xyz[a * 3 + 1], pz = xyz[a * 3 + 2];
-        const float d0 = k < c ? 1e38f : -1.0f;   // :117-119; padding never wins (real candidates are >= 0)
-        px = k < c ? px : 0.f; py = k < c ? py : 0.f; pz = k < c ? pz : 0.f;
-        // detach x/y/z from the dwordx3 load tuple so the allocator may place them independently
-        asm("" : "+v"(px), "+v"(py), "+v"(pz));
-        x[p >> 1][p & 1] = px;
-        y[p >> 1][p & 1] = py;
-        td[p >> 1][p & 1] = d0;
-        if (ZLDS) reinterpret_cast<float*>(s_z)[((p >> 2) * FPS_T + t) * 4 + (p & 3)] = pz;
-        else z[p >> 1][p & 1] = pz;
-    }
-    if (t == 0) o[0] = 0;                          // :114-116
-    const int a0 = seg_point(sg, n, 0);
-    float cx = xyz[a0 * 3 + 0], cy = xyz[a0 * 3 + 1], cz = xyz[a0 * 3 + 2];   // centre of round 1 = position 0
-    __syncthreads();
-
-    for (int j = 1; j < m; ++j) {
-        // ---- update min-dist + per-group maxima (value only) ----
-        int gmax[NG];
-#pragma unroll
-        for (int q = 0; q < NG; ++q) {
-            int gm = NEG_ONE_BITS;
-            v2f zhold = {0.f, 0.f};
-#pragma unroll
-            for (int h = 0; h < G / 2; ++h) {
-                const int pp = (q * G) / 2 + h;            // pair index
-                v2f zz;
-                if constexpr (ZLDS) {
-                    // one ds_read_b128 serves 4 consecutive slots; the empty asm keeps the compiler from narrowing it back into scalar LDS reads
-                    if ((h & 1) == 0) {
-                        v4f z4 = s_z[(pp >> 1) * FPS_T + t];
-                        asm("" : "+v"(z4));
-                        zz = z4.xy;
-                        zhold = z4.zw;
-                    } else {
-                        zz = zhold;
-                    }
-                } else {
-                    zz = z[pp];
-                }
-                const v2f dx = x[pp] - cx, dy = y[pp] - cy, dz = zz - cz;
-                const v2f d = dist2_cuda_v2(dx, dy, dz);                                   // contraction policy: fps_common.h, :142
-                td[pp][0] = vmin_f32(d[0], td[pp][0]);             // :143
-                td[pp][1] = vmin_f32(d[1], td[pp][1]);
-                gm = vmax3_i32(gm, __float_as_int(td[pp][0]), __float_as_int(td[pp][1]));
-            }
-            gmax[q] = gm;
-            __builtin_amdgcn_sched_barrier(0);   // keep the scheduler from interleaving groups (VGPR pressure)
-        }
-        int best = gmax[0];
-#pragma unroll
-        for (int q = 1; q < NG; ++q) best = max(best, gmax[q]);
-
-        // ---- wave arg-max: value -> lowest lane holding it -> lowest slot inside that lane ----
-        int qsel = NG - 1;                         // per lane: first group that holds the lane's best
-#pragma unroll
-        for (int q = NG - 2; q >= 0; --q) qsel = (gmax[q] == best) ? q : qsel;
-        const int wmax = wave_max_i32(best);
-        const int lw = __builtin_ctzll(__ballot(best == wmax));
-        const int qw = __builtin_amdgcn_readlane(qsel, lw);
-        int isel = G - 1;                          // per lane: first slot of group qw equal to the lane's best
-#pragma unroll
-        for (int q = 0; q < NG; ++q) {
-            if (qw == q) {                         // wave-uniform: static register indices inside
-#pragma unroll
-                for (int i = G - 2; i >= 0; --i) {
-                    const int p = q * G + i;
-                    isel = (__float_as_int(td[p >> 1][p & 1]) == best) ? i : isel;
-                }
-            }
-        }
-        const int iw = __builtin_amdgcn_readlane(isel, lw);
-        float fx = 0.f, fy = 0.f, fz = 0.f;
-#pragma unroll
-        for (int q = 0; q < NG; ++q) {
-            if (qw == q) {
-#pragma unroll
-                for (int i = 0; i < G; ++i) {
-                    if (iw == i) {
-                        const int p = q * G + i;
-                        fx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x[p >> 1][p & 1]), lw));
-                        fy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(y[p >> 1][p & 1]), lw));
-                        if (!ZLDS) fz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(z[ZLDS ? 0 : (p >> 1)][p & 1]), lw));
-                    }
-                }
-            }
-        }
-        const int fp = qw * G + iw;
-        const int tw = wave * 64 + lw;
-        if (ZLDS) fz = reinterpret_cast<const float*>(s_z)[((fp >> 2) * FPS_T + tw) * 4 + (fp & 3)];
-        const int buf = (j & 1) * FPS_W;
-        if (lane == 0) {
-            s_cand[buf + wave] = make_int4(wmax, __float_as_int(fx), __float_as_int(fy), __float_as_int(fz));
-            s_k[buf + wave] = ((tw & 1) * P + fp) * 512 + (tw >> 1);
-        }
-        __syncthreads();
-
-        // ---- workgroup arg-max: every wave reduces the 16 candidates redundantly (lowest wave wins ties)
-        const int4 cand = s_cand[buf + (lane & (FPS_W - 1))];
-        const int ck = s_k[buf + (lane & (FPS_W - 1))];
-        const int M = __builtin_amdgcn_readfirstlane(row_max_i32(cand.x));
-        const int wbest = __builtin_ctz((unsigned)(__ballot(cand.x == M) & 0xFFFFull));
-        cx = __int_as_float(__builtin_amdgcn_readlane(cand.y, wbest));
-        cy = __int_as_float(__builtin_amdgcn_readlane(cand.z, wbest));
-        cz = __int_as_float(__builtin_amdgcn_readlane(cand.w, wbest));
-        // cross-lane reads stay OUTSIDE the divergent store (a readlane sunk under `if (t == 0)` would let the compiler load s_k for lane 0 only)
-        const int kbest = __builtin_amdgcn_readlane(ck, wbest);
-        if (t == 0) o[j] = kbest;                                  // :166-168
-    }
-}
 // ZLDS = false: one launch for the classes c <= 4096 / 8192 / 16384, picked by the workgroup's own c; ZLDS = true: 16384 < c <= 32768 alone,
 // because its 129 KiB of LDS would otherwise be every workgroup's
 template <bool ZLDS>
@@ -295,11 +104,11 @@ __global__ __launch_bounds__(FPS_T) void fps_seg_resident_kernel(int n, int g, i
     const Segment sg = seg_open(n, g, m, pc, order, offsets, idx_out, pts_out);
     if (!seg_samples(sg, g, m, ZLDS ? 16384 : 2048, ZLDS ? 32768 : 16384)) return;
     if constexpr (ZLDS) {
-        fps_seg_resident_rounds<32, true>(sg, n, m, smem);
+        fps_resident_rounds<32, true>(sg, sg.idx, m, smem);
     } else {
-        if (sg.c <= 4096) fps_seg_resident_rounds<4, false>(sg, n, m, smem);
-        else if (sg.c <= 8192) fps_seg_resident_rounds<8, false>(sg, n, m, smem);
-        else fps_seg_resident_rounds<16, false>(sg, n, m, smem);
+        if (sg.c <= 4096) fps_resident_rounds<4, false>(sg, sg.idx, m, smem);
+        else if (sg.c <= 8192) fps_resident_rounds<8, false>(sg, sg.idx, m, smem);
+        else fps_resident_rounds<16, false>(sg, sg.idx, m, smem);
     }
     seg_finish(sg, n, m);
 }

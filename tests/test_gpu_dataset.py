@@ -1,6 +1,7 @@
 """GPU tests of gspn_amd/dataset.py on csrc/sampling_segments.hip: the segmented FPS equal to the CPU oracle run on every host-compacted
 instance, in every size class of the kernels and on a lattice where ties are everywhere; the padded rows equal to the documented draws;
-the same picks as the per-instance loop over farthest_point_sample; the error codes of the C entry point; the captured call; resample_scene
+the same picks as the per-instance loop over farthest_point_sample; the error codes of the C entry point; a segment that is the whole scene equal to
+the dense kernel, which runs the same round loop (csrc/fps_rounds.h), in every instantiation; the captured call; resample_scene
 and augment_and_box against the numpy restatement (tests/dataset_ref.py)."""
 import ctypes
 import functools
@@ -160,6 +161,59 @@ def test_abi_error_codes_and_the_empty_batch():
     want = DR.instance_sets(pc.cpu().numpy(), label.cpu().numpy(), g, m, 0)
     assert np.array_equal(idx.cpu().numpy(), want[0]) and np.array_equal(count.cpu().numpy(), want[2])
     assert np.array_equal(pts.cpu().numpy().view(np.int32), want[1].view(np.int32))
+
+
+# ---- 5b. one round loop, two callers: a segment that is the whole scene against the dense kernel ------------------------------------
+
+def tie_cloud(n):
+    """n points on the 1/8 lattice of [0, 2)^3 (distances exact in float32), a quarter of them exact duplicates of other points"""
+    rng = np.random.default_rng(n)
+    pc = (rng.integers(0, 16, (n, 3)) * 0.125).astype(np.float32)
+    dst = rng.permutation(n)[:n // 4]
+    pc[dst] = pc[rng.integers(0, n, n // 4)]
+    return pc
+
+
+def rounds_with_a_tied_maximum(pc, picks):
+    """replays the oracle's picks on exact coordinates: the rounds whose largest min-distance is held by more than one point"""
+    p = pc.astype(np.float64)
+    td = np.full(len(p), np.inf)
+    tied = 0
+    for j in range(1, len(picks)):
+        td = np.minimum(td, ((p - p[picks[j - 1]]) ** 2).sum(1))
+        assert td[picks[j]] == td.max() > 0
+        tied += int((td == td.max()).sum() > 1)
+    return tied
+
+
+# 300 ... 2048: fps_small C = 1, 2, 3, 4; 2049, 4097, 8193: fps_resident P = 4, 8, 16; 16385: P = 32 with the z plane in LDS
+@pytest.mark.parametrize("n,ties", [(300, False), (1024, False), (1536, False), (2048, False), (2049, False), (4097, False), (8193, False),
+                                    (16385, False), (1536, True), (4097, True)])
+def test_a_whole_scene_segment_equals_the_dense_kernel(n, ties):
+    from gspn_amd import _lib as L
+    from gspn_amd import synth
+    from oracle import oracle as O
+    lib = L.lib()
+    g, m = 2, 64
+    pc_np = tie_cloud(n) if ties else synth.cloud_d(n, n)
+    if ties:
+        want = O.farthest_point_sample(m, pc_np[None])[0]
+        assert rounds_with_a_tied_maximum(pc_np, want) >= 1
+    pc = torch.from_numpy(pc_np).cuda()[None].contiguous()
+    order = torch.arange(n, dtype=torch.int32, device="cuda")[None].contiguous()      # every label is 1: group 1 is the scene, in order
+    offsets = torch.tensor([[0, 0, n]], dtype=torch.int32, device="cuda")
+    idx = torch.full((1, g, m), -7, dtype=torch.int32, device="cuda")
+    pts = torch.full((1, g, m, 3), -7.0, dtype=torch.float32, device="cuda")
+    count = torch.full((1, g), -7, dtype=torch.int32, device="cuda")
+    dense = torch.full((1, m), -7, dtype=torch.int32, device="cuda")
+    assert lib.gspn_fps_segments(1, n, g, m, L.ptr(dev_seed(0)), L.ptr(pc), L.ptr(order), L.ptr(offsets), L.ptr(None), L.ptr(idx), L.ptr(pts),
+                                 L.ptr(count), L.stream()) == 0
+    assert lib.gspn_farthestpointsampling(1, n, m, L.ptr(pc), L.ptr(None), L.ptr(dense), L.stream()) == 0       # no workspace: small / resident
+    assert count.cpu().tolist() == [[0, n]]
+    assert torch.equal(idx[0, 1], dense[0])
+    assert torch.equal(pts[0, 1], pc[0][dense[0].long()])
+    if ties:
+        assert np.array_equal(dense[0].cpu().numpy(), want)
 
 
 # ---- 6. captured -------------------------------------------------------------------------------------------------------------------

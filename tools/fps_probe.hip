@@ -1,4 +1,5 @@
-// fps_probe: per-phase cycle breakdown of fps_resident_kernel (build with -DFPS_PROFILE)
+// fps_probe: wall time of gspn_farthestpointsampling without a workspace (n [m]), and with a third argument (cells per scene) the
+// per-phase cycle breakdown of fps_cell_kernel (build with -DFPS_PROFILE)
 #include "../gspn_amd/csrc/sampling.hip"
 #include <stdio.h>
 #include <stdlib.h>
@@ -71,19 +72,6 @@ int main(int argc, char** argv) {
         hipEventRecord(e1); hipDeviceSynchronize();
         float ms; hipEventElapsedTime(&ms, e0, e1);
         printf("n=%d m=%d rc=%d: %.3f ms = %.0f cyc/round @2.4GHz\n", n, m, rc, ms, ms * 2.4e6 / (m - 1));
-#ifdef FPS_PROFILE
-        long long p[8]; hipMemcpyFromSymbol(p, HIP_SYMBOL(g_fps_prof), sizeof(p));
-        for (int w = 0; w < 2; ++w)
-            printf("  wave %d cycles/round: update %.0f | wave-argmax+resolve %.0f | lds write+barrier %.0f | read cands+reduce %.0f\n", w * 7,
-                   p[w * 4 + 0] / (double)(m - 1), p[w * 4 + 1] / (double)(m - 1), p[w * 4 + 2] / (double)(m - 1), p[w * 4 + 3] / (double)(m - 1));
-#endif
     }
-#ifdef FPS_PROFILE
-    long long tl[128]; hipMemcpyFromSymbol(tl, HIP_SYMBOL(g_fps_tl), sizeof(tl));
-    long long t0 = tl[0];
-    for (int w = 0; w < 16; ++w) for (int i = 0; i < 4; ++i) if (tl[w * 8 + i] < t0) t0 = tl[w * 8 + i];
-    printf("round 100 timeline (cycles since first tick): wave: end-update end-resolve after-barrier end-reduce\n");
-    for (int w = 0; w < 16; ++w) printf("  w%02d: %6lld %6lld %6lld %6lld\n", w, tl[w*8]-t0, tl[w*8+1]-t0, tl[w*8+2]-t0, tl[w*8+3]-t0);
-#endif
     return 0;
 }

@@ -155,6 +155,7 @@ SIGNATURES = {
     "gspn_instance_overlaps": [_I, _I, _I, _I, _I] + [_P] * 8 + [_P],
     "gspn_instance_match": [_I, _I, _I, _I, _I, _I] + [_P] * 13 + [_P],
     "gspn_segment_labels": [_I, _I, _I] + [_P] * 6 + [_P],
+    "gspn_lift_masks": [_I] * 5 + [_P] * 8 + [_D] + [_P] * 5 + [_P],
 }
 
 # entry points that do not return an int status: symbol -> (argtypes, restype)
@@ -184,6 +185,7 @@ SPECIAL = {
     "gspn_tile_sum_part_floats": ([_L, _I, _I], _L),
     "gspn_fps_segments_ws_bytes": ([_I, _I, _I], _L),
     "gspn_segment_labels_ws_bytes": ([_I], _L),
+    "gspn_lift_part_doubles": ([_I, _I], _L),
 }
 
 ABI_VERSION = 21       # == GSPN_ABI_VERSION of include/gspn_hip.h this binding was written against

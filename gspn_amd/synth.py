@@ -38,6 +38,22 @@ def cloud_s(n, seed):
     return pts
 
 
+def scan_vertices(pc, seg_label, group_label, v, seed, jitter=0.01):
+    """A synthetic scan around one scene: pc (n, 3) f32, seg_label, group_label (n,) -> xyz (v, 3) f32, seg_label, group_label (v,) i32.
+    The first n rows are the scene as it is -- the network's scene is a subset of its scan's vertices, as in real data --, the other
+    v - n are seeded scene points moved by `jitter` * N(0, 1) per axis, which inherit their point's labels."""
+    pc = np.asarray(pc, np.float32)
+    n = pc.shape[0]
+    if pc.shape != (n, 3) or len(seg_label) != n or len(group_label) != n or v < n:
+        raise ValueError("scan_vertices: pc (n, 3) with n labels of each kind and v >= n expected, got %s, %d, %d and v = %d"
+                         % (pc.shape, len(seg_label), len(group_label), v))
+    rng = np.random.default_rng(7919 * int(seed) + 3)
+    parent = rng.integers(0, n, size=v - n)
+    moved = (pc[parent] + np.float32(jitter) * rng.standard_normal((v - n, 3)).astype(np.float32)).astype(np.float32)
+    at = np.concatenate((np.arange(n), parent))
+    return (np.concatenate((pc, moved)), np.asarray(seg_label)[at].astype(np.int32), np.asarray(group_label)[at].astype(np.int32))
+
+
 def batch(kind, b, n, seed0=0):
     f = {"U": cloud_u, "D": cloud_d, "S": cloud_s}[kind]
     return np.stack([f(n, seed0 + i) for i in range(b)]).astype(np.float32)

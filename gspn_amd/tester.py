@@ -23,6 +23,7 @@ from .train import DeviceDataset, restore_variables
 __all__ = ["Tester", "RESULT_FILE"]
 
 RESULT_FILE = "semantic_instance_evaluation.txt"          # test.py:222
+_LIFT_KEYS = ("detections", "rpointnet_mask_selected", "pc_coord_cropped_final_unnormalized", "pc_seed", "fb_prob", "sem_class_logits")
 
 
 class _Capture:
@@ -103,7 +104,8 @@ class Tester:
 
     def _step(self, geo, valid):
         """the buffers -> {'pred': scene_predictions', 'ap_counts': instance_match's with the rows' classes and confidences,
-        'iou_inter', 'iou_union' (B, C - 1) int64: the semantic IoU counts of each slot}"""
+        'iou_inter', 'iou_union' (B, C - 1) int64: the semantic IoU counts of each slot, 'lift': the six tensors of the batch that
+        lift.scan_predictions reads}"""
         from .inference import rpointnet_inference
         u, cfg = self.buf, self.cfg
         tf_util.set_variable_store(self.store)
@@ -121,8 +123,10 @@ class Tester:
             # per slot, so that the filled slots of a short batch can be left out (train.py:365-368 on the whole scene's points)
             logits = ep["sem_class_logits"]
             per_slot = [semantic_iou_counts(logits[s], u["seg_label"][s]) for s in range(self.b)]
+            # what lift.scan_predictions reads of a batch, as the step leaves it: run_vertices lifts each scene behind the step
+            lift = {k: ep[k] for k in _LIFT_KEYS}
             return {"pred": pred, "ap_counts": counts, "iou_inter": torch.stack([p[0] for p in per_slot]),
-                    "iou_union": torch.stack([p[1] for p in per_slot])}
+                    "iou_union": torch.stack([p[1] for p in per_slot]), "lift": lift}
 
     def _capture(self, valid):
         from .graph import CapturedStep
@@ -150,10 +154,8 @@ class Tester:
         print('RESTORE MODEL FROM ' + str(path), flush=True)
         return ckpt
 
-    def predict(self, idx):
-        """idx: 1 to batch_size scene numbers -> (pred, batch), clones cut to len(idx) scenes.  pred: scene_predictions' dict.  batch: the
-        ten tensors of DeviceDataset.batch plus 'ap_counts' (what InstanceAP.add_counts takes) and 'iou_inter', 'iou_union'
-        (len(idx), C - 1) int64, the semantic IoU counts of each scene."""
+    def _outputs(self, idx):
+        """the step on the scenes idx -> _step's dict itself, not cloned: it holds until the next step"""
         from .graph import copy_into
         slots = self._assemble(idx)
         geo, valid = self._geometry(), self._valid_index(slots)
@@ -168,6 +170,13 @@ class Tester:
             out = cap.out
         else:
             out = self._step(geo, valid)
+        return out
+
+    def predict(self, idx):
+        """idx: 1 to batch_size scene numbers -> (pred, batch), clones cut to len(idx) scenes.  pred: scene_predictions' dict.  batch: the
+        ten tensors of DeviceDataset.batch plus 'ap_counts' (what InstanceAP.add_counts takes) and 'iou_inter', 'iou_union'
+        (len(idx), C - 1) int64, the semantic IoU counts of each scene."""
+        out = self._outputs(idx)
         k = len(idx)
         cut = lambda t: t[:k].clone()
         batch = {name: cut(t) for name, t in self.buf.items()}
@@ -199,6 +208,55 @@ class Tester:
                 for s, k in enumerate(idx):
                     write_ground_truth(gt_dir, self.scans[k], batch["seg_label"][s], batch["group_label"][s], self.label_map)
                     write_predictions(pred_dir, self.scans[k], pred, s)
+        if not evaluate:
+            return None
+        result = metric.compute()
+        result["iou"] = float(mean_iou(inter, union))
+        if out_dir is not None:
+            write_result_file(os.path.join(pred_dir, RESULT_FILE), result)
+        return result
+
+    def run_vertices(self, out_dir, vertices, evaluate=True):
+        """run() at the resolution of each scan's own mesh.  vertices(k) -> {'xyz': (V, 3) float32} for scene k, the scan's
+        vertices in the coordinates of the scene's points, and, for the ground truth and the evaluation, 'seg_label' and 'group_label'
+        (V,) int32 in the cache's numbering (classes 0..C-1, groups from 0); numpy arrays or tensors.  The scenes run batched through
+        the same step as run(); behind it lift.scan_predictions runs eagerly once per scan, V differing from scan to scan.  out_dir:
+        <out_dir>/pred_vertices/<scan>.txt with pred_mask/, one line per vertex in every mask, and, where vertices(k) has labels,
+        <out_dir>/gt_vertices/<scan>.txt.  evaluate: AP per scan through InstanceAP at B = 1 and the semantic IoU counts of
+        sem_class_logits[src] against the vertices' labels -> run()'s dict, also written to <out_dir>/pred_vertices/
+        semantic_instance_evaluation.txt; evaluate=False -> None.  run()'s own outputs and every variable are left as they are."""
+        from .lift import scan_predictions
+        metric = InstanceAP(int(self.cfg.NUM_CATEGORY), label_map=self.label_map) if evaluate else None
+        c = int(self.cfg.NUM_CATEGORY)
+        inter = torch.zeros(c - 1, dtype=torch.int64, device=self.dev)
+        union = torch.zeros(c - 1, dtype=torch.int64, device=self.dev)
+        if out_dir is not None:
+            gt_dir, pred_dir = os.path.join(out_dir, "gt_vertices"), os.path.join(out_dir, "pred_vertices")
+            os.makedirs(gt_dir, exist_ok=True)
+            os.makedirs(pred_dir, exist_ok=True)
+        for lo in range(0, len(self.data), self.b):
+            idx = list(range(lo, min(lo + self.b, len(self.data))))
+            out = self._outputs(idx)
+            for s, k in enumerate(idx):
+                scan = vertices(k)
+                xyz = torch.as_tensor(scan["xyz"]).to(self.dev)
+                pred = scan_predictions(out["lift"], s, xyz, pc=self.buf["pc"], label_map=self.label_map, **self.thresholds)
+                labelled = "seg_label" in scan and "group_label" in scan
+                if evaluate and not labelled:
+                    raise ValueError("Tester.run_vertices: vertices(%d) has no 'seg_label' and 'group_label' to evaluate against" % k)
+                if labelled:
+                    seg = torch.as_tensor(scan["seg_label"]).to(self.dev).int().contiguous()
+                    group = torch.as_tensor(scan["group_label"]).to(self.dev).int().contiguous()
+                    if tuple(seg.shape) != (xyz.shape[0],) or tuple(group.shape) != (xyz.shape[0],):
+                        raise ValueError("Tester.run_vertices: vertices(%d) must label each of its %d vertices, got %s and %s"
+                                         % (k, xyz.shape[0], tuple(seg.shape), tuple(group.shape)))
+                if evaluate:
+                    metric.add_predictions(pred, seg.unsqueeze(0), group.unsqueeze(0), max(int(group.max()), 0) + 1)
+                    semantic_iou_counts(out["lift"]["sem_class_logits"][s][pred["src"].long()], seg, inter, union)
+                if out_dir is not None:
+                    if labelled:
+                        write_ground_truth(gt_dir, self.scans[k], seg, group, self.label_map)
+                    write_predictions(pred_dir, self.scans[k], pred, 0)
         if not evaluate:
             return None
         result = metric.compute()

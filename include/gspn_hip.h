@@ -54,7 +54,8 @@ extern "C" {
  *      gspn_mlp_bwd_data_pooltop take the two structs. */
 /* Additive at 21: gspn_segment_labels (+ _ws_bytes).  Nothing that was there changed, so the number stayed; a binder that wants the two and
  * finds an older library fails at the symbol lookup.
- * Additive at 21: gspn_sample_points_in_boxes_seeds (a seed per scene; gspn_sample_points_in_boxes keeps its draws bit for bit). */
+ * Additive at 21: gspn_sample_points_in_boxes_seeds (a seed per scene; gspn_sample_points_in_boxes keeps its draws bit for bit).
+ * Additive at 21: gspn_lift_masks (+ gspn_lift_part_doubles): predictions on a scan's own vertices. */
 #define GSPN_ABI_VERSION 21
 int gspn_dist_policy(void);
 int gspn_abi_version(void);
@@ -811,6 +812,32 @@ int gspn_instance_match(int b, int r, int c, int g, int t, int min_region, const
 int gspn_segment_labels(int n, int p, int s, const int* seg_indices, const int* pair_segment, const int* pair_object, void* ws, int* out_label,
                         int* out_conflicts, void* stream);
 long gspn_segment_labels_ws_bytes(int s);
+
+/* ---------------- predictions on a scan's own vertices (gspn_amd/csrc/lift.hip, additive at ABI 21) ---------------------- */
+
+/* test.py:163-189 and :204 with a vertex of the scan in the place of a scene point, for ONE scan: gspn_nearest_in_sets behind the boxes and
+ * gspn_scene_confidence in one pass that never writes the (r,v) index tensor.  verts (v,3) f32; crops (r,p,3) f32: the crop points of each
+ * detection; boxes (r,6) f32 (centre, size); masks (r,p) f32; class_ids (r) i32; src (v) i32: the scene point each vertex takes its
+ * semantic row from, a value outside [0, n) clamped into it; sem_prob (n,c) f32; vert_fb (v) f32; mask_th a double.
+ * For detection k and vertex i:  g = masks[k][j], j the crop point of k nearest to the vertex by the unfused fp32 (dx*dx + dy*dy) + dz*dz,
+ * the smallest j among equal distances, if the vertex is inside box k (x >= c - s/2 && x <= c + s/2 on every axis, bounds included; a NaN
+ * coordinate is inside nothing); g = 0 otherwise.  In double, every float operand widened before the product:
+ *   S0 = sum g,  S1 = sum g * sem_prob[src[i], class_k],  S2 = sum g * vert_fb[i];  sem_conf = S1 / (1e-8 + S0),  fb_conf = S2 / (1e-8 + S0)
+ *   mask[k][i] = (double)g > mask_th  (u8, 0 or 1; every byte is written);  mask_points = the number of set bytes of the row.
+ * A row whose class is outside [1, c) writes zeros to all four outputs.  A vertex outside the box reads neither masks nor the tables.
+ * One workgroup per (detection, tile of 256 or 1024 vertices -- 1024 once r * ceil(v / 1024) >= 512) leaves (S0, S1, S2, set bytes) in its
+ * own slot of part; one wave per detection adds the slots in ascending order.  The order of the additions depends on (r, v) alone (no
+ * atomics): the same bits on every call.  part: gspn_lift_part_doubles(r, v) doubles (0 for sizes the call declines), 8-byte aligned; it
+ * need not be initialised and nothing is read from it that this call did not write.  sem_conf, fb_conf (r) f64; mask (r,v) u8;
+ * mask_points (r) i32.  Row offsets are 64-bit: r * v may exceed 2^31.  GSPN_ERR_ARG for a size <= 0, a null pointer or a NaN threshold;
+ * GSPN_ERR_UNSUPPORTED for p > GSPN_LIFT_MAX_P, r > 65535 or v > GSPN_LIFT_MAX_V, all before anything is launched.  No host
+ * synchronisation, nothing allocated, static shapes. */
+#define GSPN_LIFT_MAX_P 4096
+#define GSPN_LIFT_MAX_V (1 << 24)
+long gspn_lift_part_doubles(int r, int v);
+int gspn_lift_masks(int r, int v, int p, int n, int c, const float* verts, const float* crops, const float* boxes, const float* masks,
+                    const int* class_ids, const int* src, const float* sem_prob, const float* vert_fb, double mask_th, double* part,
+                    double* sem_conf, double* fb_conf, unsigned char* mask, int* mask_points, void* stream);
 
 /* ---------------- train.py: the per-step batch, the reference's optimisers, the running loss sums (gspn_amd/csrc/train.hip, ABI 20) -------
  *

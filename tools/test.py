@@ -12,9 +12,18 @@ and, not in the reference:
                      SPN_PRE_NMS_LIMIT 1536, SPN_NMS_MAX_SIZE_INFERENCE 384, NUM_POINT_INS_MASK 1024.  Without it the run has the sizes the
                      reference's test.py really runs with, the training ones.  --num_sample, when it is not the default, still wins.
   --seed, --eager (no graph capture), --no_files (AP only, nothing written)
+and, for predictions at the resolution of each scan's own mesh (Tester.run_vertices, DESIGN.md 4.21: one mask value per vertex, the
+ScanNet benchmark's format, into <out>/pred_vertices and <out>/gt_vertices, with AP and mean IoU per vertex):
+  --mesh_path DIR    ScanNet's layout as tools/data_prep.py reads it, DIR/<scan>/<scan>_vh_clean_2.ply, the scans named by --list
+  --label_path DIR   optional: the vertices' ground truth, DIR/<scan>/ as data_prep.collect_label reads it, through dataset.remap_labels;
+                     without it the masks are written and nothing is evaluated
+  --synthetic_vertices V   with --synthetic: each scene's scan is its N points followed by V - N jittered copies of seeded scene points
+                     that inherit their labels
 
     python tools/test.py --synthetic 5 --num_point 4096 --num_sample 64 --num_category 9 --batch_size 2 --model_path log/model.ckpt
     python tools/test.py --cache val.pt --list scannet_val.txt --model_path log_heads/model.ckpt --batch_size 8
+    python tools/test.py --cache val.pt --list scannet_val.txt --model_path log_heads/model.ckpt --batch_size 8 \\
+        --mesh_path scannet/mesh/scans --label_path scannet/label/scans
 """
 import argparse
 import os
@@ -52,6 +61,9 @@ def parser():
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--eager', action='store_true', help='do not capture the step in a graph')
     ap.add_argument('--no_files', action='store_true', help='write nothing, print the figures only')
+    ap.add_argument('--mesh_path', default=None, help='directory of <scan>/<scan>_vh_clean_2.ply: predict on every vertex of each scan of --list')
+    ap.add_argument('--label_path', default=None, help="directory of the scans' label files: the vertices' ground truth (with --mesh_path)")
+    ap.add_argument('--synthetic_vertices', type=int, default=0, help='vertices of the synthetic scan around each synthetic scene')
     return ap
 
 
@@ -74,6 +86,31 @@ def synthetic_cache(a):
     return out
 
 
+def synthetic_vertices(cache, v, seed):
+    """vertices(k) of Tester.run_vertices for the scenes of synthetic_cache: synth.scan_vertices around scene k, seeded with seed + k"""
+    def vertices(k):
+        xyz, seg, group = synth.scan_vertices(cache["pc"][k].numpy(), cache["seg_label"][k].numpy(), cache["group_label"][k].numpy(), v, seed + k)
+        return {"xyz": xyz, "seg_label": seg, "group_label": group}
+    return vertices
+
+
+def mesh_vertices(mesh_path, label_path, scans, device):
+    """vertices(k) of Tester.run_vertices from ScanNet's files: the vertices of <mesh_path>/<scan>/<scan>_vh_clean_2.ply as
+    tools/data_prep.py reads them and, with a label_path, their labels through data_prep.collect_label and dataset.remap_labels"""
+    import numpy as np
+    from gspn_amd import data_prep, dataset, io_util
+
+    def vertices(k):
+        scan = scans[k]
+        out = {"xyz": np.ascontiguousarray(io_util.read_color_ply(os.path.join(mesh_path, scan, scan + "_vh_clean_2.ply"))[:, :3], np.float32)}
+        if label_path:
+            sem, ins, _ = data_prep.collect_label(label_path, scan, device=device)
+            group, seg, _ = dataset.remap_labels(ins.unsqueeze(0), sem.unsqueeze(0), max(int(ins.max()), 0) + 1)
+            out["seg_label"], out["group_label"] = seg[0].int(), group[0].int()
+        return out
+    return vertices
+
+
 def read_list(path):
     with open(path) as f:
         return [line.strip() for line in f if line.strip()]
@@ -94,6 +131,14 @@ def main(argv=None):
     from gspn_amd.predict import SCANNET_LABEL_MAP
     from gspn_amd.tester import Tester
     from gspn_amd.train import DeviceDataset
+    if a.mesh_path and a.synthetic_vertices:
+        raise SystemExit("give at most one of --mesh_path DIR and --synthetic_vertices V")
+    if a.mesh_path and not a.list:
+        raise SystemExit("--mesh_path needs --list FILE: the scans whose meshes to read")
+    if a.label_path and not a.mesh_path:
+        raise SystemExit("--label_path goes with --mesh_path")
+    if a.synthetic_vertices and (a.synthetic <= 0 or a.synthetic_vertices < a.num_point):
+        raise SystemExit("--synthetic_vertices V goes with --synthetic S and V >= --num_point")
     if not 2 <= a.num_category <= len(SCANNET_LABEL_MAP):
         raise SystemExit("--num_category must lie in [2, %d], the classes of the ScanNet label map" % len(SCANNET_LABEL_MAP))
     dev = torch.device("cuda", a.gpu)
@@ -109,7 +154,15 @@ def main(argv=None):
     tester = Tester(config_of(a), data, scans=scans, batch_size=a.batch_size, seed=a.seed, captured=not a.eager,
                     label_map=SCANNET_LABEL_MAP[:a.num_category])
     tester.restore(a.model_path, scope=a.restore_scope)
-    result = tester.run(out_dir=None if a.no_files else a.out, evaluate=True)
+    if a.mesh_path or a.synthetic_vertices:
+        vertices = (mesh_vertices(a.mesh_path, a.label_path, scans, dev) if a.mesh_path
+                    else synthetic_vertices(cache, a.synthetic_vertices, a.seed))
+        result = tester.run_vertices(None if a.no_files else a.out, vertices, evaluate=bool(a.synthetic_vertices or a.label_path))
+        if result is None:
+            print("per-vertex masks written to %s (no --label_path: nothing to evaluate against)" % os.path.join(a.out, "pred_vertices"))
+            return None
+    else:
+        result = tester.run(out_dir=None if a.no_files else a.out, evaluate=True)
     print("AP: %.3f  AP_50%%: %.3f  AP_25%%: %.3f  mean IoU: %.3f" % (result["all_ap"], result["all_ap_50%"], result["all_ap_25%"], result["iou"]))
     return result
 

@@ -156,6 +156,7 @@ SIGNATURES = {
     "gspn_instance_match": [_I, _I, _I, _I, _I, _I] + [_P] * 13 + [_P],
     "gspn_segment_labels": [_I, _I, _I] + [_P] * 6 + [_P],
     "gspn_lift_masks": [_I] * 5 + [_P] * 8 + [_D] + [_P] * 5 + [_P],
+    "gspn_nearest_point": [_I, _I, _I, _P, _P, _P, _P, _P, _P],
 }
 
 # entry points that do not return an int status: symbol -> (argtypes, restype)
@@ -186,6 +187,7 @@ SPECIAL = {
     "gspn_fps_segments_ws_bytes": ([_I, _I, _I], _L),
     "gspn_segment_labels_ws_bytes": ([_I], _L),
     "gspn_lift_part_doubles": ([_I, _I], _L),
+    "gspn_nearest_point_ws_bytes": ([_I, _I], _L),
 }
 
 ABI_VERSION = 21       # == GSPN_ABI_VERSION of include/gspn_hip.h this binding was written against

@@ -8,20 +8,25 @@ nearest crop point of a detection behind the box test, the nearest seed, the sum
 takes the semantic softmax row of the scene point nearest to it (src), the first minimum of the unfused fp32 (dx*dx + dy*dy) + dz*dz.
 When the vertices are the scene's own, pairwise distinct points, src is the identity and scan_predictions reproduces scene_predictions.
 
-vertex_tables is the first column of three_nn against the scene's points and against the seeds; gspn_lift_masks (csrc/lift.hip) fuses
+vertex_tables is the nearest scene point and the nearest seed of every vertex -- nearest_point (nearest.py) for a known
+set of more than NEAREST_FROM_M points, the first column of three_nn below; the two agree bit for bit --; gspn_lift_masks (csrc/lift.hip) fuses
 nearest_in_sets and scene_confidence and never writes the (R, V) index tensor; gspn_scene_rank orders the rows as it does for a scene.
 V differs from scan to scan, so nothing here is meant for a captured step.  No CPU fallback."""
 import torch
 
 from . import _lib as L
+from .nearest import nearest_point
 from .predict import SCANNET_LABEL_MAP, SCENE_RANK_MAX_R, _on_device, _typed, scene_rank
 from .tf_interpolate import three_nn
 
-__all__ = ["LIFT_MAX_P", "LIFT_MAX_V", "lift_tile", "vertex_tables", "lift_masks", "scan_predictions"]
+__all__ = ["LIFT_MAX_P", "LIFT_MAX_V", "NEAREST_FROM_M", "lift_tile", "vertex_tables", "lift_masks", "scan_predictions"]
 
 LIFT_MAX_P = 4096             # GSPN_LIFT_MAX_P of include/gspn_hip.h: a detection's crop points sit in LDS
 LIFT_MAX_V = 1 << 24          # GSPN_LIFT_MAX_V
 LIFT_MAX_R = 65535            # the detections are the grid's second dimension
+NEAREST_FROM_M = 1024         # vertex_tables: a known set of more points than this goes to nearest_point; at or below it three_nn's one-wave
+                              # kernel is the faster form up to 150 000 vertices (measured: DESIGN.md 4.22, profiles/nearest_stage.txt)
+_SEARCHES = (None, "three_nn", "nearest_point")
 
 
 def lift_tile(r, v):
@@ -29,10 +34,19 @@ def lift_tile(r, v):
     return 1024 if int(r) * ((int(v) + 1023) // 1024) >= 512 else 256
 
 
-def vertex_tables(verts, pc, pc_seed, fb_prob):
+def _nearest_index(verts, known, search):
+    """(V, 3) against (M, 3), both on the device -> (V,) int32: the first minimum, by the search that `search` names or the size picks"""
+    if search == "nearest_point" or (search is None and known.shape[0] > NEAREST_FROM_M):
+        return nearest_point(verts.unsqueeze(0), known.unsqueeze(0))[1][0]
+    return three_nn(verts.unsqueeze(0), known.unsqueeze(0))[1][0, :, 0].contiguous()
+
+
+def vertex_tables(verts, pc, pc_seed, fb_prob, search=None):
     """One scan.  verts (V, 3), pc (N, 3), pc_seed (S, 3), fb_prob (S, 2) float32 -> src (V,) int32: the scene point nearest to each vertex,
     vert_fb (V,) float32: fb_prob[nearest seed, 1] (inference._point_probabilities' rule on the vertex itself).  Both are the first
-    column of three_nn: the first minimum of the unfused fp32 (dx*dx + dy*dy) + dz*dz, the lowest index among equal distances."""
+    column of three_nn: the first minimum of the unfused fp32 (dx*dx + dy*dy) + dz*dz, the lowest index among equal distances.
+    search: None -- nearest_point for a known set of more than NEAREST_FROM_M points, three_nn below --, or "three_nn" / "nearest_point"
+    to send both searches one way (the same bits either way; for comparing and measuring the two)."""
     verts = _typed(verts, torch.float32, 2, "verts")
     pc = _typed(pc, torch.float32, 2, "pc")
     pc_seed = _typed(pc_seed, torch.float32, 2, "pc_seed")
@@ -40,12 +54,14 @@ def vertex_tables(verts, pc, pc_seed, fb_prob):
     if verts.shape[1] != 3 or pc.shape[1] != 3 or pc_seed.shape[1] != 3 or tuple(fb_prob.shape) != (pc_seed.shape[0], 2):
         raise ValueError("vertex_tables: expected verts (V, 3), pc (N, 3), pc_seed (S, 3) and fb_prob (S, 2), got %s, %s, %s and %s"
                          % (tuple(verts.shape), tuple(pc.shape), tuple(pc_seed.shape), tuple(fb_prob.shape)))
+    if search not in _SEARCHES:
+        raise ValueError("vertex_tables: search must be one of %s, got %r" % (_SEARCHES, search))
     if min(verts.shape[0], pc.shape[0], pc_seed.shape[0]) <= 0:
         raise ValueError("vertex_tables: empty input, verts %s, pc %s, pc_seed %s" % (tuple(verts.shape), tuple(pc.shape), tuple(pc_seed.shape)))
     verts, pc, pc_seed, fb_prob = _on_device(verts=verts, pc=pc, pc_seed=pc_seed, fb_prob=fb_prob)
     with torch.no_grad():
-        src = three_nn(verts.unsqueeze(0), pc.unsqueeze(0))[1][0, :, 0].contiguous()
-        seed = three_nn(verts.unsqueeze(0), pc_seed.unsqueeze(0))[1][0, :, 0].long()
+        src = _nearest_index(verts, pc, search)
+        seed = _nearest_index(verts, pc_seed, search).long()
         return src, fb_prob[:, 1][seed].contiguous()
 
 

@@ -55,7 +55,8 @@ extern "C" {
 /* Additive at 21: gspn_segment_labels (+ _ws_bytes).  Nothing that was there changed, so the number stayed; a binder that wants the two and
  * finds an older library fails at the symbol lookup.
  * Additive at 21: gspn_sample_points_in_boxes_seeds (a seed per scene; gspn_sample_points_in_boxes keeps its draws bit for bit).
- * Additive at 21: gspn_lift_masks (+ gspn_lift_part_doubles): predictions on a scan's own vertices. */
+ * Additive at 21: gspn_lift_masks (+ gspn_lift_part_doubles): predictions on a scan's own vertices.
+ * Additive at 21: gspn_nearest_point (+ gspn_nearest_point_ws_bytes): exact one-nearest search over a cell grid in global memory. */
 #define GSPN_ABI_VERSION 21
 int gspn_dist_policy(void);
 int gspn_abi_version(void);
@@ -838,6 +839,28 @@ long gspn_lift_part_doubles(int r, int v);
 int gspn_lift_masks(int r, int v, int p, int n, int c, const float* verts, const float* crops, const float* boxes, const float* masks,
                     const int* class_ids, const int* src, const float* sem_prob, const float* vert_fb, double mask_th, double* part,
                     double* sem_conf, double* fb_conf, unsigned char* mask, int* mask_points, void* stream);
+
+/* ---------------- one nearest neighbour over a global cell grid (gspn_amd/csrc/nearest.hip, additive at ABI 21) -------------- */
+
+/* For every query of xyz1 (b,n,3) the nearest of the known points xyz2 (b,m,3) of its scene: dist (b,n) f32, idx (b,n) i32.  The pair is
+ * the FIRST COLUMN OF gspn_threenn on the same inputs, bit for bit: the distance is the unfused fp32 (dx*dx + dy*dy) + dz*dz
+ * (tf_interpolate.cpp:71-74), squared; among equal distances the lowest index wins; a pair whose distance is NaN or +inf never wins; a
+ * query with no winner gets (+inf, 0), what the reference's 1e40 initialisation leaves.  Exact, not approximate, and the same bits on every
+ * call: the known points are sorted into a grid of cells in ws (bounding box, histogram, exclusive scan, scatter; integer atomics only, no
+ * float atomics), about 4 per cell and at most 2^16 cells per scene, with cells per axis that follow the box's extents; a query scans the
+ * 3 x 3 x 3 block of cells around its own, accepts when its best distance is below the shrunk distance to every face of the block that has
+ * cells behind it, and otherwise goes on over every cell its ball touches (with an empty block: over blocks of twice the reach until one
+ * holds a point or every cell was read), comparing (distance, index) pairs so that the order of the points inside a cell does not matter; a
+ * cell that lies farther from the query than the best pair found is not read.  A query far outside the box of the known points, or in a
+ * hollow of the cloud, degrades towards a scan of all of them and stays correct.
+ * ws: gspn_nearest_point_ws_bytes(b, m) bytes (0 for sizes the call declines), 16-byte aligned; it need not be initialised, the call resets
+ * its own counters and reads nothing from it that it did not write.  Row offsets are 64-bit: b * n may exceed 2^31.  GSPN_ERR_ARG for a
+ * negative size, m == 0 with n > 0, or a null pointer; GSPN_ERR_UNSUPPORTED for m > GSPN_NEAREST_MAX_M, a ws that is not 16-byte aligned or
+ * b * ceil(n / 256) >= 2^31, all before anything is launched; b == 0 or n == 0 returns 0.  No host synchronisation, nothing allocated,
+ * static shapes: the call captures in a graph. */
+#define GSPN_NEAREST_MAX_M (1 << 24)
+long gspn_nearest_point_ws_bytes(int b, int m);
+int gspn_nearest_point(int b, int n, int m, const float* xyz1, const float* xyz2, void* ws, float* dist, int* idx, void* stream);
 
 /* ---------------- train.py: the per-step batch, the reference's optimisers, the running loss sums (gspn_amd/csrc/train.hip, ABI 20) -------
  *

@@ -696,9 +696,12 @@ def scan_predictions_torch(ep, s, verts, pc, chunk=1024):
 
 def measure_lift(a, shape, b, n, dev):
     """--measures lift: scan_predictions against scene_predictions on the scene's own points, then on synthetic scans of
-    150 000 and 500 000 vertices around the scene with the share of vertex_tables and of gspn_lift_masks alone, and the same arithmetic
+    150 000 and 500 000 vertices around the scene with the share of vertex_tables and of gspn_lift_masks alone, vertex_tables by three_nn
+    and by nearest_point with the build alone and both searches by the size of the known set, and the same arithmetic
     in torch on the device.  Call times: device events around the calls as a user makes them, allocations and torch's own kernels included."""
     from gspn_amd import lift
+    from gspn_amd.nearest import nearest_point
+    from gspn_amd.tf_interpolate import three_nn
     RP, pc, masks, ep, det_rois, (m, p, c, ns) = predict_inputs(a, b, n, dev)
     own = pc[0].contiguous()
     ours, whole = lift.scan_predictions(ep, 0, own, pc=pc), RP.scene_predictions(ep, pc)
@@ -721,6 +724,21 @@ def measure_lift(a, shape, b, n, dev):
         entry.update(timed_alternating({"scan_predictions_and_parts": lambda: lift.scan_predictions(ep, 0, verts, pc=pc),
                                         "vertex_tables": lambda: lift.vertex_tables(verts, own, ep["pc_seed"][0], ep["fb_prob"][0]),
                                         "lift_masks": lambda: lift.lift_masks(*args)}, a.warmup, a.iters))
+        # vertex_tables by the parent's route (three_nn twice) and with both searches through nearest_point, the build alone
+        # (a call with one query: six build launches and one query workgroup), and the two searches by the size of the known set
+        tables = {k: lift.vertex_tables(verts, own, ep["pc_seed"][0], ep["fb_prob"][0], search=k) for k in ("three_nn", "nearest_point")}
+        entry["routes_equal"] = bool(torch.equal(tables["three_nn"][0], tables["nearest_point"][0])
+                                     and torch.equal(tables["three_nn"][1].view(torch.int32), tables["nearest_point"][1].view(torch.int32)))
+        q1, k1 = verts.unsqueeze(0), own.unsqueeze(0)
+        entry.update(timed_alternating({
+            "vertex_tables_three_nn": lambda: lift.vertex_tables(verts, own, ep["pc_seed"][0], ep["fb_prob"][0], search="three_nn"),
+            "vertex_tables_nearest_point": lambda: lift.vertex_tables(verts, own, ep["pc_seed"][0], ep["fb_prob"][0], search="nearest_point"),
+            "nearest_point_build_alone": lambda: nearest_point(q1[:, :1], k1)}, a.warmup, a.iters))
+        by_size = entry.setdefault("by_known_size", {})
+        for size in (256, 512, 1024, 2048, 4096, 8192, n):
+            known = k1[:, torch.randperm(n, generator=torch.Generator().manual_seed(size))[:size].to(dev)].contiguous()
+            by_size[str(size)] = timed_alternating({"three_nn": lambda: three_nn(q1, known)[1][0, :, 0].contiguous(),
+                                                    "nearest_point": lambda: nearest_point(q1, known)[1][0]}, a.warmup, a.iters)
         if v <= a.lift_torch_max:
             sem_conf, fb_conf, mask = scan_predictions_torch(ep, 0, verts, pc)
             at = pred["order"][0].long()

@@ -157,6 +157,8 @@ SIGNATURES = {
     "gspn_segment_labels": [_I, _I, _I] + [_P] * 6 + [_P],
     "gspn_lift_masks": [_I] * 5 + [_P] * 8 + [_D] + [_P] * 5 + [_P],
     "gspn_nearest_point": [_I, _I, _I, _P, _P, _P, _P, _P, _P],
+    "gspn_segment_vote": [_I, _I, _I, _P, _P, _D, _P, _P, _P, _P],
+    "gspn_segment_label_vote": [_I, _I, _I, _P, _P, _P, _P, _P],
 }
 
 # entry points that do not return an int status: symbol -> (argtypes, restype)
@@ -188,6 +190,8 @@ SPECIAL = {
     "gspn_segment_labels_ws_bytes": ([_I], _L),
     "gspn_lift_part_doubles": ([_I, _I], _L),
     "gspn_nearest_point_ws_bytes": ([_I, _I], _L),
+    "gspn_segment_vote_ws_bytes": ([_I, _I, _I], _L),
+    "gspn_segment_label_vote_ws_bytes": ([_I, _I, _I], _L),
 }
 
 ABI_VERSION = 21       # == GSPN_ABI_VERSION of include/gspn_hip.h this binding was written against

@@ -3,6 +3,7 @@ cache tools/train.py --cache loads.
 
   segment_labels     data_prep.py:25-40   the (segment, objectId) pairs of segGroups onto the vertices: gspn_segment_labels
                                           (csrc/data_prep.hip), a table and a gather instead of groups x segments passes of np.where
+  read_segments      :15, :27             the segIndices of a scan's segs.json as they are (also what segments.compact_segments takes)
   collect_label      :13-45               the three label files of a scan -> semantic labels, instance labels, the count of Error! lines
   downsample_scans   :76-87               scans of unequal size to nsample points by farthest_point_sample, one scan or several per call
   prepare_scans      :48-92               the driver: <dataset>/mesh/scans, <dataset>/label/scans -> <out>/mesh/scans/<scan>.ply,
@@ -30,7 +31,7 @@ from . import io_util
 from .dataset import instance_point_sets, remap_labels, resample_scene
 from .tf_sampling import farthest_point_sample
 
-__all__ = ["SEGMENT_LABELS_MAX_N", "SEGMENT_LABELS_MAX_S", "FPS_SEGMENTS_MAX_N", "CACHE_KEYS", "segment_labels", "collect_label",
+__all__ = ["SEGMENT_LABELS_MAX_N", "SEGMENT_LABELS_MAX_S", "FPS_SEGMENTS_MAX_N", "CACHE_KEYS", "segment_labels", "read_segments", "collect_label",
            "downsample_scans", "prepare_scans", "build_cache"]
 
 SEGMENT_LABELS_MAX_N = 1 << 24    # GSPN_SEGMENT_LABELS_MAX_N of include/gspn_hip.h
@@ -110,6 +111,13 @@ def flatten_seg_groups(seg_groups):
     return segments, objects
 
 
+def read_segments(label_path, scan):
+    """<label_path>/<scan>/<scan>_vh_clean_2.0.010000.segs.json -> its segIndices, (V,) np.int64: the raw id of every vertex's segment of the
+    mesh's over-segmentation, what collect_label joins into instances and segments.compact_segments numbers for a vote."""
+    with open(os.path.join(label_path, scan, scan) + "_vh_clean_2.0.010000.segs.json") as f:
+        return np.asarray(json.load(f)["segIndices"], dtype=np.int64).reshape(-1)
+
+
 def collect_label(label_path, scan, device=None):
     """data_prep.py:13-45.  Reads <label_path>/<scan>/<scan>.aggregation.json, <scan>_vh_clean_2.0.010000.segs.json and
     <scan>_vh_clean_2.labels.ply -> sem_label (n,) int32, ins_label (n,) int32 on `device`, and the number of Error! lines as an int."""
@@ -117,8 +125,7 @@ def collect_label(label_path, scan, device=None):
     base = os.path.join(label_path, scan, scan)
     with open(base + ".aggregation.json") as f:
         seg_groups = json.load(f)["segGroups"]
-    with open(base + "_vh_clean_2.0.010000.segs.json") as f:
-        seg_indices = np.asarray(json.load(f)["segIndices"], dtype=np.int64).reshape(-1)
+    seg_indices = read_segments(label_path, scan)
     _, sem = io_util.read_label_ply(base + "_vh_clean_2.labels.ply")
     if sem.shape[0] != seg_indices.shape[0]:
         raise ValueError("collect_label: %s: %d vertices in the labels file, %d segment entries" % (scan, sem.shape[0], seg_indices.shape[0]))

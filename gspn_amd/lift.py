@@ -17,6 +17,7 @@ import torch
 from . import _lib as L
 from .nearest import nearest_point
 from .predict import SCANNET_LABEL_MAP, SCENE_RANK_MAX_R, _on_device, _typed, scene_rank
+from .segments import SEGMENT_MAX_COUNTERS, SEGMENT_MAX_S, segment_label_vote, segment_vote
 from .tf_interpolate import three_nn
 
 __all__ = ["LIFT_MAX_P", "LIFT_MAX_V", "NEAREST_FROM_M", "lift_tile", "vertex_tables", "lift_masks", "scan_predictions"]
@@ -119,7 +120,8 @@ def lift_masks(verts, crops, boxes, masks, class_ids, src, sem_prob, vert_fb, ma
 _KEYS = ("detections", "rpointnet_mask_selected", "pc_coord_cropped_final_unnormalized", "pc_seed", "fb_prob", "sem_class_logits")
 
 
-def scan_predictions(end_points, scene, verts, *, pc=None, sem_conf_th=0.01, fb_conf_th=0.01, mask_th=0.4, label_map=SCANNET_LABEL_MAP):
+def scan_predictions(end_points, scene, verts, *, pc=None, sem_conf_th=0.01, fb_conf_th=0.01, mask_th=0.4, label_map=SCANNET_LABEL_MAP,
+                     segments=None, num_segments=None, vote_th=0.5):
     """test.py:155-205 on the vertices of one scan.  end_points: rpointnet_inference's of a batch, as they are (read: detections (B, R, 8),
     rpointnet_mask_selected (B, R, P), pc_coord_cropped_final_unnormalized (B, R, P, 3), pc_seed, fb_prob, sem_class_logits (B, N, C));
     scene: the scan's slot in that batch; verts (V, 3) float32: the scan's vertices, in the coordinates of the scene's points; pc (B, N, 3):
@@ -128,6 +130,11 @@ def scan_predictions(end_points, scene, verts, *, pc=None, sem_conf_th=0.01, fb_
     score, mask_points (1, R), count (1,), masks (1, R, V) uint8, every per-detection entry in output order; write_predictions(out_dir,
     scan, pred, 0) takes it as it is -- and 'src' (V,) int32, the scene point nearest to each vertex, for lifting anything else that is
     defined on the scene's points (semantic IoU on vertices: semantic_iou_counts(sem_class_logits[scene][src], vertex_seg_label)).
+    segments (V,) int32 with num_segments: the compact segment ids of the vertices (segments.compact_segments), a value outside
+    [0, num_segments) unsegmented.  Then every mask row is snapped to the segments by segments.segment_vote at vote_th
+    before the rows are put in output order -- masks and mask_points change, the confidences, the order, the score and the count come
+    from the soft values as before --, and the dict gains 'sem_label' (V,) int32: segment_label_vote of the first maximal column of
+    sem_class_logits[scene][src].  Without segments the dict has exactly the keys and bits it had.
     Raises ValueError on a missing key or a shape or dtype that does not fit, NotImplementedError for R > 1024, P > 4096 or V > 2^24,
     before anything runs."""
     for k in _KEYS:
@@ -168,9 +175,26 @@ def scan_predictions(end_points, scene, verts, *, pc=None, sem_conf_th=0.01, fb_
     thresholds = [float(t) for t in (sem_conf_th, fb_conf_th, mask_th)]
     if any(t != t for t in thresholds):
         raise ValueError("scan_predictions: a threshold is NaN")
+    if segments is None:
+        if num_segments is not None:
+            raise ValueError("scan_predictions: num_segments without segments")
+    else:
+        segments = _typed(segments, torch.int32, 1, "segments")
+        if tuple(segments.shape) != (v,):
+            raise ValueError("scan_predictions: segments must name the segment of each of the %d vertices, got %s" % (v, tuple(segments.shape)))
+        if num_segments is None or int(num_segments) < 0:
+            raise ValueError("scan_predictions: segments needs num_segments >= 0 (segments.compact_segments gives both), got %r" % (num_segments,))
+        num_segments, vote_th = int(num_segments), float(vote_th)
+        if not 0.0 <= vote_th < 1.0:
+            raise ValueError("scan_predictions: vote_th must lie in [0, 1), got %r" % vote_th)
     if r > SCENE_RANK_MAX_R or p > LIFT_MAX_P or v > LIFT_MAX_V:
         raise NotImplementedError("scan_predictions: R <= %d, P <= %d and V <= %d (got %d, %d and %d)"
                                   % (SCENE_RANK_MAX_R, LIFT_MAX_P, LIFT_MAX_V, r, p, v))
+    if segments is not None:
+        if num_segments > SEGMENT_MAX_S or (r + 1) * num_segments > SEGMENT_MAX_COUNTERS or num_segments * c > SEGMENT_MAX_COUNTERS:
+            raise NotImplementedError("scan_predictions: num_segments <= %d, (R + 1) * num_segments and num_segments * C <= %d (got %d)"
+                                      % (SEGMENT_MAX_S, SEGMENT_MAX_COUNTERS, num_segments))
+        segments, = _on_device(segments=segments)
     verts, pc, detections, masks, crops, logits, pc_seed, fb_prob = _on_device(
         verts=verts, pc=pc, detections=detections, rpointnet_mask_selected=masks, pc_coord_cropped_final_unnormalized=crops,
         sem_class_logits=logits, pc_seed=pc_seed, fb_prob=fb_prob)
@@ -180,11 +204,19 @@ def scan_predictions(end_points, scene, verts, *, pc=None, sem_conf_th=0.01, fb_
         sem_prob = torch.softmax(logits[s:s + 1], -1)[0]                                                # inference._point_probabilities' table of the scene
         class_ids = det[:, 6].int()                                                                     # :180, .astype(np.int32)
         sem_conf, fb_conf, mask, mask_points = lift_masks(verts, crops[s], det[:, :6], masks[s], class_ids, src, sem_prob, vert_fb, thresholds[2])
+        sem_label = None
+        if segments is not None:                                                                        # 4.23: in place, the hard masks alone
+            mask, mask_points = segment_vote(mask, segments, num_segments, vote_th, out=mask)
+            own = logits[s].max(-1).indices.int().index_select(0, src.long())                           # the first maximal column, as gspn_sem_iou_counts takes it
+            sem_label = segment_label_vote(own, segments, num_segments, c)
         order, count, label_ids, confidence, score = scene_rank(det[None, :, 7], class_ids[None], sem_conf[None], fb_conf[None], thresholds[0],
                                                                 thresholds[1], label_map)
         at = order[0].long()
-        return {
+        pred = {
             "order": order, "count": count, "label_ids": label_ids, "confidence": confidence,
             "sem_conf": sem_conf[at][None], "fb_conf": fb_conf[at][None], "score": score,
             "masks": mask.index_select(0, at)[None], "mask_points": mask_points[at][None], "src": src,
         }
+        if sem_label is not None:
+            pred["sem_label"] = sem_label
+        return pred

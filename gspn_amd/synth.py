@@ -54,6 +54,26 @@ def scan_vertices(pc, seg_label, group_label, v, seed, jitter=0.01):
     return (np.concatenate((pc, moved)), np.asarray(seg_label)[at].astype(np.int32), np.asarray(group_label)[at].astype(np.int32))
 
 
+def scan_segments(xyz, seg_label, group_label, cell, seed):
+    """A synthetic over-segmentation of a scan: xyz (v, 3) f32, seg_label, group_label (v,), cell > 0 -> raw segment ids (v,) int64.
+    Segments are nested inside (seg_label, group_label): within one instance a segment is the vertices of one cube of side `cell` of the
+    coordinates (floor(xyz / cell)).  The ids are seeded: increasing with gaps of 1 to 4, then handed to the segments in shuffled
+    order, as a real file's ids are sparse and unordered (segments.compact_segments is there to be exercised)."""
+    xyz = np.asarray(xyz, np.float32)
+    v = xyz.shape[0]
+    if xyz.shape != (v, 3) or len(seg_label) != v or len(group_label) != v or not cell > 0:
+        raise ValueError("scan_segments: xyz (v, 3) with v labels of each kind and cell > 0 expected, got %s, %d, %d and cell = %r"
+                         % (xyz.shape, len(seg_label), len(group_label), cell))
+    cubes = np.floor(xyz.astype(np.float64) / float(cell)).astype(np.int64)
+    keys = np.concatenate((np.asarray(seg_label, np.int64).reshape(v, 1), np.asarray(group_label, np.int64).reshape(v, 1), cubes), axis=1)
+    _, inverse = np.unique(keys, axis=0, return_inverse=True)
+    inverse = inverse.reshape(-1)
+    k = int(inverse.max()) + 1 if v else 0
+    rng = np.random.default_rng(104729 * int(seed) + 11)
+    ids = np.cumsum(rng.integers(1, 5, size=k))                      # k different ids with gaps
+    return rng.permutation(ids)[inverse].astype(np.int64)
+
+
 def batch(kind, b, n, seed0=0):
     f = {"U": cloud_u, "D": cloud_d, "S": cloud_s}[kind]
     return np.stack([f(n, seed0 + i) for i in range(b)]).astype(np.float32)

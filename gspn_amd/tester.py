@@ -37,7 +37,8 @@ class Tester:
     with is_augment=False, permute_points=False (test.py:44).  scans: one name per scene (default scene_%04d), the stems of the files.
     seed: seeds the variables' initial values (a restore overwrites them) and the crops: scene k draws with seed + 2 * k and
     seed + 2 * k + 1.  fused_crop as in rpointnet_inference; sem_conf_th, fb_conf_th, mask_th, label_map as in scene_predictions
-    (test.py:137-139, :136), label_map with one entry per category.
+    (test.py:137-139, :136), label_map with one entry per category; vote_th: the segment vote's threshold in [0, 1), read by run_vertices for
+    a scan that brings 'segments' and by nothing else.
 
     The variables are created by one rpointnet_inference pass over the first batch, in the reference's order.
     captured=True: rpointnet_inference, scene_predictions, the AP counts and the semantic IoU counts replay from one graph.CapturedStep.
@@ -46,7 +47,7 @@ class Tester:
     Every variable, the moving statistics included, is left as it was: nothing here runs in training mode."""
 
     def __init__(self, config, data, scans=None, batch_size=1, seed=0, captured=True, fused_crop=False, sem_conf_th=0.01, fb_conf_th=0.01,
-                 mask_th=0.4, label_map=SCANNET_LABEL_MAP, max_captures=8):
+                 mask_th=0.4, label_map=SCANNET_LABEL_MAP, max_captures=8, vote_th=0.5):
         if not isinstance(data, DeviceDataset):
             raise TypeError("Tester: data must be a train.DeviceDataset")
         if data.is_augment or data.permute_points:
@@ -65,6 +66,9 @@ class Tester:
         config.BATCH_SIZE = self.b
         self.seed, self.captured, self.fused_crop, self.max_captures = int(seed), bool(captured), bool(fused_crop), int(max_captures)
         self.thresholds = dict(sem_conf_th=float(sem_conf_th), fb_conf_th=float(fb_conf_th), mask_th=float(mask_th))
+        self.vote_th = float(vote_th)                # run_vertices alone: the segment vote of a scan that brings 'segments' 
+        if not 0.0 <= self.vote_th < 1.0:
+            raise ValueError("Tester: vote_th must lie in [0, 1), got %r" % self.vote_th)
         self.dev = data.pc.device
         self.store = tf_util.set_variable_store(tf_util.VariableStore(device=self.dev, seed=self.seed))
 
@@ -219,13 +223,17 @@ class Tester:
     def run_vertices(self, out_dir, vertices, evaluate=True):
         """run() at the resolution of each scan's own mesh.  vertices(k) -> {'xyz': (V, 3) float32} for scene k, the scan's
         vertices in the coordinates of the scene's points, and, for the ground truth and the evaluation, 'seg_label' and 'group_label'
-        (V,) int32 in the cache's numbering (classes 0..C-1, groups from 0); numpy arrays or tensors.  The scenes run batched through
+        (V,) int32 in the cache's numbering (classes 0..C-1, groups from 0); numpy arrays or tensors.  A scan that also brings 'segments'
+        ((V,) integers: the raw ids of its mesh's over-segmentation, data_prep.read_segments) has its masks and its semantic labels
+        snapped to them at the tester's vote_th: the ids are compacted, scan_predictions votes, the files and the AP come
+        from the voted masks and the IoU counts from the voted labels; a scan without goes the way it always went.  The scenes run batched through
         the same step as run(); behind it lift.scan_predictions runs eagerly once per scan, V differing from scan to scan.  out_dir:
         <out_dir>/pred_vertices/<scan>.txt with pred_mask/, one line per vertex in every mask, and, where vertices(k) has labels,
         <out_dir>/gt_vertices/<scan>.txt.  evaluate: AP per scan through InstanceAP at B = 1 and the semantic IoU counts of
         sem_class_logits[src] against the vertices' labels -> run()'s dict, also written to <out_dir>/pred_vertices/
         semantic_instance_evaluation.txt; evaluate=False -> None.  run()'s own outputs and every variable are left as they are."""
         from .lift import scan_predictions
+        from .segments import compact_segments
         metric = InstanceAP(int(self.cfg.NUM_CATEGORY), label_map=self.label_map) if evaluate else None
         c = int(self.cfg.NUM_CATEGORY)
         inter = torch.zeros(c - 1, dtype=torch.int64, device=self.dev)
@@ -240,7 +248,15 @@ class Tester:
             for s, k in enumerate(idx):
                 scan = vertices(k)
                 xyz = torch.as_tensor(scan["xyz"]).to(self.dev)
-                pred = scan_predictions(out["lift"], s, xyz, pc=self.buf["pc"], label_map=self.label_map, **self.thresholds)
+                voted = {}
+                if "segments" in scan:
+                    raw = torch.as_tensor(scan["segments"]).to(self.dev)
+                    if tuple(raw.shape) != (xyz.shape[0],):
+                        raise ValueError("Tester.run_vertices: vertices(%d) must name the segment of each of its %d vertices, got %s"
+                                         % (k, xyz.shape[0], tuple(raw.shape)))
+                    compact, nseg = compact_segments(raw)
+                    voted = dict(segments=compact, num_segments=nseg, vote_th=self.vote_th)
+                pred = scan_predictions(out["lift"], s, xyz, pc=self.buf["pc"], label_map=self.label_map, **self.thresholds, **voted)
                 labelled = "seg_label" in scan and "group_label" in scan
                 if evaluate and not labelled:
                     raise ValueError("Tester.run_vertices: vertices(%d) has no 'seg_label' and 'group_label' to evaluate against" % k)
@@ -252,7 +268,10 @@ class Tester:
                                          % (k, xyz.shape[0], tuple(seg.shape), tuple(group.shape)))
                 if evaluate:
                     metric.add_predictions(pred, seg.unsqueeze(0), group.unsqueeze(0), max(int(group.max()), 0) + 1)
-                    semantic_iou_counts(out["lift"]["sem_class_logits"][s][pred["src"].long()], seg, inter, union)
+                    if voted:                        # a one-hot row's first maximum is the label: the same counts entry
+                        semantic_iou_counts(torch.nn.functional.one_hot(pred["sem_label"].long(), c).float(), seg, inter, union)
+                    else:
+                        semantic_iou_counts(out["lift"]["sem_class_logits"][s][pred["src"].long()], seg, inter, union)
                 if out_dir is not None:
                     if labelled:
                         write_ground_truth(gt_dir, self.scans[k], seg, group, self.label_map)

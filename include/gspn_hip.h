@@ -56,7 +56,8 @@ extern "C" {
  * finds an older library fails at the symbol lookup.
  * Additive at 21: gspn_sample_points_in_boxes_seeds (a seed per scene; gspn_sample_points_in_boxes keeps its draws bit for bit).
  * Additive at 21: gspn_lift_masks (+ gspn_lift_part_doubles): predictions on a scan's own vertices.
- * Additive at 21: gspn_nearest_point (+ gspn_nearest_point_ws_bytes): exact one-nearest search over a cell grid in global memory. */
+ * Additive at 21: gspn_nearest_point (+ gspn_nearest_point_ws_bytes): exact one-nearest search over a cell grid in global memory.
+ * Additive at 21: gspn_segment_vote, gspn_segment_label_vote (+ their _ws_bytes): masks and labels snapped to a scan's segments. */
 #define GSPN_ABI_VERSION 21
 int gspn_dist_policy(void);
 int gspn_abi_version(void);
@@ -861,6 +862,37 @@ int gspn_lift_masks(int r, int v, int p, int n, int c, const float* verts, const
 #define GSPN_NEAREST_MAX_M (1 << 24)
 long gspn_nearest_point_ws_bytes(int b, int m);
 int gspn_nearest_point(int b, int n, int m, const float* xyz1, const float* xyz2, void* ws, float* dist, int* idx, void* stream);
+
+/* ---------------- segment voting (gspn_amd/csrc/segments.hip, additive at ABI 21) ------------------------------------------- */
+
+/* One scan of v vertices.  seg (v) i32: the segment of every vertex; a vertex whose entry is outside [0, s) is UNSEGMENTED: it never votes,
+ * keeps its own value, and its entry indexes nothing.
+ *
+ * gspn_segment_vote: masks (r,v) u8, any nonzero byte set.  size[g] = the vertices of segment g, cnt[k][g] = those whose byte of row k is
+ * set; segment g is set in row k iff (double)cnt[k][g] > vote_th * (double)size[g], one IEEE double multiply and a strict compare.
+ *   out[k][i] = the bit of seg[i] in row k for a segmented vertex, masks[k][i] != 0 for an unsegmented one   (r,v) u8, 0 or 1, every byte written
+ *   mask_points[k] = the number of set bytes of out[k]                                                       (r) i32
+ * out may be masks itself.  vote_th a double in [0, 1).
+ * gspn_segment_label_vote: labels (v) i32, c classes.  The winner of a segment is the label in [0, c) that most of its vertices hold, the
+ * lowest among equal counts; a label outside [0, c) does not vote.  out[i] (v) i32 = the winner of seg[i] for a segmented vertex whose
+ * segment had a voter, labels[i] otherwise.  out may be labels itself.
+ *
+ * Integer atomics only (no float atomics): the same bits on every call.  Row offsets are 64-bit: r * v may exceed 2^31.  ws:
+ * gspn_segment_vote_ws_bytes(r, v, s) -- (r + 1) * s i32 counters, then r * ceil(s / 64) decision words -- or
+ * gspn_segment_label_vote_ws_bytes(v, s, c) -- s * c counters, s winners -- bytes (0 for sizes the call declines, and for r == 0 or
+ * v == 0), 16-byte aligned; it need not be initialised and nothing is read from it that the call did not write.
+ * GSPN_ERR_ARG for a negative size, a null pointer (ws included), vote_th NaN or outside [0, 1), or c < 1; GSPN_ERR_UNSUPPORTED for
+ * v > GSPN_SEGMENT_VOTE_MAX_V, r > 65535, s > GSPN_SEGMENT_VOTE_MAX_S, (r + 1) * s or s * c > GSPN_SEGMENT_VOTE_MAX_COUNTERS, or a ws that
+ * is not 16-byte aligned, all before anything is launched; r == 0 or v == 0 then returns 0.  No host synchronisation, nothing allocated,
+ * static shapes: a call with a caller-held ws captures in a graph. */
+#define GSPN_SEGMENT_VOTE_MAX_V (1 << 24)
+#define GSPN_SEGMENT_VOTE_MAX_S (1 << 24)
+#define GSPN_SEGMENT_VOTE_MAX_COUNTERS (1 << 28)
+long gspn_segment_vote_ws_bytes(int r, int v, int s);
+int gspn_segment_vote(int r, int v, int s, const unsigned char* masks, const int* seg, double vote_th, void* ws, unsigned char* out,
+                      int* mask_points, void* stream);
+long gspn_segment_label_vote_ws_bytes(int v, int s, int c);
+int gspn_segment_label_vote(int v, int s, int c, const int* labels, const int* seg, void* ws, int* out, void* stream);
 
 /* ---------------- train.py: the per-step batch, the reference's optimisers, the running loss sums (gspn_amd/csrc/train.hip, ABI 20) -------
  *

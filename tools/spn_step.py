@@ -41,6 +41,10 @@
             synthetic scans of --lift-vertices vertices around the scene, with vertex_tables and gspn_lift_masks timed alone beside it,
             alternating in one process; and the same arithmetic in torch on the device in chunks of vertices (up to --lift-torch-max
             vertices, at most 5 repeats).  Call times: device events around the calls as a user makes them
+  segments  the segment vote (gspn_amd/segments.py) on the masks of `lift`'s inputs -- 100 rows -- at the scene's own points and at
+            --lift-vertices vertices, the segments synth.scan_segments' 0.25 m cubes: segment_vote (its own workspace, and one the caller
+            holds) and segment_label_vote against the same arithmetic in torch on the device (index_add_ per row), compact_segments, and
+            scan_predictions with and without segments beside lift_masks and vertex_tables, alternating in one process
   evaluate  the instance AP counts of one batch (gspn_amd/evaluate.py) on synthetic masks at Config(istrain=False)'s widths -- 100 rows, 100
             groups, 19 categories, the benchmark's 10 thresholds: instance_overlaps against the same counts written in torch on the device
             (masks.float() against a one-hot of seg * G + group), each alone and in front of instance_match, alternating in one process,
@@ -61,6 +65,7 @@ Prints one JSON line per (shape, measurement): median / min milliseconds over --
     python tools/spn_step.py --shapes 2x18000,2x30000 --measures dataset --iters 30
     python tools/spn_step.py --shapes 2x18000 --measures predict --iters 30
     python tools/spn_step.py --shapes 1x18000 --measures lift --iters 30
+    python tools/spn_step.py --shapes 1x18000 --measures segments --warmup 5 --iters 30
     python tools/spn_step.py --shapes 2x18000,8x32768 --measures train --iters 20
     python tools/spn_step.py --shapes 2x18000 --measures evaluate --iters 30
     python tools/spn_step.py --shapes 1x150000 --measures data_prep --iters 9
@@ -748,6 +753,77 @@ def measure_lift(a, shape, b, n, dev):
                       "iters": a.iters, **res}), flush=True)
 
 
+def segment_vote_torch(masks, seg, s, vote_th):
+    """segments.segment_vote in torch on the device: the sizes once, then an index_add_ of the set vertices, the double compare and a gather
+    per row -> out (R, V) uint8, mask_points (R,) int32"""
+    inside = (seg >= 0) & (seg < s)
+    ids = seg.long().clamp(0, max(s - 1, 0))
+    size = torch.zeros(s, dtype=torch.int32, device=seg.device).index_add_(0, ids, inside.int()).double()
+    out = torch.empty_like(masks)
+    for k in range(masks.shape[0]):
+        own = masks[k] != 0
+        cnt = torch.zeros(s, dtype=torch.int32, device=seg.device).index_add_(0, ids, (inside & own).int()).double()
+        out[k] = torch.where(inside, (cnt > vote_th * size)[ids], own)
+    return out, out.sum(1, dtype=torch.int32)
+
+
+def segment_label_vote_torch(labels, seg, s, c):
+    """segments.segment_label_vote in torch on the device: one index_add_ into the (S, C) table, its first maxima, a gather"""
+    inside = (seg >= 0) & (seg < s)
+    votes = inside & (labels >= 0) & (labels < c)
+    ids = seg.long().clamp(0, max(s - 1, 0))
+    cnt = torch.zeros(s * c, dtype=torch.int32, device=seg.device).index_add_(0, ids * c + labels.long().clamp(0, c - 1), votes.int()).view(s, c)
+    best, arg = cnt.max(1)
+    return torch.where(inside & (best > 0)[ids], arg.int()[ids], labels)
+
+
+def measure_segments(a, shape, b, n, dev):
+    """--measures segments: segment_vote on the masks gspn_lift_masks leaves for the synthetic head outputs of `lift` -- 100
+    rows -- on the scene's own points and on synthetic scans of --lift-vertices vertices, with synth.scan_segments' cubes of 0.25 m inside
+    instances of 1 m cubes as the segments; with a workspace it allocates and with one the caller holds; against the same arithmetic in torch
+    on the device; segment_label_vote at the `lift` inputs' categories and its torch form; compact_segments; and scan_predictions with
+    and without segments beside lift_masks and vertex_tables, alternating in one process.  Call times by device events."""
+    from gspn_amd import _lib, lift
+    from gspn_amd import segments as SG
+    RP, pc, masks, ep, det_rois, (m, p, c, ns) = predict_inputs(a, b, n, dev)
+    own = pc[0].contiguous()
+    res = {}
+    for v in [n] + [int(t) for t in a.lift_vertices.split(",") if t]:
+        xyz = synth.scan_vertices(own.cpu().numpy(), np.zeros(n, np.int32), np.zeros(n, np.int32), v, 3)[0]
+        cube = np.floor(xyz.astype(np.float64)).astype(np.int64)
+        group = ((cube[:, 0] * 7 + cube[:, 1]) * 5 + cube[:, 2]).astype(np.int32)                    # instances: the 1 m cubes of the room
+        raw = torch.from_numpy(synth.scan_segments(xyz, group % c, group, 0.25, 5)).to(dev)
+        verts = torch.from_numpy(xyz).to(dev)
+        seg, s = SG.compact_segments(raw)
+        src, vert_fb = lift.vertex_tables(verts, own, ep["pc_seed"][0], ep["fb_prob"][0])
+        sem_prob = torch.softmax(ep["sem_class_logits"][0:1], -1)[0]
+        det = ep["detections"][0]
+        args = (verts, ep["pc_coord_cropped_final_unnormalized"][0], det[:, :6].contiguous(), ep["rpointnet_mask_selected"][0], det[:, 6].int(), src,
+                sem_prob, vert_fb)
+        mask = lift.lift_masks(*args)[2]
+        labels = ep["sem_class_logits"][0].max(-1).indices.int().index_select(0, src.long())
+        ws = torch.empty((int(_lib.lib().gspn_segment_vote_ws_bytes(m, v, s)),), dtype=torch.uint8, device=dev)
+        held = torch.empty_like(mask)
+        ours, theirs = SG.segment_vote(mask, seg, s), segment_vote_torch(mask, seg, s, 0.5)
+        entry = res.setdefault("at_%d" % v, {})
+        entry.update({"segments": s, "mask_bytes": m * v, "set_share_in": round(float((mask != 0).float().mean()), 5),
+                      "set_share_out": round(float(ours[0].float().mean()), 5), "bytes_changed": int((ours[0] != mask).sum()),
+                      "vote_equals_torch": bool(torch.equal(ours[0], theirs[0]) and torch.equal(ours[1], theirs[1])),
+                      "labels_equal_torch": bool(torch.equal(SG.segment_label_vote(labels, seg, s, c), segment_label_vote_torch(labels, seg, s, c)))})
+        entry.update(timed_alternating({
+            "segment_vote": lambda: SG.segment_vote(mask, seg, s),
+            "segment_vote_held_ws_and_out": lambda: SG.segment_vote(mask, seg, s, out=held, ws=ws),
+            "segment_vote_torch": lambda: segment_vote_torch(mask, seg, s, 0.5),
+            "segment_label_vote": lambda: SG.segment_label_vote(labels, seg, s, c),
+            "segment_label_vote_torch": lambda: segment_label_vote_torch(labels, seg, s, c),
+            "compact_segments": lambda: SG.compact_segments(raw),
+            "lift_masks": lambda: lift.lift_masks(*args),
+            "vertex_tables": lambda: lift.vertex_tables(verts, own, ep["pc_seed"][0], ep["fb_prob"][0]),
+            "scan_predictions": lambda: lift.scan_predictions(ep, 0, verts, pc=pc),
+            "scan_predictions_segments": lambda: lift.scan_predictions(ep, 0, verts, pc=pc, segments=seg, num_segments=s)}, a.warmup, a.iters))
+    print(json.dumps({"shape": shape, "kind": a.kind, "measure": "segments", "rows": m, "categories": c, "iters": a.iters, **res}), flush=True)
+
+
 def instance_counts_torch(masks, pred_class, seg, group, c, g):
     """instance_overlaps' four outputs in torch on the device: masks.float() against a one-hot of seg * G + group, a (B, N, C * G) float tensor"""
     live = (seg > 0) & (seg < c) & (group >= 0) & (group < g)
@@ -975,6 +1051,8 @@ def main():
             measure_predict(a, shape, b, n, dev)
         if "lift" in measures:
             measure_lift(a, shape, b, n, dev)
+        if "segments" in measures:
+            measure_segments(a, shape, b, n, dev)
         if "train" in measures:
             measure_train(a, shape, b, n, dev)
         if "evaluate" in measures:

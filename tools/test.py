@@ -19,11 +19,17 @@ ScanNet benchmark's format, into <out>/pred_vertices and <out>/gt_vertices, with
                      without it the masks are written and nothing is evaluated
   --synthetic_vertices V   with --synthetic: each scene's scan is its N points followed by V - N jittered copies of seeded scene points
                      that inherit their labels
+and, on top of either, the segment vote (masks and semantic labels snapped to the segments of each scan's over-segmentation):
+  --segments         with --mesh_path and --label_path: each scan's segIndices, <label_path>/<scan>/<scan>_vh_clean_2.0.010000.segs.json;
+                     with --synthetic_vertices: synth.scan_segments, cubes of --segment_cell inside every instance
+  --vote_th T        a segment is set where more than T of its vertices are [default: 0.5]; in [0, 1)
 
     python tools/test.py --synthetic 5 --num_point 4096 --num_sample 64 --num_category 9 --batch_size 2 --model_path log/model.ckpt
     python tools/test.py --cache val.pt --list scannet_val.txt --model_path log_heads/model.ckpt --batch_size 8
     python tools/test.py --cache val.pt --list scannet_val.txt --model_path log_heads/model.ckpt --batch_size 8 \\
         --mesh_path scannet/mesh/scans --label_path scannet/label/scans
+    python tools/test.py --cache val.pt --list scannet_val.txt --model_path log_heads/model.ckpt --batch_size 8 \\
+        --mesh_path scannet/mesh/scans --label_path scannet/label/scans --segments
 """
 import argparse
 import os
@@ -64,6 +70,9 @@ def parser():
     ap.add_argument('--mesh_path', default=None, help='directory of <scan>/<scan>_vh_clean_2.ply: predict on every vertex of each scan of --list')
     ap.add_argument('--label_path', default=None, help="directory of the scans' label files: the vertices' ground truth (with --mesh_path)")
     ap.add_argument('--synthetic_vertices', type=int, default=0, help='vertices of the synthetic scan around each synthetic scene')
+    ap.add_argument('--segments', action='store_true', help="snap the per-vertex masks and labels to each scan's segments (the segment vote)")
+    ap.add_argument('--vote_th', type=float, default=0.5, help='the share of a segment above which it is set [default: 0.5]')
+    ap.add_argument('--segment_cell', type=float, default=0.25, help='side of a synthetic segment (with --synthetic_vertices) [default: 0.25]')
     return ap
 
 
@@ -86,17 +95,22 @@ def synthetic_cache(a):
     return out
 
 
-def synthetic_vertices(cache, v, seed):
-    """vertices(k) of Tester.run_vertices for the scenes of synthetic_cache: synth.scan_vertices around scene k, seeded with seed + k"""
+def synthetic_vertices(cache, v, seed, segment_cell=None):
+    """vertices(k) of Tester.run_vertices for the scenes of synthetic_cache: synth.scan_vertices around scene k, seeded with seed + k;
+    with a segment_cell also 'segments', synth.scan_segments of that scan with the same seed"""
     def vertices(k):
         xyz, seg, group = synth.scan_vertices(cache["pc"][k].numpy(), cache["seg_label"][k].numpy(), cache["group_label"][k].numpy(), v, seed + k)
-        return {"xyz": xyz, "seg_label": seg, "group_label": group}
+        out = {"xyz": xyz, "seg_label": seg, "group_label": group}
+        if segment_cell is not None:
+            out["segments"] = synth.scan_segments(xyz, seg, group, segment_cell, seed + k)
+        return out
     return vertices
 
 
-def mesh_vertices(mesh_path, label_path, scans, device):
+def mesh_vertices(mesh_path, label_path, scans, device, segments=False):
     """vertices(k) of Tester.run_vertices from ScanNet's files: the vertices of <mesh_path>/<scan>/<scan>_vh_clean_2.ply as
-    tools/data_prep.py reads them and, with a label_path, their labels through data_prep.collect_label and dataset.remap_labels"""
+    tools/data_prep.py reads them and, with a label_path, their labels through data_prep.collect_label and dataset.remap_labels;
+    segments: also 'segments', data_prep.read_segments of the scan"""
     import numpy as np
     from gspn_amd import data_prep, dataset, io_util
 
@@ -107,6 +121,8 @@ def mesh_vertices(mesh_path, label_path, scans, device):
             sem, ins, _ = data_prep.collect_label(label_path, scan, device=device)
             group, seg, _ = dataset.remap_labels(ins.unsqueeze(0), sem.unsqueeze(0), max(int(ins.max()), 0) + 1)
             out["seg_label"], out["group_label"] = seg[0].int(), group[0].int()
+        if segments:
+            out["segments"] = data_prep.read_segments(label_path, scan)
         return out
     return vertices
 
@@ -139,6 +155,12 @@ def main(argv=None):
         raise SystemExit("--label_path goes with --mesh_path")
     if a.synthetic_vertices and (a.synthetic <= 0 or a.synthetic_vertices < a.num_point):
         raise SystemExit("--synthetic_vertices V goes with --synthetic S and V >= --num_point")
+    if a.segments and not (a.synthetic_vertices or (a.mesh_path and a.label_path)):
+        raise SystemExit("--segments goes with --mesh_path DIR --label_path DIR (the scans' segs.json) or with --synthetic_vertices V")
+    if not 0.0 <= a.vote_th < 1.0:
+        raise SystemExit("--vote_th must lie in [0, 1)")
+    if not a.segment_cell > 0:
+        raise SystemExit("--segment_cell must be positive")
     if not 2 <= a.num_category <= len(SCANNET_LABEL_MAP):
         raise SystemExit("--num_category must lie in [2, %d], the classes of the ScanNet label map" % len(SCANNET_LABEL_MAP))
     dev = torch.device("cuda", a.gpu)
@@ -152,11 +174,11 @@ def main(argv=None):
     if scans is not None and len(scans) != len(data):
         raise SystemExit("%s names %d scans, the cache holds %d scenes" % (a.list, len(scans), len(data)))
     tester = Tester(config_of(a), data, scans=scans, batch_size=a.batch_size, seed=a.seed, captured=not a.eager,
-                    label_map=SCANNET_LABEL_MAP[:a.num_category])
+                    label_map=SCANNET_LABEL_MAP[:a.num_category], vote_th=a.vote_th)
     tester.restore(a.model_path, scope=a.restore_scope)
     if a.mesh_path or a.synthetic_vertices:
-        vertices = (mesh_vertices(a.mesh_path, a.label_path, scans, dev) if a.mesh_path
-                    else synthetic_vertices(cache, a.synthetic_vertices, a.seed))
+        vertices = (mesh_vertices(a.mesh_path, a.label_path, scans, dev, a.segments) if a.mesh_path
+                    else synthetic_vertices(cache, a.synthetic_vertices, a.seed, a.segment_cell if a.segments else None))
         result = tester.run_vertices(None if a.no_files else a.out, vertices, evaluate=bool(a.synthetic_vertices or a.label_path))
         if result is None:
             print("per-vertex masks written to %s (no --label_path: nothing to evaluate against)" % os.path.join(a.out, "pred_vertices"))

@@ -15,6 +15,7 @@ V differs from scan to scan, so nothing here is meant for a captured step.  No C
 import torch
 
 from . import _lib as L
+from .mask_nms import mask_nms
 from .nearest import nearest_point
 from .predict import SCANNET_LABEL_MAP, SCENE_RANK_MAX_R, _on_device, _typed, scene_rank
 from .segments import SEGMENT_MAX_COUNTERS, SEGMENT_MAX_S, segment_label_vote, segment_vote
@@ -121,7 +122,7 @@ _KEYS = ("detections", "rpointnet_mask_selected", "pc_coord_cropped_final_unnorm
 
 
 def scan_predictions(end_points, scene, verts, *, pc=None, sem_conf_th=0.01, fb_conf_th=0.01, mask_th=0.4, label_map=SCANNET_LABEL_MAP,
-                     segments=None, num_segments=None, vote_th=0.5):
+                     segments=None, num_segments=None, vote_th=0.5, mask_nms_th=None):
     """test.py:155-205 on the vertices of one scan.  end_points: rpointnet_inference's of a batch, as they are (read: detections (B, R, 8),
     rpointnet_mask_selected (B, R, P), pc_coord_cropped_final_unnormalized (B, R, P, 3), pc_seed, fb_prob, sem_class_logits (B, N, C));
     scene: the scan's slot in that batch; verts (V, 3) float32: the scan's vertices, in the coordinates of the scene's points; pc (B, N, 3):
@@ -135,6 +136,10 @@ def scan_predictions(end_points, scene, verts, *, pc=None, sem_conf_th=0.01, fb_
     before the rows are put in output order -- masks and mask_points change, the confidences, the order, the score and the count come
     from the soft values as before --, and the dict gains 'sem_label' (V,) int32: segment_label_vote of the first maximal column of
     sem_class_logits[scene][src].  Without segments the dict has exactly the keys and bits it had.
+    mask_nms_th: a float in [0, 1), or None.  Then mask_nms.mask_nms at that IoU runs on the rows already in output order
+    -- after the segment vote, where there is one --, with count and label_ids as they are (per class, like refine_detections): a row
+    that an earlier kept row of its label overlaps above the threshold comes out all zero with mask_points 0, and the dict gains 'keep'
+    (1, R) uint8; the confidences, the order, the score and the count are not touched.  With None the keys and bits are what they were.
     Raises ValueError on a missing key or a shape or dtype that does not fit, NotImplementedError for R > 1024, P > 4096 or V > 2^24,
     before anything runs."""
     for k in _KEYS:
@@ -187,6 +192,10 @@ def scan_predictions(end_points, scene, verts, *, pc=None, sem_conf_th=0.01, fb_
         num_segments, vote_th = int(num_segments), float(vote_th)
         if not 0.0 <= vote_th < 1.0:
             raise ValueError("scan_predictions: vote_th must lie in [0, 1), got %r" % vote_th)
+    if mask_nms_th is not None:
+        mask_nms_th = float(mask_nms_th)
+        if not 0.0 <= mask_nms_th < 1.0:
+            raise ValueError("scan_predictions: mask_nms_th must lie in [0, 1), got %r" % mask_nms_th)
     if r > SCENE_RANK_MAX_R or p > LIFT_MAX_P or v > LIFT_MAX_V:
         raise NotImplementedError("scan_predictions: R <= %d, P <= %d and V <= %d (got %d, %d and %d)"
                                   % (SCENE_RANK_MAX_R, LIFT_MAX_P, LIFT_MAX_V, r, p, v))
@@ -219,4 +228,6 @@ def scan_predictions(end_points, scene, verts, *, pc=None, sem_conf_th=0.01, fb_
         }
         if sem_label is not None:
             pred["sem_label"] = sem_label
+        if mask_nms_th is not None:                                                                     # 4.24: in place, on the rows in output order
+            pred["masks"], pred["keep"], pred["mask_points"] = mask_nms(pred["masks"], count, label_ids, iou_th=mask_nms_th, out=pred["masks"])
         return pred

@@ -135,7 +135,7 @@ def scene_rank(det_score, class_ids, sem_conf, fb_conf, sem_conf_th=0.01, fb_con
 _KEYS = ("detections", "rpointnet_mask_selected", "pc_coord_cropped_final_unnormalized", "pc_seed", "fb_prob", "sem_class_logits")
 
 
-def scene_predictions(end_points, pc, *, sem_conf_th=0.01, fb_conf_th=0.01, mask_th=0.4, label_map=SCANNET_LABEL_MAP):
+def scene_predictions(end_points, pc, *, sem_conf_th=0.01, fb_conf_th=0.01, mask_th=0.4, label_map=SCANNET_LABEL_MAP, mask_nms_th=None):
     """test.py:155-205 for the whole batch.  end_points: rpointnet_inference's, as they are (read: detections (B, R, 8),
     rpointnet_mask_selected (B, R, P), pc_coord_cropped_final_unnormalized (B, R, P, 3), pc_seed, fb_prob, sem_class_logits (B, N, C));
     pc (B, N, 3); label_map: C integers.  -> a dict, every per-detection entry in output order (scene_rank's):
@@ -143,6 +143,9 @@ def scene_predictions(end_points, pc, *, sem_conf_th=0.01, fb_conf_th=0.01, mask
       label_ids (B, R) int32, confidence (B, R) float32, sem_conf, fb_conf, score (B, R) float64
       masks (B, R, N) uint8 (0 or 1), mask_points (B, R) int32: the set bytes of each mask
     The point tables come from inference._point_probabilities, the nearest crop points from nearest_in_sets behind the detection boxes.
+    mask_nms_th: a float in [0, 1), or None.  Then mask_nms.mask_nms at that IoU runs on the rows in output order with
+    count and label_ids as they are: a row that an earlier kept row of its label overlaps above the threshold comes out all zero with
+    mask_points 0, and the dict gains 'keep' (B, R) uint8; nothing else changes.  With None the keys and bits are what they were.
     Raises ValueError on a missing key or a shape or dtype that does not fit, NotImplementedError for R > 1024, before anything runs."""
     for k in _KEYS:
         if k not in end_points:
@@ -169,6 +172,10 @@ def scene_predictions(end_points, pc, *, sem_conf_th=0.01, fb_conf_th=0.01, mask
         label_map = _typed(label_map, torch.int32, 1, "label_map")
     if len(label_map) != c:
         raise ValueError("scene_predictions: label_map must have one entry per class, %d, got %d" % (c, len(label_map)))
+    if mask_nms_th is not None:
+        mask_nms_th = float(mask_nms_th)
+        if not 0.0 <= mask_nms_th < 1.0:
+            raise ValueError("scene_predictions: mask_nms_th must lie in [0, 1), got %r" % mask_nms_th)
     if r > SCENE_RANK_MAX_R:
         raise NotImplementedError("scene_predictions: R <= %d (got %d)" % (SCENE_RANK_MAX_R, r))
     pc, detections, masks, crops, logits, pc_seed, fb_prob = _on_device(
@@ -184,11 +191,15 @@ def scene_predictions(end_points, pc, *, sem_conf_th=0.01, fb_conf_th=0.01, mask
         order, count, label_ids, confidence, score = scene_rank(detections[:, :, 7], class_ids, sem_conf, fb_conf, sem_conf_th, fb_conf_th,
                                                                 label_map)
         at = order.long()
-        return {
+        pred = {
             "order": order, "count": count, "label_ids": label_ids, "confidence": confidence,
             "sem_conf": torch.gather(sem_conf, 1, at), "fb_conf": torch.gather(fb_conf, 1, at), "score": score,
             "masks": torch.gather(mask, 1, at.unsqueeze(-1).expand(b, r, n)), "mask_points": torch.gather(mask_points, 1, at),
         }
+        if mask_nms_th is not None:                                                                     # 4.24: in place, on the rows in output order
+            from .mask_nms import mask_nms                  # (mask_nms imports this module's helpers)
+            pred["masks"], pred["keep"], pred["mask_points"] = mask_nms(pred["masks"], count, label_ids, iou_th=mask_nms_th, out=pred["masks"])
+        return pred
 
 
 def semantic_iou_counts(logits, labels, inter=None, union=None):

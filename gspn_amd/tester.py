@@ -38,7 +38,8 @@ class Tester:
     seed: seeds the variables' initial values (a restore overwrites them) and the crops: scene k draws with seed + 2 * k and
     seed + 2 * k + 1.  fused_crop as in rpointnet_inference; sem_conf_th, fb_conf_th, mask_th, label_map as in scene_predictions
     (test.py:137-139, :136), label_map with one entry per category; vote_th: the segment vote's threshold in [0, 1), read by run_vertices for
-    a scan that brings 'segments' and by nothing else.
+    a scan that brings 'segments' and by nothing else; mask_nms_th: None, or the IoU in [0, 1) above which run_vertices suppresses a
+    per-vertex mask that copies an earlier one of its label; run() and the captured predict step never read it.
 
     The variables are created by one rpointnet_inference pass over the first batch, in the reference's order.
     captured=True: rpointnet_inference, scene_predictions, the AP counts and the semantic IoU counts replay from one graph.CapturedStep.
@@ -47,7 +48,7 @@ class Tester:
     Every variable, the moving statistics included, is left as it was: nothing here runs in training mode."""
 
     def __init__(self, config, data, scans=None, batch_size=1, seed=0, captured=True, fused_crop=False, sem_conf_th=0.01, fb_conf_th=0.01,
-                 mask_th=0.4, label_map=SCANNET_LABEL_MAP, max_captures=8, vote_th=0.5):
+                 mask_th=0.4, label_map=SCANNET_LABEL_MAP, max_captures=8, vote_th=0.5, mask_nms_th=None):
         if not isinstance(data, DeviceDataset):
             raise TypeError("Tester: data must be a train.DeviceDataset")
         if data.is_augment or data.permute_points:
@@ -69,6 +70,9 @@ class Tester:
         self.vote_th = float(vote_th)                # run_vertices alone: the segment vote of a scan that brings 'segments' 
         if not 0.0 <= self.vote_th < 1.0:
             raise ValueError("Tester: vote_th must lie in [0, 1), got %r" % self.vote_th)
+        self.mask_nms_th = None if mask_nms_th is None else float(mask_nms_th)      # run_vertices alone: mask NMS on every scan
+        if self.mask_nms_th is not None and not 0.0 <= self.mask_nms_th < 1.0:
+            raise ValueError("Tester: mask_nms_th must lie in [0, 1), got %r" % self.mask_nms_th)
         self.dev = data.pc.device
         self.store = tf_util.set_variable_store(tf_util.VariableStore(device=self.dev, seed=self.seed))
 
@@ -226,8 +230,9 @@ class Tester:
         (V,) int32 in the cache's numbering (classes 0..C-1, groups from 0); numpy arrays or tensors.  A scan that also brings 'segments'
         ((V,) integers: the raw ids of its mesh's over-segmentation, data_prep.read_segments) has its masks and its semantic labels
         snapped to them at the tester's vote_th: the ids are compacted, scan_predictions votes, the files and the AP come
-        from the voted masks and the IoU counts from the voted labels; a scan without goes the way it always went.  The scenes run batched through
-        the same step as run(); behind it lift.scan_predictions runs eagerly once per scan, V differing from scan to scan.  out_dir:
+        from the voted masks and the IoU counts from the voted labels; a scan without goes the way it always went.  With the tester's
+        mask_nms_th every scan's masks then pass mask NMS: a suppressed mask is empty, so it is not written and not counted.
+        The scenes run batched through the same step as run(); behind it lift.scan_predictions runs eagerly once per scan, V differing from scan to scan.  out_dir:
         <out_dir>/pred_vertices/<scan>.txt with pred_mask/, one line per vertex in every mask, and, where vertices(k) has labels,
         <out_dir>/gt_vertices/<scan>.txt.  evaluate: AP per scan through InstanceAP at B = 1 and the semantic IoU counts of
         sem_class_logits[src] against the vertices' labels -> run()'s dict, also written to <out_dir>/pred_vertices/
@@ -256,7 +261,8 @@ class Tester:
                                          % (k, xyz.shape[0], tuple(raw.shape)))
                     compact, nseg = compact_segments(raw)
                     voted = dict(segments=compact, num_segments=nseg, vote_th=self.vote_th)
-                pred = scan_predictions(out["lift"], s, xyz, pc=self.buf["pc"], label_map=self.label_map, **self.thresholds, **voted)
+                pred = scan_predictions(out["lift"], s, xyz, pc=self.buf["pc"], label_map=self.label_map, **self.thresholds, **voted,
+                                        mask_nms_th=self.mask_nms_th)        # 4.24: behind the vote, on the rows in output order
                 labelled = "seg_label" in scan and "group_label" in scan
                 if evaluate and not labelled:
                     raise ValueError("Tester.run_vertices: vertices(%d) has no 'seg_label' and 'group_label' to evaluate against" % k)

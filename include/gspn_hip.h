@@ -57,7 +57,8 @@ extern "C" {
  * Additive at 21: gspn_sample_points_in_boxes_seeds (a seed per scene; gspn_sample_points_in_boxes keeps its draws bit for bit).
  * Additive at 21: gspn_lift_masks (+ gspn_lift_part_doubles): predictions on a scan's own vertices.
  * Additive at 21: gspn_nearest_point (+ gspn_nearest_point_ws_bytes): exact one-nearest search over a cell grid in global memory.
- * Additive at 21: gspn_segment_vote, gspn_segment_label_vote (+ their _ws_bytes): masks and labels snapped to a scan's segments. */
+ * Additive at 21: gspn_segment_vote, gspn_segment_label_vote (+ their _ws_bytes): masks and labels snapped to a scan's segments.
+ * Additive at 21: gspn_mask_overlaps, gspn_mask_nms (+ their _ws_bytes): duplicate instance masks suppressed by pairwise IoU. */
 #define GSPN_ABI_VERSION 21
 int gspn_dist_policy(void);
 int gspn_abi_version(void);
@@ -893,6 +894,38 @@ int gspn_segment_vote(int r, int v, int s, const unsigned char* masks, const int
                       int* mask_points, void* stream);
 long gspn_segment_label_vote_ws_bytes(int v, int s, int c);
 int gspn_segment_label_vote(int v, int s, int c, const int* labels, const int* seg, void* ws, int* out, void* stream);
+
+/* ---------------- mask NMS (gspn_amd/csrc/mask_nms.hip, additive at ABI 21) -------------------------------------------------- */
+
+/* b scenes, each r mask rows of v bytes in PRIORITY ORDER (row 0 the best), any nonzero byte set.  size[k] = the set bytes of row k,
+ * inter[i][j] = the vertices set in both rows i and j.
+ *
+ * gspn_mask_overlaps: masks (b,r,v) u8 -> sizes (b,r) i32, inter (b,r,r) i32, symmetric, sizes on the diagonal.
+ * gspn_mask_nms: count (b) i32 ON THE DEVICE, live = clamp(count, 0, r) leading rows; labels (b,r) i32 or null; iou_th a double in [0, 1).
+ * Walk k = 0 .. live-1: row k is SUPPRESSED iff some earlier KEPT row i < k has (labels null or label[i] == label[k]) and
+ *   (double)inter[i][k] > iou_th * (double)(size[i] + size[k] - inter[i][k]),    one IEEE double multiply and a strict compare.
+ * A suppressed row suppresses nobody; an IoU exactly at the threshold does not suppress; an empty row neither suppresses nor is suppressed.
+ *   keep[k] (b,r) u8        = 1 for a kept live row, 0 for a suppressed row and for a row at or beyond live
+ *   out[k] (b,r,v) u8       = all zero for a suppressed row, the input as 0 / 1 for every other row (the rows beyond live too); every byte written
+ *   mask_points[k] (b,r) i32 = the set bytes of out[k]
+ * out may be masks itself.
+ *
+ * Integer atomics only (no float atomics): the same bits on every call.  Row offsets are 64-bit: b * r * v may exceed 2^31.  ws:
+ * gspn_mask_overlaps_ws_bytes(b, r, v) -- b * r * ceil(v / 64) 64-bit words -- or gspn_mask_nms_ws_bytes(b, r, v) -- the same, then, each
+ * 16-byte aligned, b * r and b * r * r i32 -- bytes (0 for sizes the call declines, and for b, r or v == 0), 16-byte aligned; it need not
+ * be initialised and nothing is read from it that the call did not write.
+ * GSPN_ERR_ARG for a negative size, a null pointer other than labels (ws included), iou_th NaN or outside [0, 1); GSPN_ERR_UNSUPPORTED for
+ * r > GSPN_MASK_NMS_MAX_R, v > GSPN_MASK_NMS_MAX_V, b > GSPN_MASK_NMS_MAX_B (a grid dimension) or a ws that is not 16-byte aligned, all
+ * before anything is launched; b, r or v == 0 then returns 0.  No host synchronisation (count is read on the device), nothing allocated,
+ * static shapes: a call with a caller-held ws captures in a graph. */
+#define GSPN_MASK_NMS_MAX_R 1024
+#define GSPN_MASK_NMS_MAX_V (1 << 24)
+#define GSPN_MASK_NMS_MAX_B 65535
+long gspn_mask_overlaps_ws_bytes(int b, int r, int v);
+int gspn_mask_overlaps(int b, int r, int v, const unsigned char* masks, void* ws, int* sizes, int* inter, void* stream);
+long gspn_mask_nms_ws_bytes(int b, int r, int v);
+int gspn_mask_nms(int b, int r, int v, const unsigned char* masks, const int* count, const int* labels, double iou_th, void* ws,
+                  unsigned char* out, unsigned char* keep, int* mask_points, void* stream);
 
 /* ---------------- train.py: the per-step batch, the reference's optimisers, the running loss sums (gspn_amd/csrc/train.hip, ABI 20) -------
  *

@@ -45,6 +45,10 @@
             --lift-vertices vertices, the segments synth.scan_segments' 0.25 m cubes: segment_vote (its own workspace, and one the caller
             holds) and segment_label_vote against the same arithmetic in torch on the device (index_add_ per row), compact_segments, and
             scan_predictions with and without segments beside lift_masks and vertex_tables, alternating in one process
+  mask_nms  mask NMS (gspn_amd/mask_nms.py) on the rows scan_predictions leaves behind the segment vote for `segments`' inputs -- 100 rows
+            -- at the scene's own points and at --lift-vertices vertices, as they are and with every row doubled: mask_overlaps against
+            masks.float() @ masks.float().T on the device, mask_nms whole (its own workspace, and one the caller holds), and
+            scan_predictions with segments with and without mask_nms_th, alternating in one process
   evaluate  the instance AP counts of one batch (gspn_amd/evaluate.py) on synthetic masks at Config(istrain=False)'s widths -- 100 rows, 100
             groups, 19 categories, the benchmark's 10 thresholds: instance_overlaps against the same counts written in torch on the device
             (masks.float() against a one-hot of seg * G + group), each alone and in front of instance_match, alternating in one process,
@@ -66,6 +70,7 @@ Prints one JSON line per (shape, measurement): median / min milliseconds over --
     python tools/spn_step.py --shapes 2x18000 --measures predict --iters 30
     python tools/spn_step.py --shapes 1x18000 --measures lift --iters 30
     python tools/spn_step.py --shapes 1x18000 --measures segments --warmup 5 --iters 30
+    python tools/spn_step.py --shapes 1x18000 --measures mask_nms --warmup 5 --iters 30
     python tools/spn_step.py --shapes 2x18000,8x32768 --measures train --iters 20
     python tools/spn_step.py --shapes 2x18000 --measures evaluate --iters 30
     python tools/spn_step.py --shapes 1x150000 --measures data_prep --iters 9
@@ -824,6 +829,61 @@ def measure_segments(a, shape, b, n, dev):
     print(json.dumps({"shape": shape, "kind": a.kind, "measure": "segments", "rows": m, "categories": c, "iters": a.iters, **res}), flush=True)
 
 
+def mask_overlaps_torch(masks):
+    """mask_nms.mask_overlaps in torch on the device: the masks as floats (a copy four times their size) and one fp32 GEMM; exact while a
+    count stays below 2^24 -> sizes (R,) int32, inter (R, R) int32"""
+    f = (masks != 0).float()
+    inter = (f @ f.T).int()
+    return inter.diagonal().contiguous(), inter
+
+
+def measure_mask_nms(a, shape, b, n, dev):
+    """--measures mask_nms: the rows scan_predictions leaves in output order behind the segment vote, for `segments`' inputs
+    -- 100 rows -- on the scene's own points and on synthetic scans of --lift-vertices vertices, and the same rows with every even row
+    copied onto the odd row behind it (duplicates for the stage to find): mask_overlaps against masks.float() @ masks.float().T on the
+    device, mask_nms whole with a workspace it allocates and with one the caller holds, and scan_predictions with segments with and
+    without mask_nms_th, alternating in one process.  Call times by device events."""
+    from gspn_amd import _lib, lift
+    from gspn_amd import mask_nms as MN
+    from gspn_amd import segments as SG
+    RP, pc, masks, ep, det_rois, (m, p, c, ns) = predict_inputs(a, b, n, dev)
+    own = pc[0].contiguous()
+    res = {}
+    for v in [n] + [int(t) for t in a.lift_vertices.split(",") if t]:
+        xyz = synth.scan_vertices(own.cpu().numpy(), np.zeros(n, np.int32), np.zeros(n, np.int32), v, 3)[0]
+        cube = np.floor(xyz.astype(np.float64)).astype(np.int64)
+        group = ((cube[:, 0] * 7 + cube[:, 1]) * 5 + cube[:, 2]).astype(np.int32)                    # instances: the 1 m cubes of the room
+        seg, s = SG.compact_segments(torch.from_numpy(synth.scan_segments(xyz, group % c, group, 0.25, 5)).to(dev))
+        verts = torch.from_numpy(xyz).to(dev)
+        pred = lift.scan_predictions(ep, 0, verts, pc=pc, segments=seg, num_segments=s)
+        rows, count, labels = pred["masks"][0].contiguous(), pred["count"][0], pred["label_ids"][0].contiguous()
+        twice = rows.clone()
+        twice[1::2] = twice[0:2 * (m // 2):2]
+        labels2 = labels.clone()
+        labels2[1::2] = labels2[0:2 * (m // 2):2]
+        ws = torch.empty((int(_lib.lib().gspn_mask_nms_ws_bytes(1, m, v)),), dtype=torch.uint8, device=dev)
+        held = torch.empty_like(rows)
+        ours, theirs = MN.mask_overlaps(rows), mask_overlaps_torch(rows)
+        kept, kept2 = MN.mask_nms(rows, count, labels, iou_th=0.5)[1], MN.mask_nms(twice, count, labels2, iou_th=0.5)[1]
+        entry = res.setdefault("at_%d" % v, {})
+        entry.update({"mask_bytes": m * v, "live_rows": int(count), "set_share": round(float((rows != 0).float().mean()), 5),
+                      "overlaps_equal_torch": bool(torch.equal(ours[0], theirs[0]) and torch.equal(ours[1], theirs[1])),
+                      "nonzero_pairs": int((ours[1] != 0).sum()), "suppressed": int(count) - int(kept.sum()),
+                      "suppressed_doubled_rows": int(count) - int(kept2.sum())})
+        entry.update(timed_alternating({
+            "mask_overlaps": lambda: MN.mask_overlaps(rows),
+            "mask_overlaps_held_ws": lambda: MN.mask_overlaps(rows, ws=ws),
+            "mask_overlaps_torch": lambda: mask_overlaps_torch(rows),
+            "mask_overlaps_doubled_rows": lambda: MN.mask_overlaps(twice, ws=ws),
+            "mask_nms": lambda: MN.mask_nms(rows, count, labels, iou_th=0.5),
+            "mask_nms_held_ws_and_out": lambda: MN.mask_nms(rows, count, labels, iou_th=0.5, out=held, ws=ws),
+            "mask_nms_doubled_rows": lambda: MN.mask_nms(twice, count, labels2, iou_th=0.5, out=held, ws=ws),
+            "scan_predictions_segments": lambda: lift.scan_predictions(ep, 0, verts, pc=pc, segments=seg, num_segments=s),
+            "scan_predictions_segments_mask_nms": lambda: lift.scan_predictions(ep, 0, verts, pc=pc, segments=seg, num_segments=s, mask_nms_th=0.5)},
+            a.warmup, a.iters))
+    print(json.dumps({"shape": shape, "kind": a.kind, "measure": "mask_nms", "rows": m, "iters": a.iters, **res}), flush=True)
+
+
 def instance_counts_torch(masks, pred_class, seg, group, c, g):
     """instance_overlaps' four outputs in torch on the device: masks.float() against a one-hot of seg * G + group, a (B, N, C * G) float tensor"""
     live = (seg > 0) & (seg < c) & (group >= 0) & (group < g)
@@ -1053,6 +1113,8 @@ def main():
             measure_lift(a, shape, b, n, dev)
         if "segments" in measures:
             measure_segments(a, shape, b, n, dev)
+        if "mask_nms" in measures:
+            measure_mask_nms(a, shape, b, n, dev)
         if "train" in measures:
             measure_train(a, shape, b, n, dev)
         if "evaluate" in measures:

@@ -23,6 +23,9 @@ and, on top of either, the segment vote (masks and semantic labe
   --segments         with --mesh_path and --label_path: each scan's segIndices, <label_path>/<scan>/<scan>_vh_clean_2.0.010000.segs.json;
                      with --synthetic_vertices: synth.scan_segments, cubes of --segment_cell inside every instance
   --vote_th T        a segment is set where more than T of its vertices are [default: 0.5]; in [0, 1)
+and mask NMS (a per-vertex mask that copies an earlier one of its label is emptied before the files and the figures):
+  --mask_nms T       with --mesh_path or --synthetic_vertices: suppress a mask whose IoU with an earlier kept one of its label is above T,
+                     in [0, 1); behind the segment vote where --segments is given [default: off]
 
     python tools/test.py --synthetic 5 --num_point 4096 --num_sample 64 --num_category 9 --batch_size 2 --model_path log/model.ckpt
     python tools/test.py --cache val.pt --list scannet_val.txt --model_path log_heads/model.ckpt --batch_size 8
@@ -30,6 +33,8 @@ and, on top of either, the segment vote (masks and semantic labe
         --mesh_path scannet/mesh/scans --label_path scannet/label/scans
     python tools/test.py --cache val.pt --list scannet_val.txt --model_path log_heads/model.ckpt --batch_size 8 \\
         --mesh_path scannet/mesh/scans --label_path scannet/label/scans --segments
+    python tools/test.py --cache val.pt --list scannet_val.txt --model_path log_heads/model.ckpt --batch_size 8 \\
+        --mesh_path scannet/mesh/scans --label_path scannet/label/scans --segments --mask_nms 0.5
 """
 import argparse
 import os
@@ -73,6 +78,7 @@ def parser():
     ap.add_argument('--segments', action='store_true', help="snap the per-vertex masks and labels to each scan's segments (the segment vote)")
     ap.add_argument('--vote_th', type=float, default=0.5, help='the share of a segment above which it is set [default: 0.5]')
     ap.add_argument('--segment_cell', type=float, default=0.25, help='side of a synthetic segment (with --synthetic_vertices) [default: 0.25]')
+    ap.add_argument('--mask_nms', type=float, default=None, help='suppress per-vertex masks above this IoU with an earlier one of their label [default: off]')
     return ap
 
 
@@ -161,6 +167,10 @@ def main(argv=None):
         raise SystemExit("--vote_th must lie in [0, 1)")
     if not a.segment_cell > 0:
         raise SystemExit("--segment_cell must be positive")
+    if a.mask_nms is not None and not (a.synthetic_vertices or a.mesh_path):
+        raise SystemExit("--mask_nms goes with the vertex modes: --mesh_path DIR or --synthetic_vertices V")
+    if a.mask_nms is not None and not 0.0 <= a.mask_nms < 1.0:
+        raise SystemExit("--mask_nms must lie in [0, 1)")
     if not 2 <= a.num_category <= len(SCANNET_LABEL_MAP):
         raise SystemExit("--num_category must lie in [2, %d], the classes of the ScanNet label map" % len(SCANNET_LABEL_MAP))
     dev = torch.device("cuda", a.gpu)
@@ -174,7 +184,7 @@ def main(argv=None):
     if scans is not None and len(scans) != len(data):
         raise SystemExit("%s names %d scans, the cache holds %d scenes" % (a.list, len(scans), len(data)))
     tester = Tester(config_of(a), data, scans=scans, batch_size=a.batch_size, seed=a.seed, captured=not a.eager,
-                    label_map=SCANNET_LABEL_MAP[:a.num_category], vote_th=a.vote_th)
+                    label_map=SCANNET_LABEL_MAP[:a.num_category], vote_th=a.vote_th, mask_nms_th=a.mask_nms)
     tester.restore(a.model_path, scope=a.restore_scope)
     if a.mesh_path or a.synthetic_vertices:
         vertices = (mesh_vertices(a.mesh_path, a.label_path, scans, dev, a.segments) if a.mesh_path

@@ -85,6 +85,24 @@ __device__ __forceinline__ int wave_max_i32(int v) {
     int d = __builtin_amdgcn_readlane(v, 48);
     return max(max(a, b), max(c, d));
 }
+// sum over the wave in a __shfl_down tree (32, 16, ... 1): the order of the additions is fixed, the double sums of predict.hip and lift.hip
+// are pinned to it
+template <typename T>
+__device__ __forceinline__ T wave_sum_lane0(T v) {
+    for (int off = GSPN_WAVE / 2; off > 0; off >>= 1) v += __shfl_down(v, off, GSPN_WAVE);
+    return v;                                                        // lane 0 holds the wave's sum
+}
+// max / min of a per-lane float, in every lane
+__device__ __forceinline__ float wave_max_f32(float v) {
+#pragma unroll
+    for (int o = GSPN_WAVE / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, GSPN_WAVE));
+    return v;
+}
+__device__ __forceinline__ float wave_min_f32(float v) {
+#pragma unroll
+    for (int o = GSPN_WAVE / 2; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, GSPN_WAVE));
+    return v;
+}
 __device__ __forceinline__ int lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 // the number of set bits of a ballot mask below this lane: the slot of a hit among the wave's hits, in lane order
 __device__ __forceinline__ int mbcnt64(unsigned long long mask) {

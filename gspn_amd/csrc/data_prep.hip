@@ -17,11 +17,6 @@
 
 namespace {
 
-__device__ __forceinline__ int wave_sum_i32(int v) {
-    for (int off = GSPN_WAVE / 2; off > 0; off >>= 1) v += __shfl_down(v, off, GSPN_WAVE);
-    return v;                                                                     // lane 0 holds the wave's sum
-}
-
 __global__ __launch_bounds__(SL_THREADS) void segment_table_init_kernel(int s, int* __restrict__ winner, int* __restrict__ named,
                                                                         int* __restrict__ seen, int* __restrict__ conflicts) {
     const int stride = gridDim.x * SL_THREADS;
@@ -93,7 +88,7 @@ __global__ __launch_bounds__(SL_THREADS) void segment_conflicts_kernel(int s, co
     int sum = 0;
     for (int i = blockIdx.x * SL_THREADS + threadIdx.x; i < s; i += stride)
         if (seen[i]) sum += named[i] - 1;                                         // seen implies named >= 1
-    sum = wave_sum_i32(sum);
+    sum = wave_sum_lane0(sum);
     if ((threadIdx.x & (GSPN_WAVE - 1)) == 0 && sum) atomicAdd(conflicts, sum);
 }
 

@@ -19,11 +19,6 @@
 
 namespace {
 
-__device__ __forceinline__ int wave_sum_i32(int v) {
-    for (int off = GSPN_WAVE / 2; off > 0; off >>= 1) v += __shfl_down(v, off, GSPN_WAVE);
-    return v;                                                                     // lane 0 holds the wave's sum
-}
-
 // one set point j of a row of class cls
 __device__ __forceinline__ void count_point(int j, int cls, int c, int g, const int* __restrict__ seg, const int* __restrict__ group, int* bins,
                                             int& size, int& void_points) {
@@ -80,8 +75,8 @@ __global__ __launch_bounds__(IO_THREADS) void instance_overlaps_kernel(int r, in
     }
     for (int j = tail + threadIdx.x; j < n; j += IO_THREADS)
         if (m[j]) count_point(j, cls, c, g, seg, group, bins, size, void_points);
-    size = wave_sum_i32(size);
-    void_points = wave_sum_i32(void_points);
+    size = wave_sum_lane0(size);
+    void_points = wave_sum_lane0(void_points);
     if ((threadIdx.x & (GSPN_WAVE - 1)) == 0) {
         if (void_points) atomicAdd(&bins[g], void_points);
         if (size) atomicAdd(&bins[g + 1], size);

@@ -43,11 +43,6 @@ typedef unsigned long long u64;
 
 namespace {
 
-__device__ __forceinline__ int mn_wave_sum(int v) {
-    for (int off = GSPN_WAVE / 2; off > 0; off >>= 1) v += __shfl_down(v, off, GSPN_WAVE);
-    return v;                                                        // lane 0 holds the wave's sum
-}
-
 // the 4 bits "byte k of x is not zero", bit k for byte k
 __device__ __forceinline__ unsigned mn_nibble(unsigned x) {
     const unsigned y = (((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u;      // the top bit of every nonzero byte
@@ -95,7 +90,7 @@ __global__ __launch_bounds__(MN_T) void mn_pack_kernel(int r, int v, int words, 
         packed[rr * words + w] = word;
         n = __popcll(word);
     }
-    n = mn_wave_sum(n);
+    n = wave_sum_lane0(n);
     if (tid == 0 && n != 0) atomicAdd(&sizes[rr], n);
 }
 

@@ -24,15 +24,6 @@
 
 namespace {
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-    for (int off = GSPN_WAVE / 2; off > 0; off >>= 1) v += __shfl_down(v, off, GSPN_WAVE);
-    return v;                                                                     // lane 0 holds the wave's sum
-}
-__device__ __forceinline__ int wave_sum_i32(int v) {
-    for (int off = GSPN_WAVE / 2; off > 0; off >>= 1) v += __shfl_down(v, off, GSPN_WAVE);
-    return v;
-}
-
 __global__ __launch_bounds__(SC_THREADS) void scene_confidence_kernel(int r, int n, int p, int c, const int* __restrict__ idx,
                                                                       const float* __restrict__ masks, const int* __restrict__ class_ids,
                                                                       const float* __restrict__ sem_prob, const float* __restrict__ point_fb,
@@ -75,10 +66,10 @@ __global__ __launch_bounds__(SC_THREADS) void scene_confidence_kernel(int r, int
         out_mask[j] = set ? 1 : 0;
         points += set ? 1 : 0;
     }
-    s0 = wave_sum_f64(s0);
-    s1 = wave_sum_f64(s1);
-    s2 = wave_sum_f64(s2);
-    points = wave_sum_i32(points);
+    s0 = wave_sum_lane0(s0);
+    s1 = wave_sum_lane0(s1);
+    s2 = wave_sum_lane0(s2);
+    points = wave_sum_lane0(points);
     const int wave = threadIdx.x / GSPN_WAVE;
     if ((threadIdx.x & (GSPN_WAVE - 1)) == 0) {
         red[0][wave] = s0;

@@ -33,11 +33,6 @@
 
 namespace {
 
-__device__ __forceinline__ int sv_wave_sum(int v) {
-    for (int off = GSPN_WAVE / 2; off > 0; off >>= 1) v += __shfl_down(v, off, GSPN_WAVE);
-    return v;                                                        // lane 0 holds the wave's sum
-}
-
 __global__ __launch_bounds__(SV_T) void sv_init_kernel(long ncnt, int npts, int* __restrict__ cnt, int* __restrict__ mask_points) {
     for (long i = blockIdx.x * (long)SV_T + threadIdx.x; i < ncnt; i += (long)gridDim.x * SV_T) cnt[i] = 0;
     for (long i = blockIdx.x * (long)SV_T + threadIdx.x; i < npts; i += (long)gridDim.x * SV_T) mask_points[i] = 0;
@@ -94,7 +89,7 @@ __global__ __launch_bounds__(SV_T) void sv_decide_kernel(long nwords, int words,
         if ((double)cnt[row * s + sg] > vote_th * (double)n) members = n;    // (cnt > 0 here, so n > 0)
     }
     const unsigned long long ballot = __ballot(members != 0);
-    members = sv_wave_sum(members);                                  // <= v <= 2^24
+    members = wave_sum_lane0(members);                                  // <= v <= 2^24
     if (lane == 0) {
         bits[word] = ballot;
         if (members != 0) atomicAdd(&mask_points[row], members);
@@ -129,7 +124,7 @@ __global__ __launch_bounds__(SV_T) void sv_apply_kernel(int r, int v, int s, int
                 n += !segmented && set ? 1 : 0;                      // the segmented ones were counted by sv_decide_kernel
             }
         }
-        n = sv_wave_sum(n);
+        n = wave_sum_lane0(n);
         if (lane == 0 && n != 0) atomicAdd(&mask_points[row], n);
     }
 }

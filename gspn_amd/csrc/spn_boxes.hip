@@ -20,17 +20,6 @@
 
 namespace {
 
-__device__ __forceinline__ float wave_max_f32(float v) {
-#pragma unroll
-    for (int o = GSPN_WAVE / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, GSPN_WAVE));
-    return v;
-}
-__device__ __forceinline__ float wave_min_f32(float v) {
-#pragma unroll
-    for (int o = GSPN_WAVE / 2; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, GSPN_WAVE));
-    return v;
-}
-
 // ---------------------------------------------------------------------------------------------------- box_shrink
 // grid (ceil(s / NB), b).  Boxes past s in the last chunk are computed on a clamped index and not written.
 template <int NB>

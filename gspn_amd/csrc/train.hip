@@ -25,17 +25,6 @@
 
 namespace {
 
-__device__ __forceinline__ float wave_max_f32(float v) {
-#pragma unroll
-    for (int o = GSPN_WAVE / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, GSPN_WAVE));
-    return v;
-}
-__device__ __forceinline__ float wave_min_f32(float v) {
-#pragma unroll
-    for (int o = GSPN_WAVE / 2; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, GSPN_WAVE));
-    return v;
-}
-
 // ---------------------------------------------------------------------------------------------------- the permutation
 // gspn_batch_perm of include/gspn_hip.h: a 4-round balanced Feistel network over `bits` (even) bits, cycle-walked into [0, n)
 struct PermKey {

@@ -124,6 +124,38 @@ def test_lift_masks_against_the_definition(shape):
         assert rc == 0
 
 
+@pytest.mark.parametrize("shape", [(2, 257, 3, 7, 4), (512, 1025, 5, 33, 6)])           # one vertex per lane; four: 512 * ceil(1025 / 1024) >= 512
+def test_lift_masks_is_nearest_in_sets_behind_the_threshold(shape):
+    """The two entry points over the shared tile (csrc/inbox_nearest.h), against each other and without a tolerance: for the rows of a
+    valid class, mask[k][i] is idx[k][i] >= 0 and float64(masks[k][idx[k][i]]) > mask_th with idx = gspn_nearest_in_sets(b = 1, ...) on the
+    same arrays, and mask_points[k] is that row's sum.  Row 0 holds every vertex and row 1 none, so that each instantiation sees a tile
+    of more than 128 inside vertices (one lane per vertex), one of exactly 1 (the vertex past the first tile, 64 lanes for it) and
+    one of 0."""
+    from gspn_amd import _lib as L
+    from gspn_amd.lift import lift_tile
+    r, v, p, n, c = shape
+    tile = lift_tile(r, v)
+    assert tile == (1024 if r == 512 else 256)
+    case = make_case(*shape, seed=29 + v, full_row=True)
+    valid = (case["class_ids"] > 0) & (case["class_ids"] < c)
+    assert valid[0] and valid[1]
+    inside = np.stack([LR.inside(case["verts"], b) for b in case["boxes"]])[valid]            # (valid rows, v)
+    per_tile = np.concatenate([inside[:, at:at + tile].sum(1) for at in range(0, v, tile)])
+    assert (per_tile > 128).any() and (per_tile == 1).any() and (per_tile == 0).any()
+    dev = on_device(case)
+    idx = torch.full((1, r, v), -7, dtype=torch.int32, device="cuda")
+    rc = L.lib().gspn_nearest_in_sets(1, r, v, p, L.ptr(dev["verts"]), L.ptr(dev["crops"]), L.ptr(dev["boxes"]), L.ptr(idx), L.stream())
+    torch.cuda.synchronize()
+    assert rc == 0
+    idx = idx[0].cpu().numpy()
+    assert idx.min() >= -1 and idx.max() < p
+    rc, (_, _, mask, points), _ = raw_call(dev, 0.4, float("nan"))
+    assert rc == 0
+    want = (idx >= 0) & (np.take_along_axis(case["masks"], np.maximum(idx, 0), 1).astype(np.float64) > 0.4)
+    assert np.array_equal(mask.cpu().numpy()[valid], want[valid].astype(np.uint8))
+    assert np.array_equal(points.cpu().numpy()[valid], want[valid].sum(1).astype(np.int32))
+
+
 def test_lift_masks_declines_what_it_does_not_take():
     from gspn_amd.lift import lift_masks
     case = make_case(2, 300, 4097, 9, 4, seed=3)

@@ -161,6 +161,8 @@ SIGNATURES = {
     "gspn_segment_label_vote": [_I, _I, _I, _P, _P, _P, _P, _P],
     "gspn_mask_overlaps": [_I, _I, _I, _P, _P, _P, _P, _P],
     "gspn_mask_nms": [_I, _I, _I, _P, _P, _P, _D, _P, _P, _P, _P, _P],
+    "gspn_mask_components": [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
+    "gspn_mask_component_filter": [_I, _I, _I, _P, _P, _I, _D, _P, _P, _P, _P, _P, _P],
 }
 
 # entry points that do not return an int status: symbol -> (argtypes, restype)
@@ -196,6 +198,8 @@ SPECIAL = {
     "gspn_segment_label_vote_ws_bytes": ([_I, _I, _I], _L),
     "gspn_mask_overlaps_ws_bytes": ([_I, _I, _I], _L),
     "gspn_mask_nms_ws_bytes": ([_I, _I, _I], _L),
+    "gspn_mask_components_ws_bytes": ([_I, _I, _I], _L),
+    "gspn_mask_component_filter_ws_bytes": ([_I, _I, _I], _L),
 }
 
 ABI_VERSION = 21       # == GSPN_ABI_VERSION of include/gspn_hip.h this binding was written against

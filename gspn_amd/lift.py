@@ -15,6 +15,7 @@ V differs from scan to scan, so nothing here is meant for a captured step.  No C
 import torch
 
 from . import _lib as L
+from .components import COMPONENTS_MAX_F, _parameters, component_filter
 from .mask_nms import mask_nms
 from .nearest import nearest_point
 from .predict import SCANNET_LABEL_MAP, SCENE_RANK_MAX_R, _on_device, _typed, scene_rank
@@ -122,7 +123,7 @@ _KEYS = ("detections", "rpointnet_mask_selected", "pc_coord_cropped_final_unnorm
 
 
 def scan_predictions(end_points, scene, verts, *, pc=None, sem_conf_th=0.01, fb_conf_th=0.01, mask_th=0.4, label_map=SCANNET_LABEL_MAP,
-                     segments=None, num_segments=None, vote_th=0.5, mask_nms_th=None):
+                     segments=None, num_segments=None, vote_th=0.5, mask_nms_th=None, faces=None, min_component=None, min_component_share=0.0):
     """test.py:155-205 on the vertices of one scan.  end_points: rpointnet_inference's of a batch, as they are (read: detections (B, R, 8),
     rpointnet_mask_selected (B, R, P), pc_coord_cropped_final_unnormalized (B, R, P, 3), pc_seed, fb_prob, sem_class_logits (B, N, C));
     scene: the scan's slot in that batch; verts (V, 3) float32: the scan's vertices, in the coordinates of the scene's points; pc (B, N, 3):
@@ -140,6 +141,13 @@ def scan_predictions(end_points, scene, verts, *, pc=None, sem_conf_th=0.01, fb_
     -- after the segment vote, where there is one --, with count and label_ids as they are (per class, like refine_detections): a row
     that an earlier kept row of its label overlaps above the threshold comes out all zero with mask_points 0, and the dict gains 'keep'
     (1, R) uint8; the confidences, the order, the score and the count are not touched.  With None the keys and bits are what they were.
+    faces (F, 3) int32 with min_component: the scan's triangles (components.mesh_faces) and an int >= 1.  Then
+    components.component_filter(min_vertices=min_component, min_share=min_component_share) runs in place on the hard rows behind the
+    segment vote, BEFORE the rows are put in output order and before mask NMS, which must see the cleaned rows: a component of a row
+    smaller than min_component vertices, or than min_component_share of the row's largest, is dropped.  masks and mask_points change and
+    the dict gains 'components' and 'components_kept' (1, R) int32 in output order; the confidences, the order, the score and the count
+    come from the soft values as before.  One of the two without the other raises ValueError; with neither the keys and bits are what
+    they were.
     Raises ValueError on a missing key or a shape or dtype that does not fit, NotImplementedError for R > 1024, P > 4096 or V > 2^24,
     before anything runs."""
     for k in _KEYS:
@@ -196,6 +204,14 @@ def scan_predictions(end_points, scene, verts, *, pc=None, sem_conf_th=0.01, fb_
         mask_nms_th = float(mask_nms_th)
         if not 0.0 <= mask_nms_th < 1.0:
             raise ValueError("scan_predictions: mask_nms_th must lie in [0, 1), got %r" % mask_nms_th)
+    if (faces is None) != (min_component is None):
+        raise ValueError("scan_predictions: faces and min_component go together (got faces %s, min_component %r)"
+                         % ("None" if faces is None else "given", min_component))
+    if faces is not None:
+        faces = _typed(faces, torch.int32, 2, "faces")
+        if faces.shape[1] != 3:
+            raise ValueError("scan_predictions: faces must be (F, 3) (components.mesh_faces), got %s" % (tuple(faces.shape),))
+        min_component, min_component_share = _parameters(min_component, min_component_share, "scan_predictions")
     if r > SCENE_RANK_MAX_R or p > LIFT_MAX_P or v > LIFT_MAX_V:
         raise NotImplementedError("scan_predictions: R <= %d, P <= %d and V <= %d (got %d, %d and %d)"
                                   % (SCENE_RANK_MAX_R, LIFT_MAX_P, LIFT_MAX_V, r, p, v))
@@ -204,6 +220,10 @@ def scan_predictions(end_points, scene, verts, *, pc=None, sem_conf_th=0.01, fb_
             raise NotImplementedError("scan_predictions: num_segments <= %d, (R + 1) * num_segments and num_segments * C <= %d (got %d)"
                                       % (SEGMENT_MAX_S, SEGMENT_MAX_COUNTERS, num_segments))
         segments, = _on_device(segments=segments)
+    if faces is not None:
+        if faces.shape[0] > COMPONENTS_MAX_F:
+            raise NotImplementedError("scan_predictions: F <= %d (got %d)" % (COMPONENTS_MAX_F, faces.shape[0]))
+        faces, = _on_device(faces=faces)
     verts, pc, detections, masks, crops, logits, pc_seed, fb_prob = _on_device(
         verts=verts, pc=pc, detections=detections, rpointnet_mask_selected=masks, pc_coord_cropped_final_unnormalized=crops,
         sem_class_logits=logits, pc_seed=pc_seed, fb_prob=fb_prob)
@@ -218,6 +238,9 @@ def scan_predictions(end_points, scene, verts, *, pc=None, sem_conf_th=0.01, fb_
             mask, mask_points = segment_vote(mask, segments, num_segments, vote_th, out=mask)
             own = logits[s].max(-1).indices.int().index_select(0, src.long())                           # the first maximal column, as gspn_sem_iou_counts takes it
             sem_label = segment_label_vote(own, segments, num_segments, c)
+        components = None
+        if faces is not None:                                                                           # 4.25: in place, behind the vote, before the order
+            mask, mask_points, components, kept = component_filter(mask, faces, min_vertices=min_component, min_share=min_component_share, out=mask)
         order, count, label_ids, confidence, score = scene_rank(det[None, :, 7], class_ids[None], sem_conf[None], fb_conf[None], thresholds[0],
                                                                 thresholds[1], label_map)
         at = order[0].long()
@@ -228,6 +251,8 @@ def scan_predictions(end_points, scene, verts, *, pc=None, sem_conf_th=0.01, fb_
         }
         if sem_label is not None:
             pred["sem_label"] = sem_label
+        if components is not None:
+            pred["components"], pred["components_kept"] = components[at][None], kept[at][None]
         if mask_nms_th is not None:                                                                     # 4.24: in place, on the rows in output order
             pred["masks"], pred["keep"], pred["mask_points"] = mask_nms(pred["masks"], count, label_ids, iou_th=mask_nms_th, out=pred["masks"])
         return pred

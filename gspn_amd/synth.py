@@ -74,6 +74,53 @@ def scan_segments(xyz, seg_label, group_label, cell, seed):
     return rng.permutation(ids)[inverse].astype(np.int64)
 
 
+def scan_faces(xyz, seg_label, group_label, cell, seed, bridges=0):
+    """A synthetic mesh over a scan: xyz (v, 3) f32, seg_label, group_label (v,), cell > 0 -> faces (F, 3) int32 in seeded order.
+    The vertices of every (seg_label, group_label) instance form ONE connected piece and no edge joins two instances: an instance's
+    vertices are ordered by their cube of side `cell` (scan_segments' cubes) and in seeded order inside a cube, a triangle strip runs
+    over that order (an instance of two vertices gets one degenerate face, of one vertex none), and half as many seeded triangles again
+    join vertices at most 8 places apart in it.  bridges: that many more faces (a, b, b), each ONE edge between two instances, all
+    different -- real meshes join a chair to its floor; needs two instances."""
+    xyz = np.asarray(xyz, np.float32)
+    v = xyz.shape[0]
+    if xyz.shape != (v, 3) or len(seg_label) != v or len(group_label) != v or not cell > 0 or bridges < 0:
+        raise ValueError("scan_faces: xyz (v, 3) with v labels of each kind, cell > 0 and bridges >= 0 expected, got %s, %d, %d, cell = %r, "
+                         "bridges = %r" % (xyz.shape, len(seg_label), len(group_label), cell, bridges))
+    rng = np.random.default_rng(15485863 * int(seed) + 17)
+    cubes = np.floor(xyz.astype(np.float64) / float(cell)).astype(np.int64)
+    keys = np.concatenate((np.asarray(seg_label, np.int64).reshape(v, 1), np.asarray(group_label, np.int64).reshape(v, 1)), axis=1)
+    _, inst = np.unique(keys, axis=0, return_inverse=True)
+    inst = inst.reshape(-1)
+    order = np.lexsort((rng.random(v), cubes[:, 2], cubes[:, 1], cubes[:, 0], inst))       # by instance, then cube, then seeded
+    at = inst[order]
+    pos = np.arange(v)
+    first = np.concatenate(([True], at[1:] != at[:-1])) if v else np.zeros(0, bool)
+    start = np.maximum.accumulate(np.where(first, pos, 0)) if v else pos                   # where each vertex's instance starts in `order`
+    count = np.bincount(at, minlength=1)[at] if v else pos
+    stop = start + count                                                                    # and where it stops
+    strip = pos[pos + 2 < stop]
+    faces = [np.stack((order[strip], order[strip + 1], order[strip + 2]), axis=1)]
+    pair = pos[first & (count == 2)]
+    faces.append(np.stack((order[pair], order[pair + 1], order[pair + 1]), axis=1) if pair.size else np.zeros((0, 3), np.int64))
+    extra = rng.permutation(v)[:v // 2]
+    j, k = rng.integers(1, 9, size=extra.size), rng.integers(1, 9, size=extra.size)
+    inside = (extra + j + k < stop[extra]) if extra.size else np.zeros(0, bool)
+    extra, j, k = extra[inside], j[inside], k[inside]
+    faces.append(np.stack((order[extra], order[extra + j], order[extra + j + k]), axis=1) if extra.size else np.zeros((0, 3), np.int64))
+    if bridges:
+        if v == 0 or at[-1] == at[0]:
+            raise ValueError("scan_faces: bridges need two instances")
+        seen, rows = set(), []
+        while len(rows) < bridges:
+            a, b = (int(x) for x in rng.integers(0, v, size=2))
+            if inst[a] != inst[b] and (min(a, b), max(a, b)) not in seen:
+                seen.add((min(a, b), max(a, b)))
+                rows.append((a, b, b))
+        faces.append(np.array(rows, np.int64))
+    faces = np.concatenate(faces)
+    return np.ascontiguousarray(faces[rng.permutation(faces.shape[0])].astype(np.int32))
+
+
 def batch(kind, b, n, seed0=0):
     f = {"U": cloud_u, "D": cloud_d, "S": cloud_s}[kind]
     return np.stack([f(n, seed0 + i) for i in range(b)]).astype(np.float32)

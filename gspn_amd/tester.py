@@ -40,6 +40,8 @@ class Tester:
     (test.py:137-139, :136), label_map with one entry per category; vote_th: the segment vote's threshold in [0, 1), read by run_vertices for
     a scan that brings 'segments' and by nothing else; mask_nms_th: None, or the IoU in [0, 1) above which run_vertices suppresses a
     per-vertex mask that copies an earlier one of its label; run() and the captured predict step never read it.
+    min_component (an int >= 1, or None) and min_component_share (in [0, 1]): run_vertices drops the components of a mask that are smaller
+    than that many vertices or than that share of the mask's largest, for a scan that brings 'faces' (DESIGN.md 4.25); nothing else reads them.
 
     The variables are created by one rpointnet_inference pass over the first batch, in the reference's order.
     captured=True: rpointnet_inference, scene_predictions, the AP counts and the semantic IoU counts replay from one graph.CapturedStep.
@@ -48,7 +50,8 @@ class Tester:
     Every variable, the moving statistics included, is left as it was: nothing here runs in training mode."""
 
     def __init__(self, config, data, scans=None, batch_size=1, seed=0, captured=True, fused_crop=False, sem_conf_th=0.01, fb_conf_th=0.01,
-                 mask_th=0.4, label_map=SCANNET_LABEL_MAP, max_captures=8, vote_th=0.5, mask_nms_th=None):
+                 mask_th=0.4, label_map=SCANNET_LABEL_MAP, max_captures=8, vote_th=0.5, mask_nms_th=None, min_component=None,
+                 min_component_share=0.0):
         if not isinstance(data, DeviceDataset):
             raise TypeError("Tester: data must be a train.DeviceDataset")
         if data.is_augment or data.permute_points:
@@ -73,6 +76,10 @@ class Tester:
         self.mask_nms_th = None if mask_nms_th is None else float(mask_nms_th)      # run_vertices alone: mask NMS on every scan
         if self.mask_nms_th is not None and not 0.0 <= self.mask_nms_th < 1.0:
             raise ValueError("Tester: mask_nms_th must lie in [0, 1), got %r" % self.mask_nms_th)
+        self.min_component, self.min_component_share = None, 0.0                   # run_vertices alone: a scan that brings 'faces' 
+        if min_component is not None:
+            from .components import _parameters
+            self.min_component, self.min_component_share = _parameters(min_component, min_component_share, "Tester")
         self.dev = data.pc.device
         self.store = tf_util.set_variable_store(tf_util.VariableStore(device=self.dev, seed=self.seed))
 
@@ -232,12 +239,15 @@ class Tester:
         snapped to them at the tester's vote_th: the ids are compacted, scan_predictions votes, the files and the AP come
         from the voted masks and the IoU counts from the voted labels; a scan without goes the way it always went.  With the tester's
         mask_nms_th every scan's masks then pass mask NMS: a suppressed mask is empty, so it is not written and not counted.
+        With the tester's min_component a scan that brings 'faces' ((F, 3) integers: its mesh's triangles, io_util.read_ply_faces) has the
+        small components of its masks dropped behind the vote and before mask NMS; a scan without goes as it went.
         The scenes run batched through the same step as run(); behind it lift.scan_predictions runs eagerly once per scan, V differing from scan to scan.  out_dir:
         <out_dir>/pred_vertices/<scan>.txt with pred_mask/, one line per vertex in every mask, and, where vertices(k) has labels,
         <out_dir>/gt_vertices/<scan>.txt.  evaluate: AP per scan through InstanceAP at B = 1 and the semantic IoU counts of
         sem_class_logits[src] against the vertices' labels -> run()'s dict, also written to <out_dir>/pred_vertices/
         semantic_instance_evaluation.txt; evaluate=False -> None.  run()'s own outputs and every variable are left as they are."""
         from .lift import scan_predictions
+        from .components import mesh_faces
         from .segments import compact_segments
         metric = InstanceAP(int(self.cfg.NUM_CATEGORY), label_map=self.label_map) if evaluate else None
         c = int(self.cfg.NUM_CATEGORY)
@@ -261,8 +271,12 @@ class Tester:
                                          % (k, xyz.shape[0], tuple(raw.shape)))
                     compact, nseg = compact_segments(raw)
                     voted = dict(segments=compact, num_segments=nseg, vote_th=self.vote_th)
+                cleaned = {}
+                if self.min_component is not None and "faces" in scan:          # 4.25: behind the vote, before the order and mask NMS
+                    cleaned = dict(faces=mesh_faces(scan["faces"], xyz.shape[0]), min_component=self.min_component,
+                                   min_component_share=self.min_component_share)
                 pred = scan_predictions(out["lift"], s, xyz, pc=self.buf["pc"], label_map=self.label_map, **self.thresholds, **voted,
-                                        mask_nms_th=self.mask_nms_th)        # 4.24: behind the vote, on the rows in output order
+                                        mask_nms_th=self.mask_nms_th, **cleaned)        # 4.24: behind the vote, on the rows in output order
                 labelled = "seg_label" in scan and "group_label" in scan
                 if evaluate and not labelled:
                     raise ValueError("Tester.run_vertices: vertices(%d) has no 'seg_label' and 'group_label' to evaluate against" % k)

@@ -58,7 +58,8 @@ extern "C" {
  * Additive at 21: gspn_lift_masks (+ gspn_lift_part_doubles): predictions on a scan's own vertices.
  * Additive at 21: gspn_nearest_point (+ gspn_nearest_point_ws_bytes): exact one-nearest search over a cell grid in global memory.
  * Additive at 21: gspn_segment_vote, gspn_segment_label_vote (+ their _ws_bytes): masks and labels snapped to a scan's segments.
- * Additive at 21: gspn_mask_overlaps, gspn_mask_nms (+ their _ws_bytes): duplicate instance masks suppressed by pairwise IoU. */
+ * Additive at 21: gspn_mask_overlaps, gspn_mask_nms (+ their _ws_bytes): duplicate instance masks suppressed by pairwise IoU.
+ * Additive at 21: gspn_mask_components, gspn_mask_component_filter (+ their _ws_bytes): fragments cut off on the mesh dropped from masks. */
 #define GSPN_ABI_VERSION 21
 int gspn_dist_policy(void);
 int gspn_abi_version(void);
@@ -926,6 +927,43 @@ int gspn_mask_overlaps(int b, int r, int v, const unsigned char* masks, void* ws
 long gspn_mask_nms_ws_bytes(int b, int r, int v);
 int gspn_mask_nms(int b, int r, int v, const unsigned char* masks, const int* count, const int* labels, double iou_th, void* ws,
                   unsigned char* out, unsigned char* keep, int* mask_points, void* stream);
+
+/* ---------------- mask components (gspn_amd/csrc/components.hip, additive at ABI 21) ----------------------------------------- */
+
+/* One scan: r mask rows of v bytes, any nonzero byte set, and f triangles faces (f,3) i32.  The edges of a face (a, b, c) are {a,b}, {b,c},
+ * {a,c}; an edge with an end outside [0, v) is ignored, duplicate and degenerate faces are harmless.  The components of row k are the
+ * connected components of its set vertices under the edges whose two ends are both set in row k; rows are independent.
+ *
+ * gspn_mask_components:
+ *   comp[k][x] (r,v) i32 = the smallest vertex of x's component in row k, -1 where x is not set
+ *   ncomp[k] (r) i32     = the number of components of row k
+ *   largest[k] (r) i32   = the vertex count of its largest component, 0 for an empty row
+ * gspn_mask_component_filter: a component of s vertices is KEPT iff s >= min_vertices and (double)s >= min_share * (double)largest[k], one
+ * IEEE double multiply and a non-strict compare.  min_vertices >= 1, min_share a double in [0, 1]; 1 keeps the largest component(s) alone,
+ * ties included; (1, 0) is the identity up to the normalisation of a nonzero byte to 1.
+ *   out[k][x] (r,v) u8     = 1 iff x is set and its component is kept, else 0; every byte written
+ *   mask_points[k] (r) i32 = the set bytes of out[k]
+ *   ncomp[k], nkept[k] (r) i32 = the components of row k, and those kept
+ * out may be masks itself.
+ *
+ * A lock-free union-find whose loops all carry the bound v; ncomp[k] = -1 marks a row in which a loop reached it, which a correct build
+ * never does.  Integer atomics only: the same bits on every call.  Row offsets are 64-bit: r * v may exceed 2^31.  ws:
+ * gspn_mask_components_ws_bytes(r, v, f) -- v * ceil(r / 64) 64-bit words, then, each 16-byte aligned, r * v and r i32 -- or
+ * gspn_mask_component_filter_ws_bytes(r, v, f) -- the same, then r * v and r i32 more -- bytes (0 for sizes the call declines, and for r or
+ * v == 0), 16-byte aligned; it need not be initialised and nothing is read from it that the call did not write.
+ * GSPN_ERR_ARG for a negative size, a null pointer (ws included; faces may be null when f == 0), min_vertices < 1, min_share NaN or outside
+ * [0, 1]; GSPN_ERR_UNSUPPORTED for r > GSPN_MASK_COMPONENTS_MAX_R, v > GSPN_MASK_COMPONENTS_MAX_V, f > GSPN_MASK_COMPONENTS_MAX_F or a ws
+ * that is not 16-byte aligned, all before anything is launched; r or v == 0 then returns 0, and with f == 0 every set vertex is its own
+ * component.  No host synchronisation, nothing allocated, static shapes: a call with a caller-held ws captures in a graph. */
+#define GSPN_MASK_COMPONENTS_MAX_R 1024
+#define GSPN_MASK_COMPONENTS_MAX_V (1 << 24)
+#define GSPN_MASK_COMPONENTS_MAX_F (1 << 26)
+long gspn_mask_components_ws_bytes(int r, int v, int f);
+int gspn_mask_components(int r, int v, int f, const unsigned char* masks, const int* faces, void* ws, int* comp, int* ncomp, int* largest,
+                         void* stream);
+long gspn_mask_component_filter_ws_bytes(int r, int v, int f);
+int gspn_mask_component_filter(int r, int v, int f, const unsigned char* masks, const int* faces, int min_vertices, double min_share, void* ws,
+                               unsigned char* out, int* mask_points, int* ncomp, int* nkept, void* stream);
 
 /* ---------------- train.py: the per-step batch, the reference's optimisers, the running loss sums (gspn_amd/csrc/train.hip, ABI 20) -------
  *

@@ -49,7 +49,10 @@
             -- at the scene's own points and at --lift-vertices vertices, as they are and with every row doubled: mask_overlaps against
             masks.float() @ masks.float().T on the device, mask_nms whole (its own workspace, and one the caller holds), and
             scan_predictions with segments with and without mask_nms_th, alternating in one process
-  evaluate  the instance AP counts of one batch (gspn_amd/evaluate.py) on synthetic masks at Config(istrain=False)'s widths -- 100 rows, 100
+  components  mask components (gspn_amd/components.py) on the same rows, synth.scan_faces over `segments`' instances as the mesh (a bridge
+            per 1000 vertices): mask_components and component_filter (their own workspace, and one the caller holds) against iterated
+            scatter_reduce(amin) over the set edges in torch on the device, and scan_predictions with segments with and without the stage
+  evaluate the instance AP counts of one batch (gspn_amd/evaluate.py) on synthetic masks at Config(istrain=False)'s widths -- 100 rows, 100
             groups, 19 categories, the benchmark's 10 thresholds: instance_overlaps against the same counts written in torch on the device
             (masks.float() against a one-hot of seg * G + group), each alone and in front of instance_match, alternating in one process,
             and the two kernels replayed from a captured graph; whether the counts are equal
@@ -71,6 +74,7 @@ Prints one JSON line per (shape, measurement): median / min milliseconds over --
     python tools/spn_step.py --shapes 1x18000 --measures lift --iters 30
     python tools/spn_step.py --shapes 1x18000 --measures segments --warmup 5 --iters 30
     python tools/spn_step.py --shapes 1x18000 --measures mask_nms --warmup 5 --iters 30
+    python tools/spn_step.py --shapes 1x18000 --measures components --warmup 5 --iters 30
     python tools/spn_step.py --shapes 2x18000,8x32768 --measures train --iters 20
     python tools/spn_step.py --shapes 2x18000 --measures evaluate --iters 30
     python tools/spn_step.py --shapes 1x150000 --measures data_prep --iters 9
@@ -884,6 +888,74 @@ def measure_mask_nms(a, shape, b, n, dev):
     print(json.dumps({"shape": shape, "kind": a.kind, "measure": "mask_nms", "rows": m, "iters": a.iters, **res}), flush=True)
 
 
+def mask_components_torch(masks, faces):
+    """components.mask_components' comp in torch on the device, what a user would write: the labels start as the vertex's own index, every
+    edge whose two ends are set in a row passes the smaller label of its ends to both with scatter_reduce(amin), over all rows at once,
+    until nothing changes (one read-back per round) -> comp (R, V) int32"""
+    r, v = masks.shape
+    f = faces.long()
+    e = torch.cat((f[:, [0, 1]], f[:, [1, 2]], f[:, [0, 2]]))
+    e = e[((e >= 0) & (e < v)).all(1)]
+    on = masks != 0
+    k, j = torch.nonzero(on[:, e[:, 0]] & on[:, e[:, 1]], as_tuple=True)               # (row, edge) pairs with both ends set
+    a, b = k * v + e[j, 0], k * v + e[j, 1]
+    label = torch.arange(v, device=masks.device).repeat(r)
+    base = torch.arange(r, device=masks.device).repeat_interleave(v) * v
+    while True:
+        low = torch.minimum(label[a], label[b])
+        new = label.scatter_reduce(0, a, low, "amin").scatter_reduce(0, b, low, "amin")
+        new = new[base + new]                                                          # one pointer jump: a label's own label
+        if torch.equal(new, label):
+            break
+        label = new
+    return torch.where(on, label.view(r, v), -1).int()
+
+
+def measure_components(a, shape, b, n, dev):
+    """--measures components: the rows scan_predictions leaves in output order behind the segment vote, for `segments`'
+    inputs -- 100 rows -- on the scene's own points and on synthetic scans of --lift-vertices vertices, with synth.scan_faces over
+    `segments`' instances as the mesh: mask_components and component_filter with a workspace they allocate and with one the caller holds,
+    the same labelling in torch on the device (iterated scatter_reduce(amin) to a fixed point), and scan_predictions with segments with
+    and without the stage, alternating in one process.  Call times by device events."""
+    from gspn_amd import _lib, lift
+    from gspn_amd import components as MC
+    from gspn_amd import segments as SG
+    RP, pc, masks, ep, det_rois, (m, p, c, ns) = predict_inputs(a, b, n, dev)
+    own = pc[0].contiguous()
+    res = {}
+    for v in [n] + [int(t) for t in a.lift_vertices.split(",") if t]:
+        xyz = synth.scan_vertices(own.cpu().numpy(), np.zeros(n, np.int32), np.zeros(n, np.int32), v, 3)[0]
+        cube = np.floor(xyz.astype(np.float64)).astype(np.int64)
+        group = ((cube[:, 0] * 7 + cube[:, 1]) * 5 + cube[:, 2]).astype(np.int32)                    # instances: the 1 m cubes of the room
+        seg, s = SG.compact_segments(torch.from_numpy(synth.scan_segments(xyz, group % c, group, 0.25, 5)).to(dev))
+        faces = MC.mesh_faces(synth.scan_faces(xyz, group % c, group, 0.25, 5, bridges=v // 1000), v)
+        verts = torch.from_numpy(xyz).to(dev)
+        pred = lift.scan_predictions(ep, 0, verts, pc=pc, segments=seg, num_segments=s)
+        rows = pred["masks"][0].contiguous()
+        nf = int(faces.shape[0])
+        ws_c = torch.empty((int(_lib.lib().gspn_mask_components_ws_bytes(m, v, nf)),), dtype=torch.uint8, device=dev)
+        ws_f = torch.empty((int(_lib.lib().gspn_mask_component_filter_ws_bytes(m, v, nf)),), dtype=torch.uint8, device=dev)
+        held = torch.empty_like(rows)
+        comp, ncomp, largest = MC.mask_components(rows, faces)
+        out, points, _, nkept = MC.component_filter(rows, faces, min_vertices=100, min_share=0.1)
+        entry = res.setdefault("at_%d" % v, {})
+        entry.update({"mask_bytes": m * v, "faces": nf, "set_share": round(float((rows != 0).float().mean()), 5),
+                      "components": int(ncomp.sum()), "largest": int(largest.max()), "kept": int(nkept.sum()),
+                      "vertices_dropped": int((rows != 0).sum()) - int(points.sum()), "bound_never_reached": bool((ncomp >= 0).all()),
+                      "comp_equals_torch": bool(torch.equal(comp, mask_components_torch(rows, faces)))})
+        stage = dict(faces=faces, min_component=100, min_component_share=0.1)
+        entry.update(timed_alternating({
+            "mask_components": lambda: MC.mask_components(rows, faces),
+            "mask_components_held_ws": lambda: MC.mask_components(rows, faces, ws=ws_c),
+            "mask_components_torch": lambda: mask_components_torch(rows, faces),
+            "component_filter": lambda: MC.component_filter(rows, faces, min_vertices=100, min_share=0.1),
+            "component_filter_held_ws_and_out": lambda: MC.component_filter(rows, faces, min_vertices=100, min_share=0.1, out=held, ws=ws_f),
+            "scan_predictions_segments": lambda: lift.scan_predictions(ep, 0, verts, pc=pc, segments=seg, num_segments=s),
+            "scan_predictions_segments_components": lambda: lift.scan_predictions(ep, 0, verts, pc=pc, segments=seg, num_segments=s, **stage)},
+            a.warmup, a.iters))
+    print(json.dumps({"shape": shape, "kind": a.kind, "measure": "components", "rows": m, "iters": a.iters, **res}), flush=True)
+
+
 def instance_counts_torch(masks, pred_class, seg, group, c, g):
     """instance_overlaps' four outputs in torch on the device: masks.float() against a one-hot of seg * G + group, a (B, N, C * G) float tensor"""
     live = (seg > 0) & (seg < c) & (group >= 0) & (group < g)
@@ -1115,6 +1187,8 @@ def main():
             measure_segments(a, shape, b, n, dev)
         if "mask_nms" in measures:
             measure_mask_nms(a, shape, b, n, dev)
+        if "components" in measures:
+            measure_components(a, shape, b, n, dev)
         if "train" in measures:
             measure_train(a, shape, b, n, dev)
         if "evaluate" in measures:

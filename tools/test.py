@@ -26,6 +26,10 @@ and, on top of either, the segment vote (masks and semantic labe
 and mask NMS (a per-vertex mask that copies an earlier one of its label is emptied before the files and the figures):
   --mask_nms T       with --mesh_path or --synthetic_vertices: suppress a mask whose IoU with an earlier kept one of its label is above T,
                      in [0, 1); behind the segment vote where --segments is given [default: off]
+and mask components (the fragments of a per-vertex mask that the mesh's edges do not join to its body are dropped):
+  --components N     with --mesh_path (the faces of each scan's <scan>_vh_clean_2.ply) or --synthetic_vertices (synth.scan_faces): drop a
+                     component of fewer than N >= 1 vertices; behind the segment vote, before mask NMS [default: off]
+  --component_share S   with --components: also drop a component smaller than S of its mask's largest; in [0, 1] [default: 0]
 
     python tools/test.py --synthetic 5 --num_point 4096 --num_sample 64 --num_category 9 --batch_size 2 --model_path log/model.ckpt
     python tools/test.py --cache val.pt --list scannet_val.txt --model_path log_heads/model.ckpt --batch_size 8
@@ -35,6 +39,8 @@ and mask NMS (a per-vertex mask that copies an earlier one of it
         --mesh_path scannet/mesh/scans --label_path scannet/label/scans --segments
     python tools/test.py --cache val.pt --list scannet_val.txt --model_path log_heads/model.ckpt --batch_size 8 \\
         --mesh_path scannet/mesh/scans --label_path scannet/label/scans --segments --mask_nms 0.5
+    python tools/test.py --cache val.pt --list scannet_val.txt --model_path log_heads/model.ckpt --batch_size 8 \\
+        --mesh_path scannet/mesh/scans --label_path scannet/label/scans --segments --components 100 --component_share 0.1 --mask_nms 0.5
 """
 import argparse
 import os
@@ -79,6 +85,8 @@ def parser():
     ap.add_argument('--vote_th', type=float, default=0.5, help='the share of a segment above which it is set [default: 0.5]')
     ap.add_argument('--segment_cell', type=float, default=0.25, help='side of a synthetic segment (with --synthetic_vertices) [default: 0.25]')
     ap.add_argument('--mask_nms', type=float, default=None, help='suppress per-vertex masks above this IoU with an earlier one of their label [default: off]')
+    ap.add_argument('--components', type=int, default=None, help='drop the components of a per-vertex mask with fewer vertices than this [default: off]')
+    ap.add_argument('--component_share', type=float, default=0.0, help="and those smaller than this share of the mask's largest [default: 0]")
     return ap
 
 
@@ -101,28 +109,33 @@ def synthetic_cache(a):
     return out
 
 
-def synthetic_vertices(cache, v, seed, segment_cell=None):
+def synthetic_vertices(cache, v, seed, segment_cell=None, face_cell=None):
     """vertices(k) of Tester.run_vertices for the scenes of synthetic_cache: synth.scan_vertices around scene k, seeded with seed + k;
-    with a segment_cell also 'segments', synth.scan_segments of that scan with the same seed"""
+    with a segment_cell also 'segments', synth.scan_segments of that scan with the same seed; with a face_cell also 'faces',
+    synth.scan_faces of it"""
     def vertices(k):
         xyz, seg, group = synth.scan_vertices(cache["pc"][k].numpy(), cache["seg_label"][k].numpy(), cache["group_label"][k].numpy(), v, seed + k)
         out = {"xyz": xyz, "seg_label": seg, "group_label": group}
         if segment_cell is not None:
             out["segments"] = synth.scan_segments(xyz, seg, group, segment_cell, seed + k)
+        if face_cell is not None:
+            out["faces"] = synth.scan_faces(xyz, seg, group, face_cell, seed + k)
         return out
     return vertices
 
 
-def mesh_vertices(mesh_path, label_path, scans, device, segments=False):
+def mesh_vertices(mesh_path, label_path, scans, device, segments=False, faces=False):
     """vertices(k) of Tester.run_vertices from ScanNet's files: the vertices of <mesh_path>/<scan>/<scan>_vh_clean_2.ply as
     tools/data_prep.py reads them and, with a label_path, their labels through data_prep.collect_label and dataset.remap_labels;
-    segments: also 'segments', data_prep.read_segments of the scan"""
+    segments: also 'segments', data_prep.read_segments of the scan; faces: also 'faces', io_util.read_ply_faces of the same file"""
     import numpy as np
     from gspn_amd import data_prep, dataset, io_util
 
     def vertices(k):
         scan = scans[k]
         out = {"xyz": np.ascontiguousarray(io_util.read_color_ply(os.path.join(mesh_path, scan, scan + "_vh_clean_2.ply"))[:, :3], np.float32)}
+        if faces:
+            out["faces"] = io_util.read_ply_faces(os.path.join(mesh_path, scan, scan + "_vh_clean_2.ply"))
         if label_path:
             sem, ins, _ = data_prep.collect_label(label_path, scan, device=device)
             group, seg, _ = dataset.remap_labels(ins.unsqueeze(0), sem.unsqueeze(0), max(int(ins.max()), 0) + 1)
@@ -171,6 +184,12 @@ def main(argv=None):
         raise SystemExit("--mask_nms goes with the vertex modes: --mesh_path DIR or --synthetic_vertices V")
     if a.mask_nms is not None and not 0.0 <= a.mask_nms < 1.0:
         raise SystemExit("--mask_nms must lie in [0, 1)")
+    if a.components is None and a.component_share != 0.0:
+        raise SystemExit("--component_share goes with --components N")
+    if a.components is not None and not (a.synthetic_vertices or a.mesh_path):
+        raise SystemExit("--components goes with the vertex modes: --mesh_path DIR or --synthetic_vertices V")
+    if a.components is not None and (a.components < 1 or not 0.0 <= a.component_share <= 1.0):
+        raise SystemExit("--components must be at least 1 and --component_share must lie in [0, 1]")
     if not 2 <= a.num_category <= len(SCANNET_LABEL_MAP):
         raise SystemExit("--num_category must lie in [2, %d], the classes of the ScanNet label map" % len(SCANNET_LABEL_MAP))
     dev = torch.device("cuda", a.gpu)
@@ -184,11 +203,13 @@ def main(argv=None):
     if scans is not None and len(scans) != len(data):
         raise SystemExit("%s names %d scans, the cache holds %d scenes" % (a.list, len(scans), len(data)))
     tester = Tester(config_of(a), data, scans=scans, batch_size=a.batch_size, seed=a.seed, captured=not a.eager,
-                    label_map=SCANNET_LABEL_MAP[:a.num_category], vote_th=a.vote_th, mask_nms_th=a.mask_nms)
+                    label_map=SCANNET_LABEL_MAP[:a.num_category], vote_th=a.vote_th, mask_nms_th=a.mask_nms,
+                    min_component=a.components, min_component_share=a.component_share)
     tester.restore(a.model_path, scope=a.restore_scope)
     if a.mesh_path or a.synthetic_vertices:
-        vertices = (mesh_vertices(a.mesh_path, a.label_path, scans, dev, a.segments) if a.mesh_path
-                    else synthetic_vertices(cache, a.synthetic_vertices, a.seed, a.segment_cell if a.segments else None))
+        vertices = (mesh_vertices(a.mesh_path, a.label_path, scans, dev, a.segments, a.components is not None) if a.mesh_path
+                    else synthetic_vertices(cache, a.synthetic_vertices, a.seed, a.segment_cell if a.segments else None,
+                                            a.segment_cell if a.components is not None else None))
         result = tester.run_vertices(None if a.no_files else a.out, vertices, evaluate=bool(a.synthetic_vertices or a.label_path))
         if result is None:
             print("per-vertex masks written to %s (no --label_path: nothing to evaluate against)" % os.path.join(a.out, "pred_vertices"))

@@ -200,6 +200,7 @@ SPECIAL = {
     "gspn_mask_nms_ws_bytes": ([_I, _I, _I], _L),
     "gspn_mask_components_ws_bytes": ([_I, _I, _I], _L),
     "gspn_mask_component_filter_ws_bytes": ([_I, _I, _I], _L),
+    "gspn_grid_blocks": ([_L, _I], _L),
 }
 
 ABI_VERSION = 21       # == GSPN_ABI_VERSION of include/gspn_hip.h this binding was written against

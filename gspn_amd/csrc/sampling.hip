@@ -986,6 +986,12 @@ extern "C" int gspn_probsample(int b, int n, int m, const float* inp_p, const fl
 
 extern "C" int gspn_dist_policy(void) { return GSPN_DIST_POLICY; }
 extern "C" int gspn_abi_version(void) { return GSPN_ABI_VERSION; }
+// the grid a grid-stride launcher of this build gives `total` items in blocks of `block` threads (grid_for, common.h): lets a test prove
+// that its shape takes some threads through a second loop trip, whatever the cap of the build is
+extern "C" long gspn_grid_blocks(long total, int block) {
+    if (total < 0 || block < 1) return GSPN_ERR_ARG;
+    return (long)grid_for(total, block);
+}
 extern "C" int gspn_fill_zero(void* ptr, long bytes, void* stream) {
     if (bytes < 0) return GSPN_ERR_ARG;
     if (bytes == 0) return 0;

@@ -63,6 +63,9 @@ extern "C" {
 #define GSPN_ABI_VERSION 21
 int gspn_dist_policy(void);
 int gspn_abi_version(void);
+/* Additive at 21: gspn_grid_blocks.  The number of workgroups this build launches for a grid-stride kernel over `total` items in blocks of
+ * `block` threads (the capped grid every elementwise and gather / scatter launcher uses); GSPN_ERR_ARG for total < 0 or block < 1. */
+long gspn_grid_blocks(long total, int block);
 
 /* ---------------- tf_ops/sampling ---------------------------------------------------- */
 

@@ -34,6 +34,13 @@ __device__ __forceinline__ float dist2_cuda(float a, float b, float c) {
 }
 // Host-compiled reference loops (g++ -O2, no FMA): tf_interpolate.cpp:74
 __device__ __forceinline__ float dist2_host(float a, float b, float c) { return (a * a + b * b) + c * c; }
+// Absolute part of the margin of the 3-NN kernels' cheap rejection test (|p|^2 - 2 p.q against b3 - |q|^2; interpolate.hip,
+// threenn_nested.hip).  Their margin is relative, 4e-6 (|p| + |q|)^2, and underflows together with the squared distances of a cloud at a
+// tiny scale, where every rounding of the two evaluations is instead up to half of the fixed subnormal spacing 2^-149.  About a dozen
+// roundings take part: 2^-140 covers them 40 times over and vanishes against any normal margin.
+#define NN_MARGIN_FLOOR 0x1p-140f
+// Smallest normal float: a squared distance below it has lost the relative precision the searches' geometric arguments count on.
+#define GSPN_FLT_MIN 0x1p-126f
 
 // v_min_f32 without the canonicalising v_max the compiler puts in front of fminf() when it cannot
 // prove an operand is not a signalling NaN (one extra VALU per point in the FPS loop).  Inputs

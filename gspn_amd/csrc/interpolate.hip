@@ -79,7 +79,9 @@ __global__ __launch_bounds__(NN_BLOCK) void three_nn_kernel(int b, int n, int m,
 #pragma unroll
         for (int u = 0; u < NN_Q; ++u) {
             const float r = sqrtf(pm) + qn[u];
-            margin[u] = 4e-6f * r * r;                   // >> 8 ulp of (|p| + |q|)^2: both evaluations err by a few ulp of that scale
+            // >> 8 ulp of (|p| + |q|)^2: both evaluations err by a few ulp of that scale.  Where that scale is subnormal an ulp is the
+            // fixed 2^-149 and the product above underflows to nothing: the floor covers the dozen roundings of both evaluations there
+            margin[u] = __builtin_fmaf(4e-6f * r, r, NN_MARGIN_FLOOR);
             thr[u] = (b3[u] - qq[u]) + margin[u];        // +inf while fewer than three candidates were seen
         }
         // pad the tile to a whole batch with candidates that can never pass (|p|^2 = +inf)
@@ -372,8 +374,16 @@ __global__ __launch_bounds__(NNG_T) void three_nn_grid_kernel(int b, int n, int 
         // lies behind is at least `bound` (cells are assigned with the same lo / inv, one rounding: the 1e-3 shrink covers it many times)
         const float safe = bound * 0.999f;
         if (!(s.b3 < safe * safe)) {
-            // restart over every cell the ball of radius sqrt(b3) touches (b3 = +inf: all cells); the true three lie inside it
-            const float r = s.b3 < INFINITY ? sqrtf(s.b3) * 1.001f : INFINITY;
+            // restart over every cell the ball of radius sqrt(b3) touches (b3 = +inf: all cells); the true three lie inside it -- as long
+            // as a point beyond the cell of slack is strictly farther than b3 IN FP32: true of a normal b3 (r * r > b3), and of a subnormal
+            // or zero one only while a shrunk cell edge, squared, still exceeds it.  Where the squared distances of a tiny cloud all
+            // underflow to one value the lowest indices win from anywhere: all cells.
+            float hs = INFINITY;                                             // the shortest cell edge, shrunk like the acceptance bound
+#pragma unroll
+            for (int a = 0; a < 3; ++a)
+                if (inv[a] > 0.f) hs = fminf(hs, h[a] * 0.999f);
+            const bool ball = s.b3 < INFINITY && (s.b3 >= GSPN_FLT_MIN || hs * hs > s.b3);
+            const float r = ball ? sqrtf(s.b3) * 1.001f : INFINITY;
             s = NNBest{INFINITY, INFINITY, INFINITY, 0, 0, 0};
 #pragma unroll
             for (int a = 0; a < 3; ++a) {

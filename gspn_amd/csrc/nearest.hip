@@ -313,10 +313,20 @@ __global__ __launch_bounds__(NP_T) void nearest_query_kernel(int b, int n, int m
         if (b1 < INFINITY) {
             // go on over every cell the ball of radius sqrt(b1) touches; the nearest point lies inside it.  What was found stays: it is
             // a pair of the known set, and taking a pair twice changes nothing.
+            // The ball holds the answer as long as a point beyond the cell of slack is strictly farther than b1 IN FP32: true of a normal
+            // b1 (r * r > b1), and of a subnormal or zero one only while a shrunk cell edge, squared, still exceeds it (b1 = 0 at any
+            // ordinary scale: a query on a known point).  Where the squared distances of a tiny cloud all underflow to one value the
+            // lowest index wins from anywhere: every cell.
             const float r = sqrtf(b1) * 1.001f;
+            float hs = INFINITY;
+#pragma unroll
+            for (int a = 0; a < 3; ++a)
+                if (P.inv[a] > 0.f) hs = fminf(hs, P.h[a] * 0.999f - P.eps);
+            const bool ball = b1 >= GSPN_FLT_MIN || (hs > 0.f && hs * hs > b1);
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
-                if (P.inv[a] > 0.f) {
+                if (!ball) { c0[a] = 0; c1[a] = P.G[a] - 1; }
+                else if (P.inv[a] > 0.f) {
                     c0[a] = min(max(np_axis_cell(rel[a] - r, P.inv[a], P.G[a]) - 1, 0), c[a]);        // (one cell of slack on both sides)
                     c1[a] = max(min(np_axis_cell(rel[a] + r, P.inv[a], P.G[a]) + 1, P.G[a] - 1), c[a]);
                 }

@@ -98,7 +98,7 @@ __global__ __launch_bounds__(NNN_T) void three_nn_nested_kernel(int b, int n, in
         }
         pm = fmaxf(fmaxf(tile_pm[0], tile_pm[1]), fmaxf(tile_pm[2], tile_pm[3]));
         const float r = sqrtf(pm) + qn;
-        const float margin = 4e-6f * r * r;               // >> 8 ulp of (|p| + |q|)^2 (as three_nn_kernel)
+        const float margin = __builtin_fmaf(4e-6f * r, r, NN_MARGIN_FLOOR);      // >> 8 ulp of (|p| + |q|)^2, 2^-149 each where that is subnormal (as three_nn_kernel)
 #pragma unroll
         for (int l = 0; l < LM; ++l) thr[l] = (s[l].b3 - qq) + margin;
         __syncthreads();

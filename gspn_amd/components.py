@@ -10,26 +10,13 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .predict import _on_device, _typed
-from .segments import _workspace
+from ._args import _on_device, _out_like, _parameters, _typed, _workspace, _ws_typed
 
 __all__ = ["COMPONENTS_MAX_R", "COMPONENTS_MAX_V", "COMPONENTS_MAX_F", "mesh_faces", "mask_components", "component_filter"]
 
 COMPONENTS_MAX_R = 1024             # GSPN_MASK_COMPONENTS_MAX_R of include/gspn_hip.h: scene_rank's limit
 COMPONENTS_MAX_V = 1 << 24          # GSPN_MASK_COMPONENTS_MAX_V
 COMPONENTS_MAX_F = 1 << 26          # GSPN_MASK_COMPONENTS_MAX_F
-
-
-def _parameters(min_vertices, min_share, what):
-    """-> (int, float); ValueError for min_vertices < 1 or a min_share outside [0, 1]"""
-    if isinstance(min_vertices, bool) or int(min_vertices) != min_vertices:
-        raise ValueError("%s: min_vertices must be an integer, got %r" % (what, min_vertices))
-    min_vertices, min_share = int(min_vertices), float(min_share)
-    if min_vertices < 1 or min_vertices >= 1 << 31:
-        raise ValueError("%s: min_vertices must be at least 1, got %d" % (what, min_vertices))
-    if not 0.0 <= min_share <= 1.0:                                                 # a NaN fails both
-        raise ValueError("%s: min_share must lie in [0, 1], got %r" % (what, min_share))
-    return min_vertices, min_share
 
 
 def mesh_faces(faces, v):
@@ -67,9 +54,7 @@ def _checked(masks, faces, ws, what):
         raise ValueError("%s: expected masks (R, V) and faces (F, 3), got %s and %s" % (what, tuple(masks.shape), tuple(faces.shape)))
     if min(r, v) <= 0:
         raise ValueError("%s: empty input, masks %s" % (what, tuple(masks.shape)))
-    if ws is not None:
-        ws = _typed(ws, torch.uint8, 1, "ws")
-    return masks, faces, ws, r, v, faces.shape[0]
+    return masks, faces, _ws_typed(ws), r, v, faces.shape[0]
 
 
 def _limits(r, v, f, what):
@@ -110,17 +95,11 @@ def component_filter(masks, faces, *, min_vertices, min_share=0.0, out=None, ws=
     normalisation of a nonzero byte to 1.  Raises as mask_components does, and ValueError for a parameter outside its range."""
     masks, faces, ws, r, v, f = _checked(masks, faces, ws, "component_filter")
     min_vertices, min_share = _parameters(min_vertices, min_share, "component_filter")
-    if out is not None:
-        out = _typed(out, torch.uint8, 2, "out")
-        if tuple(out.shape) != (r, v):
-            raise ValueError("component_filter: out must be %s like masks, got %s" % ((r, v), tuple(out.shape)))
+    out = _out_like(out, (r, v), None, "component_filter")
     _limits(r, v, f, "component_filter")
     masks, faces = _on_device(masks=masks, faces=faces)
     dev = masks.device
-    if out is None:
-        out = torch.empty((r, v), dtype=torch.uint8, device=dev)
-    elif not out.is_cuda or out.device != dev or not out.is_contiguous():
-        raise ValueError("component_filter: out must be a contiguous tensor on %s" % (dev,))
+    out = _out_like(out, (r, v), dev, "component_filter")
     ws = _workspace(ws, int(L.lib().gspn_mask_component_filter_ws_bytes(r, v, f)), dev, "component_filter")
     mask_points = torch.empty((r,), dtype=torch.int32, device=dev)
     ncomp = torch.empty((r,), dtype=torch.int32, device=dev)

@@ -10,9 +10,9 @@
 // walk over stale values still descends inside x's component and ends on a vertex that WAS a root; the compare-and-swap, which executes
 // at the memory side, is what decides, and it fails on a vertex that no longer is one.
 //
-//   init     grid (chunks of 16 bytes / 256, r) over the ADDRESS of the row, as sv_count_kernel and mn_pack_kernel read: one aligned 16-byte
-//            vector per lane, the ragged ends byte by byte; parent[k][x] = set ? x : -1, size[k][x] = 0, written 64 consecutive vertices
-//            per wave and pass (the lanes trade their 16 bits by shuffles), and the row's counters zeroed
+//   init     grid (chunks of 16 bytes / 256, r) over the ADDRESS of the row (the walk of mask_rows.h), one chunk per lane;
+//            parent[k][x] = set ? x : -1, size[k][x] = 0, written 64 consecutive vertices per wave and pass (the lanes trade their 16 bits
+//            by shuffles), and the row's counters zeroed
 //   table    grid (v / 256, words): the VERTEX-MAJOR bit table, words = ceil(r / 64) 64-bit words per vertex, bit k = set in row k, read
 //            from parent (coalesced dwords) so that rows need no alignment
 //   hook     one lane per face, grid-stride: the face is read ONCE, not r times; each of its three edges ANDs its ends' words and does one
@@ -25,7 +25,7 @@
 //            one integer atomicAdd
 //   stats    one lane per (row, vertex), roots alone (comp == x): ncomp += 1, largest = max(size), one atomic of each per wave
 //   finish   (components) / apply (filter): ncomp[k] = -1 for a row in which a loop reached its bound
-//   apply    grid over the ADDRESS of out's row, one aligned 16-byte store per lane, comp read 64 consecutive vertices per wave and pass
+//   apply    grid over the ADDRESS of out's row (mask_rows.h), one chunk written per lane, comp read 64 consecutive vertices per wave and pass
 //            and the decisions traded by ballots: out = the component of the vertex is kept,
 //            size >= min_vertices and (double)size >= min_share * (double)largest; nkept and mask_points summed over the kept roots.  It
 //            reads comp and size and never masks, so out may be masks
@@ -38,21 +38,13 @@
 // is read from ws that the call did not write.
 #include "common.h"
 #include "components_args.h"
+#include "mask_rows.h"
 
 #define MC_T 256
-#define MC_VEC 16                        // bytes per aligned vector
 
 typedef unsigned long long u64;
 
 namespace {
-
-// the 4 bits "byte k of x is not zero", bit k for byte k
-__device__ __forceinline__ unsigned mc_nibble(unsigned x) {
-    const unsigned y = (((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u;      // the top bit of every nonzero byte
-    return (((y >> 7) * 0x01020408u) >> 24) & 0xFu;                                  // no two partial products share a bit: no carries
-}
-// 4 bits -> 4 bytes of 0 or 1
-__device__ __forceinline__ unsigned mc_spread(unsigned n) { return (n & 1u) | ((n & 2u) << 7) | ((n & 4u) << 14) | ((n & 8u) << 21); }
 
 // past the L1, which nobody refreshes; what the L2 holds may still be stale (see above)
 __device__ __forceinline__ int mc_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -90,7 +82,7 @@ __device__ __forceinline__ bool mc_union(int* p, int a, int b, int v) {
     return false;
 }
 
-// grid (ceil(chunks / MC_T), r).  Chunk q of a row covers its vertices [16 q - a0, 16 q - a0 + 16), a0 = the address of the row modulo 16.
+// grid (ceil(chunks / MC_T), r) over the address of the row
 __global__ __launch_bounds__(MC_T) void mc_init_kernel(int v, const unsigned char* masks, int* __restrict__ parent, int* __restrict__ size,
                                                        int* __restrict__ bad, int* __restrict__ ncomp, int* __restrict__ largest,
                                                        int* __restrict__ nkept, int* __restrict__ mask_points) {
@@ -105,27 +97,17 @@ __global__ __launch_bounds__(MC_T) void mc_init_kernel(int v, const unsigned cha
         }
     }
     const unsigned char* p = masks + (long)row * v;
-    const int a0 = (int)(reinterpret_cast<uintptr_t>(p) & (MC_VEC - 1));
-    const int i0 = (blockIdx.x * MC_T + threadIdx.x) * MC_VEC - a0;  // >= -15; < 2^24 + 16 * MC_T
-    unsigned bits = 0u;                                              // (nobody returns: the lanes trade their bits below)
-    if (i0 >= 0 && i0 + MC_VEC <= v) {
-        const uint4 x = *reinterpret_cast<const uint4*>(p + i0);     // 16-byte aligned: p + i0 = (p - a0) + 16 q
-        bits = mc_nibble(x.x) | (mc_nibble(x.y) << 4) | (mc_nibble(x.z) << 8) | (mc_nibble(x.w) << 12);
-    } else if (i0 < v) {                                             // a ragged end: the bytes outside [0, v) are not read
-        for (int k = 0; k < MC_VEC; ++k) {
-            const int i = i0 + k;
-            if (i >= 0 && i < v && p[i] != 0) bits |= 1u << k;
-        }
-    }
+    const int i0 = (blockIdx.x * MC_T + threadIdx.x) * MASK_ROW_VEC - mask_row_a0(p);    // >= -15; < 2^24 + 16 * MC_T
+    const unsigned bits = mask_row_load(p, i0, v);                   // (nobody returns: the lanes trade their bits below)
     // The wave's 64 chunks are 1024 consecutive vertices.  A lane that wrote its own 16 would put 64 bytes between one lane's dword and
     // the next (454 us at 100 x 500 000, measured); in pass t the wave writes the 64 consecutive vertices 64 t .. 64 t + 63 instead, lane l
     // taking bit l % 16 of the chunk of lane 4 t + l / 16.
     const int lane = lane_id();
-    const int first = i0 - lane * MC_VEC;                            // the first vertex of the wave's chunks, >= -15
+    const int first = i0 - lane * MASK_ROW_VEC;                      // the first vertex of the wave's chunks, >= -15
     int* par = parent + (long)row * v;
     int* sz = size + (long)row * v;
 #pragma unroll
-    for (int t = 0; t < MC_VEC; ++t) {
+    for (int t = 0; t < MASK_ROW_VEC; ++t) {
         const unsigned theirs = (unsigned)__shfl((int)bits, 4 * t + (lane >> 4), GSPN_WAVE);
         const int i = first + GSPN_WAVE * t + lane;
         if (i >= 0 && i < v) {
@@ -239,8 +221,7 @@ __global__ __launch_bounds__(MC_T) void mc_apply_kernel(int v, int min_vertices,
     const int row = blockIdx.y;
     if (blockIdx.x == 0 && threadIdx.x == 0 && bad[row] != 0) ncomp[row] = -1;      // the stats pass is over: nobody adds to it any more
     unsigned char* p = out + (long)row * v;
-    const int a0 = (int)(reinterpret_cast<uintptr_t>(p) & (MC_VEC - 1));
-    const int i0 = (blockIdx.x * MC_T + threadIdx.x) * MC_VEC - a0;  // >= -15; < 2^24 + 16 * MC_T
+    const int i0 = (blockIdx.x * MC_T + threadIdx.x) * MASK_ROW_VEC - mask_row_a0(p);    // >= -15; < 2^24 + 16 * MC_T
     const int* c = comp + (long)row * v;
     const int* sz = size + (long)row * v;
     const double floor_share = min_share * (double)largest[row];
@@ -248,11 +229,11 @@ __global__ __launch_bounds__(MC_T) void mc_apply_kernel(int v, int min_vertices,
     // comp; a lane that read its own 16 took 135 us at 100 x 500 000, measured), the ballot of the pass holds the bits of four chunks, and
     // the lane whose chunk is among them keeps its 16.
     const int lane = lane_id();
-    const int first = i0 - lane * MC_VEC;                            // the first vertex of the wave's chunks, >= -15
+    const int first = i0 - lane * MASK_ROW_VEC;                      // the first vertex of the wave's chunks, >= -15
     unsigned bits = 0u;
     int kept_roots = 0, kept_points = 0;
 #pragma unroll
-    for (int t = 0; t < MC_VEC; ++t) {
+    for (int t = 0; t < MASK_ROW_VEC; ++t) {
         const int i = first + GSPN_WAVE * t + lane;
         bool on = false;
         if (i >= 0 && i < v) {
@@ -269,21 +250,7 @@ __global__ __launch_bounds__(MC_T) void mc_apply_kernel(int v, int min_vertices,
         const u64 word = __ballot(on);
         if ((lane >> 2) == t) bits = (unsigned)(word >> (16 * (lane & 3))) & 0xFFFFu;
     }
-    if (i0 < v) {
-        if (i0 >= 0 && i0 + MC_VEC <= v) {
-            uint4 o;
-            o.x = mc_spread(bits);
-            o.y = mc_spread(bits >> 4);
-            o.z = mc_spread(bits >> 8);
-            o.w = mc_spread(bits >> 12);
-            *reinterpret_cast<uint4*>(p + i0) = o;                   // 16-byte aligned: p + i0 = (p - a0) + 16 q
-        } else {
-            for (int k = 0; k < MC_VEC; ++k) {
-                const int i = i0 + k;
-                if (i >= 0 && i < v) p[i] = (unsigned char)((bits >> k) & 1u);
-            }
-        }
-    }
+    mask_row_store(p, i0, v, bits);
     kept_roots = wave_sum_lane0(kept_roots);
     kept_points = wave_sum_lane0(kept_points);                       // <= v <= 2^24
     if (lane_id() == 0 && kept_roots != 0) {
@@ -298,8 +265,7 @@ void mc_label(hipStream_t st, int r, int v, int f, const McLayout& l, const unsi
     u64* table = reinterpret_cast<u64*>(base + l.table);
     int* size = reinterpret_cast<int*>(base + l.size);
     int* bad = reinterpret_cast<int*>(base + l.bad);
-    const int vectors = (v + 2 * (MC_VEC - 1)) / MC_VEC;             // ceil((v + a0) / 16) for the largest a0
-    const dim3 by_vector((unsigned)((vectors + MC_T - 1) / MC_T), (unsigned)r), by_vertex((unsigned)((v + MC_T - 1) / MC_T), (unsigned)r);
+    const dim3 by_vector((unsigned)((mask_row_chunks(v) + MC_T - 1) / MC_T), (unsigned)r), by_vertex((unsigned)((v + MC_T - 1) / MC_T), (unsigned)r);
     hipLaunchKernelGGL(mc_init_kernel, by_vector, dim3(MC_T), 0, st, v, masks, comp, size, bad, ncomp, largest, nkept, mask_points);
     if (f > 0) {
         hipLaunchKernelGGL(mc_table_kernel, dim3(by_vertex.x, (unsigned)l.words), dim3(MC_T), 0, st, r, v, l.words, comp, table);
@@ -340,8 +306,7 @@ extern "C" int gspn_mask_component_filter(int r, int v, int f, const unsigned ch
     int* comp = reinterpret_cast<int*>(base + l.parent);
     int* largest = reinterpret_cast<int*>(base + l.largest);
     mc_label(st, r, v, f, l, masks, faces, base, comp, ncomp, largest, nkept, mask_points);
-    const int vectors = (v + 2 * (MC_VEC - 1)) / MC_VEC;
-    hipLaunchKernelGGL(mc_apply_kernel, dim3((unsigned)((vectors + MC_T - 1) / MC_T), (unsigned)r), dim3(MC_T), 0, st, v, min_vertices, min_share,
+    hipLaunchKernelGGL(mc_apply_kernel, dim3((unsigned)((mask_row_chunks(v) + MC_T - 1) / MC_T), (unsigned)r), dim3(MC_T), 0, st, v, min_vertices, min_share,
                        comp, reinterpret_cast<int*>(base + l.size), largest, reinterpret_cast<int*>(base + l.bad), out, mask_points, ncomp, nkept);
     return gspn_launch_status();
 }

@@ -4,11 +4,11 @@
 //
 //   gspn_mask_overlaps  init    zero sizes and inter                                                                    (grid-stride)
 //                       pack    grid (blocks of 4096 vertices, r, b): the bytes become 64-bit words, ceil(v / 64) per row.  A block's 4096
-//                               bytes start at an arbitrary ADDRESS (v is arbitrary, so rows are not aligned): the block reads the 257
-//                               16-byte ALIGNED vectors that cover them, one per lane, each giving the 16 bits of its nonzero bytes to LDS;
-//                               a vector that overhangs the row's [0, v) is read byte by byte and its outside bits stay zero, so the bits
-//                               beyond v in the last word are zero.  64 lanes then cut the 64 words out of that bit string at the block's
-//                               misalignment; their popcounts, added by shuffles, go to sizes[row] with one integer atomicAdd per block
+//                               bytes start at an arbitrary address: the block reads the 257 chunks that cover them (the walk of
+//                               mask_rows.h, begun at the block's first byte), one per lane, each giving its 16 bits to LDS; the bits
+//                               outside the row's [0, v) are zero, so the bits beyond v in the last word are zero.  64 lanes then cut
+//                               the 64 words out of that bit string at the block's misalignment; their popcounts, added by shuffles, go
+//                               to sizes[row] with one integer atomicAdd per block
 //                       gram    grid (chunk groups, pairs of 32-row tiles on or above the diagonal, b): both tiles' words of a chunk of 64
 //                               words are staged in LDS (rows padded to 65 words: the 8 rows a half-wave reads fall on 8 different bank
 //                               pairs), a lane accumulates __popcll(a & b) of 4 pairs over the chunks of its group and adds what is not
@@ -20,18 +20,18 @@
 //                               ahead, sizes and labels come from LDS, and a slot of 256 rows none of which is live is passed over
 //                               (75 live rows: 34.5 us with a load per step, 30.0 with the blocks, 21.6 with the slots skipped).  It writes
 //                               keep and mask_points (size[k], or 0 for a suppressed row): the apply pass counts nothing
-//                       apply   grid (chunks of 16 bytes / 256, r, b) over the ADDRESS of out's row: a lane expands 16 bits of the packed
-//                               row -- zero for a suppressed row -- into one aligned 16-byte store; the ragged ends byte by byte.  It reads
-//                               the packed words and never masks, so out may be masks
+//                       apply   grid (chunks of 16 bytes / 256, r, b) over the ADDRESS of out's row (mask_rows.h): a lane cuts the 16 bits
+//                               of its chunk out of the packed row -- zero for a suppressed row -- and writes the chunk.  It reads the
+//                               packed words and never masks, so out may be masks
 //
 // Integer atomics only: the same bits on every call.  Row offsets are 64-bit (b * r * v exceeds 2^31).  No host synchronisation, nothing
 // allocated; nothing is read from ws that the call did not write.
 #include "common.h"
 #include "mask_nms_args.h"
+#include "mask_rows.h"
 
 #define MN_T 256
-#define MN_VEC 16                        // bytes per aligned vector
-#define MN_BLOCK_WORDS 64                // words a pack block writes: 4096 vertices, 256 vectors (+ 1 for the misalignment)
+#define MN_BLOCK_WORDS 64                // words a pack block writes: 4096 vertices, 256 chunks (+ 1 for the misalignment)
 #define MN_TILE 32                       // rows per Gram tile
 #define MN_CHUNK 64                      // words per Gram chunk
 #define MN_PAD (MN_CHUNK + 1)
@@ -43,14 +43,6 @@ typedef unsigned long long u64;
 
 namespace {
 
-// the 4 bits "byte k of x is not zero", bit k for byte k
-__device__ __forceinline__ unsigned mn_nibble(unsigned x) {
-    const unsigned y = (((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u;      // the top bit of every nonzero byte
-    return (((y >> 7) * 0x01020408u) >> 24) & 0xFu;                                  // no two partial products share a bit: no carries
-}
-// 4 bits -> 4 bytes of 0 or 1
-__device__ __forceinline__ unsigned mn_spread(unsigned n) { return (n & 1u) | ((n & 2u) << 7) | ((n & 4u) << 14) | ((n & 8u) << 21); }
-
 __global__ __launch_bounds__(MN_T) void mn_init_kernel(long nsizes, long ninter, int* __restrict__ sizes, int* __restrict__ inter) {
     for (long i = blockIdx.x * (long)MN_T + threadIdx.x; i < nsizes; i += (long)gridDim.x * MN_T) sizes[i] = 0;
     for (long i = blockIdx.x * (long)MN_T + threadIdx.x; i < ninter; i += (long)gridDim.x * MN_T) inter[i] = 0;
@@ -59,26 +51,14 @@ __global__ __launch_bounds__(MN_T) void mn_init_kernel(long nsizes, long ninter,
 // grid (ceil(words / 64), r, b)
 __global__ __launch_bounds__(MN_T) void mn_pack_kernel(int r, int v, int words, const unsigned char* masks, u64* __restrict__ packed,
                                                        int* __restrict__ sizes) {
-    __shared__ unsigned short sm[MN_T + 4];                          // 257 vectors' bits; a word reads 5 of them
+    __shared__ unsigned short sm[MN_T + 4];                          // 257 chunks' bits; a word reads 5 of them
     const long rr = (long)blockIdx.z * r + blockIdx.y;
     const unsigned char* p = masks + rr * v;
     const int vb = blockIdx.x * (MN_BLOCK_WORDS * 64);               // the block's first vertex, < v <= 2^24
-    const int a0 = (int)(reinterpret_cast<uintptr_t>(p + vb) & (MN_VEC - 1));
+    const int a0 = mask_row_a0(p + vb);
     const int tid = threadIdx.x;
-    for (int q = tid; q <= MN_T; q += MN_T) {                        // vector q covers the vertices [i0, i0 + 16); lane 0 takes the 257th
-        const int i0 = vb - a0 + MN_VEC * q;                         // >= -15
-        unsigned bits = 0u;
-        if (i0 >= 0 && i0 + MN_VEC <= v) {
-            const uint4 x = *reinterpret_cast<const uint4*>(p + i0); // 16-byte aligned: p + vb - a0 is
-            bits = mn_nibble(x.x) | (mn_nibble(x.y) << 4) | (mn_nibble(x.z) << 8) | (mn_nibble(x.w) << 12);
-        } else if (i0 < v) {                                         // a ragged end: the bytes outside [0, v) stay zero
-            for (int k = 0; k < MN_VEC; ++k) {
-                const int i = i0 + k;
-                if (i >= 0 && i < v && p[i] != 0) bits |= 1u << k;
-            }
-        }
-        sm[q] = (unsigned short)bits;
-    }
+    for (int q = tid; q <= MN_T; q += MN_T)                          // lane 0 takes the 257th chunk
+        sm[q] = (unsigned short)mask_row_load(p, vb - a0 + MASK_ROW_VEC * q, v);
     __syncthreads();
     if (tid >= GSPN_WAVE) return;
     const int w = blockIdx.x * MN_BLOCK_WORDS + tid;
@@ -210,37 +190,24 @@ __global__ __launch_bounds__(MN_T) void mn_greedy_kernel(int r, const int* __res
     }
 }
 
-// grid (ceil(chunks / MN_T), r, b).  Chunk q of a row covers its vertices [16 q - a0, 16 q - a0 + 16), a0 = the address of out's row modulo 16.
+// grid (ceil(chunks / MN_T), r, b) over the address of out's row
 __global__ __launch_bounds__(MN_T) void mn_apply_kernel(int r, int v, int words, const int* __restrict__ count, const unsigned char* __restrict__ keep,
                                                         const u64* __restrict__ packed, unsigned char* out) {
     const long rr = (long)blockIdx.z * r + blockIdx.y;
     unsigned char* p = out + rr * v;
-    const int a0 = (int)(reinterpret_cast<uintptr_t>(p) & (MN_VEC - 1));
-    const int i0 = (blockIdx.x * MN_T + threadIdx.x) * MN_VEC - a0;  // >= -15; < 2^24 + 16 * MN_T
+    const int i0 = (blockIdx.x * MN_T + threadIdx.x) * MASK_ROW_VEC - mask_row_a0(p);    // >= -15; < 2^24 + 16 * MN_T
     if (i0 >= v) return;
     const int live = min(max(count[blockIdx.z], 0), r);
     const bool gone = (int)blockIdx.y < live && keep[rr] == 0;       // uniform over the workgroup
-    const u64* pw = packed + rr * words;
-    if (i0 >= 0 && i0 + MN_VEC <= v) {
-        unsigned bits = 0u;
-        if (!gone) {
-            const int w = i0 >> 6, sh = i0 & 63;
-            u64 x = pw[w] >> sh;
-            if (sh > 64 - MN_VEC) x |= pw[w + 1] << (64 - sh);       // word w + 1 holds vertex i0 + 15 < v
-            bits = (unsigned)x & 0xFFFFu;
-        }
-        uint4 o;
-        o.x = mn_spread(bits);
-        o.y = mn_spread(bits >> 4);
-        o.z = mn_spread(bits >> 8);
-        o.w = mn_spread(bits >> 12);
-        *reinterpret_cast<uint4*>(p + i0) = o;                       // 16-byte aligned: p + i0 = (p - a0) + 16 q
-    } else {
-        for (int k = 0; k < MN_VEC; ++k) {
-            const int i = i0 + k;
-            if (i >= 0 && i < v) p[i] = gone ? 0 : (unsigned char)((pw[i >> 6] >> (i & 63)) & 1ull);
-        }
+    unsigned bits = 0u;
+    if (!gone) {                                                     // bit k = vertex i0 + k; the head chunk starts at vertex 0
+        const u64* pw = packed + rr * words;
+        const int j0 = max(i0, 0), w = j0 >> 6, sh = j0 & 63;
+        u64 x = pw[w] >> sh;
+        if (sh > 64 - MASK_ROW_VEC && w + 1 < words) x |= pw[w + 1] << (64 - sh);
+        bits = ((unsigned)x << (j0 - i0)) & 0xFFFFu;                 // (the bits beyond v in the last word are zero)
     }
+    mask_row_store(p, i0, v, bits);
 }
 
 void mn_overlaps(hipStream_t st, int b, int r, int v, const MnLayout& l, const unsigned char* masks, u64* packed, int* sizes, int* inter) {
@@ -284,8 +251,7 @@ extern "C" int gspn_mask_nms(int b, int r, int v, const unsigned char* masks, co
     int* inter = reinterpret_cast<int*>(base + l.inter);
     mn_overlaps(st, b, r, v, l, masks, packed, sizes, inter);
     hipLaunchKernelGGL(mn_greedy_kernel, dim3((unsigned)b), dim3(MN_T), 0, st, r, count, labels, iou_th, sizes, inter, keep, mask_points);
-    const int vectors = (v + 2 * (MN_VEC - 1)) / MN_VEC;             // ceil((v + a0) / 16) for the largest a0
-    hipLaunchKernelGGL(mn_apply_kernel, dim3((unsigned)((vectors + MN_T - 1) / MN_T), (unsigned)r, (unsigned)b), dim3(MN_T), 0, st, r, v, l.words,
+    hipLaunchKernelGGL(mn_apply_kernel, dim3((unsigned)((mask_row_chunks(v) + MN_T - 1) / MN_T), (unsigned)r, (unsigned)b), dim3(MN_T), 0, st, r, v, l.words,
                        count, keep, packed, out);
     return gspn_launch_status();
 }

@@ -1,10 +1,7 @@
 // mask_nms_args.h -- the host side of mask_nms.hip that needs no device: the argument checks the two launchers run before anything is
 // launched, and the layout of their workspaces.  Plain C++, no HIP header: tools/mask_nms_args_check.cpp compiles it on its own.
 #pragma once
-#include <stddef.h>
-#include <stdint.h>
-
-#include "../../include/gspn_hip.h"
+#include "stage_args.h"
 
 #define MN_MAX_R 1024                    // scene_rank's limit; the (r, r) overlap matrix of one scene is then 4 MB
 #define MN_MAX_V (1 << 24)
@@ -16,9 +13,8 @@ static inline MnLayout mn_layout(int b, int r, int v, bool nms) {
     MnLayout l;
     l.words = (int)(((long)v + 63) / 64);
     l.packed = 0;
-    l.sizes = sizeof(unsigned long long) * (size_t)b * (size_t)r * (size_t)l.words;        // a multiple of 8
-    l.sizes = (l.sizes + 15) & ~(size_t)15;
-    l.inter = (l.sizes + sizeof(int) * (size_t)b * (size_t)r + 15) & ~(size_t)15;
+    l.sizes = stage_up16(sizeof(unsigned long long) * (size_t)b * (size_t)r * (size_t)l.words);
+    l.inter = stage_up16(l.sizes + sizeof(int) * (size_t)b * (size_t)r);
     l.bytes = nms ? l.inter + sizeof(int) * (size_t)b * (size_t)r * (size_t)r : l.sizes;
     return l;
 }
@@ -30,30 +26,20 @@ static inline int mn_check_sizes(int b, int r, int v) {
     return 0;
 }
 
-// every decline of gspn_mask_overlaps, argument errors first
+// every decline of gspn_mask_overlaps, in stage_check's order
 static inline int mo_check(int b, int r, int v, const void* masks, const void* ws, const void* sizes, const void* inter) {
-    if (b < 0 || r < 0 || v < 0 || !masks || !ws || !sizes || !inter) return GSPN_ERR_ARG;
-    const int rc = mn_check_sizes(b, r, v);
-    if (rc != 0) return rc;
-    if ((reinterpret_cast<uintptr_t>(ws) & 15) != 0) return GSPN_ERR_UNSUPPORTED;
-    return 0;
+    return stage_check(stage_any_null(masks, ws, sizes, inter), mn_check_sizes(b, r, v), ws);
 }
 // every decline of gspn_mask_nms; labels may be null
 static inline int mn_check(int b, int r, int v, const void* masks, const void* count, double iou_th, const void* ws, const void* out,
                            const void* keep, const void* mask_points) {
-    if (b < 0 || r < 0 || v < 0 || !masks || !count || !ws || !out || !keep || !mask_points) return GSPN_ERR_ARG;
-    if (!(iou_th >= 0.0 && iou_th < 1.0)) return GSPN_ERR_ARG;               // a NaN fails both compares
-    const int rc = mn_check_sizes(b, r, v);
-    if (rc != 0) return rc;
-    if ((reinterpret_cast<uintptr_t>(ws) & 15) != 0) return GSPN_ERR_UNSUPPORTED;
-    return 0;
+    const bool th_ok = iou_th >= 0.0 && iou_th < 1.0;                        // a NaN fails both compares
+    return stage_check(stage_any_null(masks, count, ws, out, keep, mask_points) || !th_ok, mn_check_sizes(b, r, v), ws);
 }
 
 static inline long mo_ws_bytes(int b, int r, int v) {
-    if (mn_check_sizes(b, r, v) != 0 || b == 0 || r == 0 || v == 0) return 0;
-    return (long)mn_layout(b, r, v, false).bytes;
+    return stage_ws_bytes(mn_check_sizes(b, r, v), b == 0 || r == 0 || v == 0, [&] { return mn_layout(b, r, v, false); });
 }
 static inline long mn_ws_bytes(int b, int r, int v) {
-    if (mn_check_sizes(b, r, v) != 0 || b == 0 || r == 0 || v == 0) return 0;
-    return (long)mn_layout(b, r, v, true).bytes;
+    return stage_ws_bytes(mn_check_sizes(b, r, v), b == 0 || r == 0 || v == 0, [&] { return mn_layout(b, r, v, true); });
 }

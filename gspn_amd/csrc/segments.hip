@@ -5,10 +5,9 @@
 //
 //   gspn_segment_vote        init     zero the (r + 1) * s counters and mask_points                                       (grid-stride)
 //                            size     cnt[r][seg[i]] += 1 per segmented vertex, coalesced reads of seg
-//                            count    grid (chunks of 16 bytes / 256, r): a lane reads one 16-byte aligned vector of its row -- the vector
-//                                     grid is laid over the row's ADDRESS, so every row is read aligned whatever v is; the bytes of the
-//                                     two ragged ends come one at a time -- and leaves when it is all zero (about one (row, vertex) pair in
-//                                     a hundred lies inside a detection's box); a set byte reads seg and adds 1 to cnt[row][seg]
+//                            count    grid (chunks of 16 bytes / 256, r) over the row's ADDRESS (the walk of mask_rows.h): a lane reads the 16
+//                                     bits of one chunk and leaves when they are all zero (about one (row, vertex) pair in a hundred lies
+//                                     inside a detection's box); a set byte reads seg and adds 1 to cnt[row][seg]
 //                            decide   one lane per (row, segment): (double)cnt > vote_th * (double)size, one IEEE multiply and a strict
 //                                     compare; the wave's ballot is the decision word of its 64 segments, and the sizes of its set segments,
 //                                     added by shuffles, go to mask_points[row] with one integer atomicAdd: a set segment sets all its vertices
@@ -24,10 +23,10 @@
 // complete before the apply pass starts (stream order), and a lane of the apply pass reads only the bytes it writes.  No host
 // synchronisation, nothing allocated; nothing is read from ws that the call did not write.
 #include "common.h"
+#include "mask_rows.h"
 #include "segments_args.h"
 
 #define SV_T 256
-#define SV_VEC 16                        // bytes per lane of the count pass
 #define SV_Q 4                           // vertices per lane of the apply pass
 #define SV_ROWS 8                        // rows per workgroup of the apply pass
 
@@ -46,28 +45,18 @@ __global__ __launch_bounds__(SV_T) void sv_size_kernel(int v, int s, const int* 
     }
 }
 
-// grid (ceil(chunks / SV_T), r).  Chunk j of a row covers its vertices [16 j - a0, 16 j - a0 + 16), a0 = the row's address modulo 16.
+// grid (ceil(chunks / SV_T), r) over the row's address
 __global__ __launch_bounds__(SV_T) void sv_count_kernel(int v, int s, const unsigned char* masks, const int* __restrict__ seg, int* __restrict__ cnt) {
     const int row = blockIdx.y;
     const unsigned char* p = masks + (long)row * v;
-    const int a0 = (int)(reinterpret_cast<uintptr_t>(p) & (SV_VEC - 1));
-    const int i0 = (blockIdx.x * SV_T + threadIdx.x) * SV_VEC - a0;  // >= -15; < 2^24 + 16 * SV_T
+    const int i0 = (blockIdx.x * SV_T + threadIdx.x) * MASK_ROW_VEC - mask_row_a0(p);    // >= -15; < 2^24 + 16 * SV_T
     if (i0 >= v) return;
-    unsigned w[4] = {0u, 0u, 0u, 0u};
-    if (i0 >= 0 && i0 + SV_VEC <= v) {
-        const uint4 q = *reinterpret_cast<const uint4*>(p + i0);     // 16-byte aligned: p + i0 = (p - a0) + 16 j
-        w[0] = q.x; w[1] = q.y; w[2] = q.z; w[3] = q.w;
-    } else {                                                         // a ragged end: the bytes outside [0, v) stay zero
-        for (int b = 0; b < SV_VEC; ++b) {
-            const int i = i0 + b;
-            if (i >= 0 && i < v && p[i] != 0) w[b >> 2] |= 0xFFu << (8 * (b & 3));
-        }
-    }
-    if ((w[0] | w[1] | w[2] | w[3]) == 0u) return;
+    const unsigned bits = mask_row_load(p, i0, v);
+    if (bits == 0u) return;
     int* c = cnt + (long)row * s;
 #pragma unroll
-    for (int b = 0; b < SV_VEC; ++b) {
-        if ((w[b >> 2] >> (8 * (b & 3))) & 0xFFu) {                  // a set byte lies inside [0, v)
+    for (int b = 0; b < MASK_ROW_VEC; ++b) {
+        if ((bits >> b) & 1u) {                                      // a set byte lies inside [0, v)
             const int sg = seg[i0 + b];
             if ((unsigned)sg < (unsigned)s) atomicAdd(&c[sg], 1);
         }
@@ -184,7 +173,7 @@ extern "C" int gspn_segment_vote(int r, int v, int s, const unsigned char* masks
     const long ncnt = ((long)r + 1) * s, nwords = (long)r * l.words;
     hipLaunchKernelGGL(sv_init_kernel, dim3(grid_for(ncnt > r ? ncnt : r, SV_T)), dim3(SV_T), 0, st, ncnt, r, cnt, mask_points);
     if (s > 0) {
-        const int chunks = (v + 2 * (SV_VEC - 1)) / SV_VEC;          // ceil((v + a0) / 16) for the largest a0
+        const int chunks = mask_row_chunks(v);
         hipLaunchKernelGGL(sv_size_kernel, dim3(grid_for(v, SV_T)), dim3(SV_T), 0, st, v, s, seg, size);
         hipLaunchKernelGGL(sv_count_kernel, dim3((unsigned)((chunks + SV_T - 1) / SV_T), (unsigned)r), dim3(SV_T), 0, st, v, s, masks, seg, cnt);
         hipLaunchKernelGGL(sv_decide_kernel, dim3((unsigned)((nwords * GSPN_WAVE + SV_T - 1) / SV_T)), dim3(SV_T), 0, st, nwords, l.words, s, vote_th,

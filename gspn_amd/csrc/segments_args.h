@@ -1,10 +1,7 @@
 // segments_args.h -- the host side of segments.hip that needs no device: the argument checks the two launchers run before anything is
 // launched, and the layout of their workspaces.  Plain C++, no HIP header: tools/segments_args_check.cpp compiles it on its own.
 #pragma once
-#include <stddef.h>
-#include <stdint.h>
-
-#include "../../include/gspn_hip.h"
+#include "stage_args.h"
 
 #define SV_MAX_V (1 << 24)
 #define SV_MAX_S (1 << 24)
@@ -18,7 +15,7 @@ static inline SvLayout sv_layout(int r, int v, int s) {
     SvLayout l;
     l.words = (s + 63) / 64;
     l.cnt = 0;
-    l.bits = (sizeof(int) * ((size_t)r + 1) * (size_t)s + 15) & ~(size_t)15;
+    l.bits = stage_up16(sizeof(int) * ((size_t)r + 1) * (size_t)s);
     l.bytes = l.bits + sizeof(unsigned long long) * (size_t)r * (size_t)l.words;
     return l;
 }
@@ -45,29 +42,19 @@ static inline int sl_check_sizes(int v, int s, int c) {
     return 0;
 }
 
-// every decline of gspn_segment_vote, argument errors first
+// every decline of gspn_segment_vote, in stage_check's order
 static inline int sv_check(int r, int v, int s, const void* masks, const void* seg, double vote_th, const void* ws, const void* out,
                            const void* mask_points) {
-    if (r < 0 || v < 0 || s < 0 || !masks || !seg || !ws || !out || !mask_points) return GSPN_ERR_ARG;
-    if (!(vote_th >= 0.0 && vote_th < 1.0)) return GSPN_ERR_ARG;             // a NaN fails both compares
-    const int rc = sv_check_sizes(r, v, s);
-    if (rc != 0) return rc;
-    if ((reinterpret_cast<uintptr_t>(ws) & 15) != 0) return GSPN_ERR_UNSUPPORTED;
-    return 0;
+    const bool th_ok = vote_th >= 0.0 && vote_th < 1.0;                      // a NaN fails both compares
+    return stage_check(stage_any_null(masks, seg, ws, out, mask_points) || !th_ok, sv_check_sizes(r, v, s), ws);
 }
 static inline int sl_check(int v, int s, int c, const void* labels, const void* seg, const void* ws, const void* out) {
-    if (v < 0 || s < 0 || c < 1 || !labels || !seg || !ws || !out) return GSPN_ERR_ARG;
-    const int rc = sl_check_sizes(v, s, c);
-    if (rc != 0) return rc;
-    if ((reinterpret_cast<uintptr_t>(ws) & 15) != 0) return GSPN_ERR_UNSUPPORTED;
-    return 0;
+    return stage_check(stage_any_null(labels, seg, ws, out), sl_check_sizes(v, s, c), ws);
 }
 
 static inline long sv_ws_bytes(int r, int v, int s) {
-    if (sv_check_sizes(r, v, s) != 0 || r == 0 || v == 0) return 0;
-    return (long)sv_layout(r, v, s).bytes;
+    return stage_ws_bytes(sv_check_sizes(r, v, s), r == 0 || v == 0, [&] { return sv_layout(r, v, s); });
 }
 static inline long sl_ws_bytes(int v, int s, int c) {
-    if (sl_check_sizes(v, s, c) != 0 || v == 0) return 0;
-    return (long)sl_layout(v, s, c).bytes;
+    return stage_ws_bytes(sl_check_sizes(v, s, c), v == 0, [&] { return sl_layout(v, s, c); });
 }

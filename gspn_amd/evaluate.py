@@ -18,7 +18,8 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .predict import SCANNET_LABEL_MAP, _on_device, _typed
+from ._args import _on_device, _typed
+from .predict import SCANNET_LABEL_MAP
 
 __all__ = ["DEFAULT_OVERLAPS", "MIN_REGION_SIZE", "INSTANCE_MAX_G", "INSTANCE_MAX_CG", "INSTANCE_MATCH_MAX_R", "SCANNET_CLASS_NAMES",
            "instance_overlaps", "instance_match", "classes_from_label_ids", "InstanceAP", "average_precision", "read_predictions",

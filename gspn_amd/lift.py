@@ -15,10 +15,11 @@ V differs from scan to scan, so nothing here is meant for a captured step.  No C
 import torch
 
 from . import _lib as L
-from .components import COMPONENTS_MAX_F, _parameters, component_filter
+from ._args import _on_device, _parameters, _typed
+from .components import COMPONENTS_MAX_F, component_filter
 from .mask_nms import mask_nms
 from .nearest import nearest_point
-from .predict import SCANNET_LABEL_MAP, SCENE_RANK_MAX_R, _on_device, _typed, scene_rank
+from .predict import SCANNET_LABEL_MAP, SCENE_RANK_MAX_R, scene_rank
 from .segments import SEGMENT_MAX_COUNTERS, SEGMENT_MAX_S, segment_label_vote, segment_vote
 from .tf_interpolate import three_nn
 

@@ -8,8 +8,7 @@ words, a popcount Gram over them, integer atomics only, the same bits on every c
 import torch
 
 from . import _lib as L
-from .predict import _on_device, _typed
-from .segments import _workspace
+from ._args import _on_device, _out_like, _typed, _workspace, _ws_typed
 
 __all__ = ["MASK_NMS_MAX_R", "MASK_NMS_MAX_V", "MASK_NMS_MAX_B", "mask_overlaps", "mask_nms"]
 
@@ -51,8 +50,7 @@ def mask_overlaps(masks, ws=None):
     R > 1024, V > 2^24 or B > 65535, all before anything has run."""
     masks, single = _scenes(masks, "mask_overlaps")
     b, r, v = masks.shape
-    if ws is not None:
-        ws = _typed(ws, torch.uint8, 1, "ws")
+    ws = _ws_typed(ws)
     _limits(b, r, v, "mask_overlaps")
     masks, = _on_device(masks=masks)
     dev = masks.device
@@ -87,12 +85,8 @@ def mask_nms(masks, count=None, labels=None, *, iou_th, out=None, ws=None):
             raise ValueError("mask_nms: labels must be %s, one per row, got %s" % (lead + (r,), tuple(labels.shape)))
         labels = labels.reshape(b, r)
     iou_th = _iou_th(iou_th, "mask_nms")
-    if out is not None:
-        out = _typed(out, torch.uint8, len(lead) + 2, "out")
-        if tuple(out.shape) != lead + (r, v):
-            raise ValueError("mask_nms: out must be %s like masks, got %s" % (lead + (r, v), tuple(out.shape)))
-    if ws is not None:
-        ws = _typed(ws, torch.uint8, 1, "ws")
+    out = _out_like(out, lead + (r, v), None, "mask_nms")
+    ws = _ws_typed(ws)
     _limits(b, r, v, "mask_nms")
     masks, = _on_device(masks=masks)
     dev = masks.device
@@ -102,10 +96,7 @@ def mask_nms(masks, count=None, labels=None, *, iou_th, out=None, ws=None):
         count, = _on_device(count=count)
     if labels is not None:
         labels, = _on_device(labels=labels)
-    if out is None:
-        out = torch.empty(lead + (r, v), dtype=torch.uint8, device=dev)
-    elif not out.is_cuda or out.device != dev or not out.is_contiguous():
-        raise ValueError("mask_nms: out must be a contiguous tensor on %s" % (dev,))
+    out = _out_like(out, lead + (r, v), dev, "mask_nms")
     ws = _workspace(ws, int(L.lib().gspn_mask_nms_ws_bytes(b, r, v)), dev, "mask_nms")
     keep = torch.empty(lead + (r,), dtype=torch.uint8, device=dev)
     mask_points = torch.empty(lead + (r,), dtype=torch.int32, device=dev)

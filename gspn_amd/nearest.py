@@ -6,7 +6,7 @@ Non-differentiable.  No CPU fallback."""
 import torch
 
 from . import _lib as L
-from .predict import _on_device, _typed
+from ._args import _on_device, _typed, _workspace, _ws_typed
 
 __all__ = ["NEAREST_MAX_M", "nearest_point"]
 
@@ -28,19 +28,14 @@ def nearest_point(xyz1, xyz2, ws=None):
         raise ValueError("nearest_point: no known points, xyz2 %s" % (tuple(xyz2.shape),))
     if m > NEAREST_MAX_M:
         raise NotImplementedError("nearest_point: m <= %d (got %d)" % (NEAREST_MAX_M, m))
-    if ws is not None:
-        ws = _typed(ws, torch.uint8, 1, "ws")
+    ws = _ws_typed(ws)
     xyz1, xyz2 = _on_device(xyz1=xyz1, xyz2=xyz2)
     dev = xyz1.device
     dist = torch.empty((b, n), dtype=torch.float32, device=dev)
     idx = torch.empty((b, n), dtype=torch.int32, device=dev)
     if b == 0 or n == 0:
         return dist, idx
-    need = int(L.lib().gspn_nearest_point_ws_bytes(b, m))
-    if ws is None:
-        ws = torch.empty((need,), dtype=torch.uint8, device=dev)
-    elif ws.numel() < need or not ws.is_contiguous() or ws.device != dev or ws.data_ptr() % 16:
-        raise ValueError("nearest_point: ws must be a contiguous, 16-byte aligned uint8 tensor of at least %d bytes on %s" % (need, dev))
+    ws = _workspace(ws, int(L.lib().gspn_nearest_point_ws_bytes(b, m)), dev, "nearest_point")
     with torch.cuda.device(dev):
         L.check(L.lib().gspn_nearest_point(b, n, m, L.ptr(xyz1), L.ptr(xyz2), L.ptr(ws), L.ptr(dist), L.ptr(idx), L.stream()), "nearest_point")
     return dist, idx

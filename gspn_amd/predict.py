@@ -16,6 +16,7 @@ import os
 import torch
 
 from . import _lib as L
+from ._args import _on_device, _typed
 from .detect import nearest_in_sets
 from .inference import _point_probabilities
 
@@ -35,23 +36,6 @@ def _label_map(values, device):
     if key not in _label_maps:
         _label_maps[key] = torch.tensor(key[0], dtype=torch.int32, device=device)
     return _label_maps[key]
-
-
-def _typed(t, dtype, ndim, name):
-    """the dtype and rank rules of L.need without its device rule: the shape rules are checked between the two, so that a tensor that
-    does not fit raises ValueError wherever it lives"""
-    if not isinstance(t, torch.Tensor):
-        raise TypeError("%s must be a torch.Tensor" % name)
-    if t.dtype != dtype:
-        raise ValueError("%s must be %s, got %s" % (name, dtype, t.dtype))
-    if ndim is not None and t.dim() != ndim:
-        raise ValueError("%s must be %d-D, got shape %s" % (name, ndim, tuple(t.shape)))
-    return t.detach()
-
-
-def _on_device(**named):
-    """L.need's device rule and contiguity, for tensors whose dtype and shape have been checked"""
-    return [L.need(t, t.dtype, None, name) for name, t in named.items()]
 
 
 def scene_confidence(idx, masks, class_ids, sem_prob, point_fb, mask_th=0.4):

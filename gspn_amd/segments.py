@@ -8,7 +8,7 @@ integer atomics only, the same bits on every call.  No CPU fallback."""
 import torch
 
 from . import _lib as L
-from .predict import _on_device, _typed
+from ._args import _on_device, _out_like, _typed, _workspace, _ws_typed
 
 __all__ = ["SEGMENT_MAX_V", "SEGMENT_MAX_S", "SEGMENT_MAX_R", "SEGMENT_MAX_COUNTERS", "compact_segments", "segment_vote", "segment_label_vote"]
 
@@ -47,14 +47,6 @@ def _count(n, what, name):
     return n
 
 
-def _workspace(ws, need, dev, what):
-    if ws is None:
-        return torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
-    if ws.numel() < need or not ws.is_contiguous() or ws.device != dev or ws.data_ptr() % 16:
-        raise ValueError("%s: ws must be a contiguous, 16-byte aligned uint8 tensor of at least %d bytes on %s" % (what, need, dev))
-    return ws
-
-
 def segment_vote(masks, seg, num_segments, vote_th=0.5, out=None, ws=None):
     """masks (R, V) uint8, any nonzero byte set; seg (V,) int32, compact ids (compact_segments), a value outside [0, num_segments)
     unsegmented; vote_th a Python float (a double) in [0, 1); out: a (R, V) uint8 device tensor to write, masks itself allowed, or None;
@@ -71,21 +63,14 @@ def segment_vote(masks, seg, num_segments, vote_th=0.5, out=None, ws=None):
         raise ValueError("segment_vote: empty input, masks %s" % (tuple(masks.shape),))
     s = _count(num_segments, "segment_vote", "num_segments")
     vote_th = _vote_th(vote_th, "segment_vote")
-    if out is not None:
-        out = _typed(out, torch.uint8, 2, "out")
-        if tuple(out.shape) != (r, v):
-            raise ValueError("segment_vote: out must be %s like masks, got %s" % ((r, v), tuple(out.shape)))
-    if ws is not None:
-        ws = _typed(ws, torch.uint8, 1, "ws")
+    out = _out_like(out, (r, v), None, "segment_vote")
+    ws = _ws_typed(ws)
     if v > SEGMENT_MAX_V or s > SEGMENT_MAX_S or r > SEGMENT_MAX_R or (r + 1) * s > SEGMENT_MAX_COUNTERS:
         raise NotImplementedError("segment_vote: V <= %d, S <= %d, R <= %d and (R + 1) * S <= %d (got %d, %d and %d)"
                                   % (SEGMENT_MAX_V, SEGMENT_MAX_S, SEGMENT_MAX_R, SEGMENT_MAX_COUNTERS, v, s, r))
     masks, seg = _on_device(masks=masks, seg=seg)
     dev = masks.device
-    if out is None:
-        out = torch.empty((r, v), dtype=torch.uint8, device=dev)
-    elif not out.is_cuda or out.device != dev or not out.is_contiguous():
-        raise ValueError("segment_vote: out must be a contiguous tensor on %s" % (dev,))
+    out = _out_like(out, (r, v), dev, "segment_vote")
     ws = _workspace(ws, int(L.lib().gspn_segment_vote_ws_bytes(r, v, s)), dev, "segment_vote")
     mask_points = torch.empty((r,), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
@@ -110,8 +95,7 @@ def segment_label_vote(labels, seg, num_segments, num_classes, ws=None):
     c = int(num_classes)
     if c < 1:
         raise ValueError("segment_label_vote: num_classes must be positive, got %d" % c)
-    if ws is not None:
-        ws = _typed(ws, torch.uint8, 1, "ws")
+    ws = _ws_typed(ws)
     if v > SEGMENT_MAX_V or s > SEGMENT_MAX_S or s * c > SEGMENT_MAX_COUNTERS:
         raise NotImplementedError("segment_label_vote: V <= %d, S <= %d and S * C <= %d (got %d, %d and C = %d)"
                                   % (SEGMENT_MAX_V, SEGMENT_MAX_S, SEGMENT_MAX_COUNTERS, v, s, c))

@@ -78,7 +78,7 @@ class Tester:
             raise ValueError("Tester: mask_nms_th must lie in [0, 1), got %r" % self.mask_nms_th)
         self.min_component, self.min_component_share = None, 0.0                   # run_vertices alone: a scan that brings 'faces' 
         if min_component is not None:
-            from .components import _parameters
+            from ._args import _parameters
             self.min_component, self.min_component_share = _parameters(min_component, min_component_share, "Tester")
         self.dev = data.pc.device
         self.store = tf_util.set_variable_store(tf_util.VariableStore(device=self.dev, seed=self.seed))

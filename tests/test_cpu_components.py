@@ -14,6 +14,7 @@ import pytest
 import torch
 
 from tests import components_ref as ref
+from tests.args_check import run_args_check
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -77,12 +78,7 @@ def test_every_decline_comes_back_before_a_launch_and_the_workspaces_follow_the_
 def test_the_argument_checks_hold_under_the_host_sanitizers(tmp_path):
     """tools/components_args_check.cpp: the launchers' host-side checks and workspace layouts as a program of their own, built with the
     address and undefined-behaviour sanitizers and run over the decline table -- never loaded into Python"""
-    import subprocess
-    exe = str(tmp_path / "components_args_check")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    os.path.join(ROOT, "tools", "components_args_check.cpp"), "-o", exe], check=True)
-    done = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert done.returncode == 0 and done.stdout.strip() == "ok", done.stdout
+    run_args_check("components_args_check", tmp_path)
 
 
 # ---- the mesh files --------------------------------------------------------------------------------------------------------------------

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from tests import segments_ref as ref
+from tests.args_check import run_args_check
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -70,12 +71,7 @@ def test_the_segment_symbols_are_declared_exported_and_bound_at_abi_21():
 def test_the_argument_checks_hold_under_the_host_sanitizers(tmp_path):
     """tools/segments_args_check.cpp: the launchers' host-side checks and workspace layouts as a program of their own, built with the
     address and undefined-behaviour sanitizers and run over the decline table -- never loaded into Python"""
-    import subprocess
-    exe = str(tmp_path / "segments_args_check")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    os.path.join(ROOT, "tools", "segments_args_check.cpp"), "-o", exe], check=True)
-    done = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert done.returncode == 0 and done.stdout.strip() == "ok", done.stdout
+    run_args_check("segments_args_check", tmp_path)
 
 
 # 12 vertices, 4 segments, 3 rows: segment 0 has four vertices, 1 two, 2 three, 3 one; vertex 9 is unsegmented (-1), vertex 10 carries an id

@@ -75,21 +75,6 @@ def test_the_overlaps_and_the_nms_equal_the_restatement_at_the_vector_and_word_e
             same(nms(masks, labels=labels, iou_th=th), ref.mask_nms_ref(masks, labels=labels, iou_th=th), "V %d R %d at %r with labels" % (v, r, th))
 
 
-@pytest.mark.parametrize("v", (64, 67, 4099, 8200))
-def test_a_vector_set_in_exactly_one_byte_at_each_of_its_positions(v):
-    masks = np.zeros((16, v), np.uint8)
-    for k in range(16):                                               # whatever a row's alignment, the 16 rows put the byte at all 16 positions
-        masks[k, 32 + k] = BYTES[1 + k % 3]
-    sizes, inter = overlaps(masks)
-    assert sizes.tolist() == [1] * 16 and np.array_equal(inter, np.eye(16, dtype=np.int32))
-    got = nms(masks, iou_th=0.0)
-    assert got[1].tolist() == [1] * 16 and np.array_equal(got[0], (masks != 0).astype(np.uint8))
-    masks[:, v - 1] = 7                                               # now they all share the last vertex: at 0 one shared vertex suppresses
-    got = nms(masks, iou_th=0.0)
-    same(got, ref.mask_nms_ref(masks, iou_th=0.0), "V %d sharing the last vertex" % v)
-    assert got[1].tolist() == [1] + [0] * 15 and got[2].tolist() == [2] + [0] * 15
-
-
 # ---- tiling --------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("r", R_EDGES)
 def test_the_row_counts_at_the_edges_of_the_pair_tile(r):

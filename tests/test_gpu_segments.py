@@ -76,20 +76,6 @@ def test_five_segments_under_heavy_contention():
     same(vote(masks, seg, 5), ref.fast_segment_vote_ref(masks, seg, 5), "V 70001 S 5")
 
 
-@pytest.mark.parametrize("v", (64, 67, 4099))
-def test_a_vector_set_in_exactly_one_byte_at_each_of_its_positions(v):
-    rng = np.random.default_rng(4)
-    masks = np.zeros((16, v), np.uint8)
-    for k in range(16):                                               # whatever a row's alignment, the 16 rows put the byte at all 16 positions
-        masks[k, 32 + k] = BYTES[1 + k % 3]
-    for s, seg in ((v, np.arange(v)), (5, rng.integers(0, 5, size=v))):
-        want = ref.segment_vote_ref(masks, seg, s)
-        same(vote(masks, seg, s), want, "V %d S %d" % (v, s))
-        same(vote(masks, seg, s, 0.0), ref.segment_vote_ref(masks, seg, s, 0.0), "V %d S %d at 0" % (v, s))
-    got = vote(masks, np.arange(v), v)
-    assert got[1].tolist() == [1] * 16 and all(got[0][k, 32 + k] == 1 for k in range(16))
-
-
 # ---- ties ----------------------------------------------------------------------------------------------------------------------------------
 def test_ties_on_segments_exactly_half_set():
     sizes = [2, 4, 6, 10, 64, 130, 1000]

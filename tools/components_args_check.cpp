@@ -7,17 +7,8 @@
 //
 // It walks the decline table of include/gspn_hip.h, the sizes at and one past every limit (where int arithmetic would overflow if the
 // layout multiplied in int), and the layouts at the largest legal sizes.  Exit status 0 and "ok" when every row holds.
-#include <math.h>
-#include <stdio.h>
-
 #include "../gspn_amd/csrc/components_args.h"
-
-static int failures = 0;
-#define EXPECT(what, got, want)                                                                              \
-    do {                                                                                                     \
-        const long g_ = (long)(got), w_ = (long)(want);                                                      \
-        if (g_ != w_) { printf("FAIL %s: got %ld, expected %ld (line %d)\n", what, g_, w_, __LINE__); ++failures; } \
-    } while (0)
+#include "args_check.h"
 
 static long up16(long n) { return (n + 15) / 16 * 16; }
 
@@ -107,6 +98,5 @@ int main() {
     EXPECT("layout: r = 64 has one word", mc_layout(64, 1, true).words, 1);
     EXPECT("layout: r = 65 has two", mc_layout(65, 1, true).words, 2);
 
-    if (failures == 0) printf("ok\n");
-    return failures == 0 ? 0 : 1;
+    return args_check_done();
 }

@@ -7,17 +7,8 @@
 //
 // It walks the decline table of include/gspn_hip.h, the sizes at and one past every limit (where int arithmetic would overflow if the
 // layout multiplied in int), and the layouts at the largest legal sizes.  Exit status 0 and "ok" when every row holds.
-#include <math.h>
-#include <stdio.h>
-
 #include "../gspn_amd/csrc/mask_nms_args.h"
-
-static int failures = 0;
-#define EXPECT(what, got, want)                                                                              \
-    do {                                                                                                     \
-        const long g_ = (long)(got), w_ = (long)(want);                                                      \
-        if (g_ != w_) { printf("FAIL %s: got %ld, expected %ld (line %d)\n", what, g_, w_, __LINE__); ++failures; } \
-    } while (0)
+#include "args_check.h"
 
 int main() {
     alignas(16) static char buf[64];
@@ -98,6 +89,5 @@ int main() {
     EXPECT("layout: v = 65 has two", mn_layout(1, 1, 65, true).words, 2);
     EXPECT("layout: an odd word count rounds up", mn_layout(1, 3, 9, true).sizes, 32);
 
-    if (failures == 0) printf("ok\n");
-    return failures == 0 ? 0 : 1;
+    return args_check_done();
 }

@@ -7,17 +7,8 @@
 //
 // It walks the decline table of include/gspn_hip.h, the sizes at and one past every limit (where int arithmetic would overflow if the
 // checks multiplied in int), and the layouts at the largest legal sizes.  Exit status 0 and "ok" when every row holds.
-#include <math.h>
-#include <stdio.h>
-
 #include "../gspn_amd/csrc/segments_args.h"
-
-static int failures = 0;
-#define EXPECT(what, got, want)                                                                              \
-    do {                                                                                                     \
-        const long g_ = (long)(got), w_ = (long)(want);                                                      \
-        if (g_ != w_) { printf("FAIL %s: got %ld, expected %ld (line %d)\n", what, g_, w_, __LINE__); ++failures; } \
-    } while (0)
+#include "args_check.h"
 
 int main() {
     alignas(16) static char buf[64];
@@ -95,6 +86,5 @@ int main() {
     const int declined_l[][3] = {{-1, 4, 5}, {9, -1, 5}, {9, 4, 0}, {0, 4, 5}, {big, 4, 5}, {9, big, 5}, {9, 1 << 24, 17}, {imax, imax, imax}};
     for (const auto& d : declined_l) EXPECT("labels ws: declined sizes", sl_ws_bytes(d[0], d[1], d[2]), 0);
 
-    if (failures == 0) printf("ok\n");
-    return failures == 0 ? 0 : 1;
+    return args_check_done();
 }

@@ -1,4 +1,4 @@
-"""The argument rules the stage modules share (predict, evaluate, nearest, lift, segments, mask_nms, components): each checks dtypes, ranks and
+"""The argument rules the stage modules share (predict, evaluate, nearest, lift, segments, mask_nms, components, holes): each checks dtypes, ranks and
 shapes first, so that a tensor that does not fit raises ValueError wherever it lives, then the limits (NotImplementedError), and only then
 touches the device and the library.  Private to the package."""
 import torch
@@ -65,3 +65,16 @@ def _parameters(min_vertices, min_share, what):
     if not 0.0 <= min_share <= 1.0:                                                 # a NaN fails both
         raise ValueError("%s: min_share must lie in [0, 1], got %r" % (what, min_share))
     return min_vertices, min_share
+
+
+def _hole_parameters(max_vertices, max_share, what):
+    """the hole fill's parameters (hole_fill, lift.scan_predictions, tester.Tester) -> (int, float); ValueError for max_vertices < 0 or a
+    max_share outside [0, 1]"""
+    if isinstance(max_vertices, bool) or int(max_vertices) != max_vertices:
+        raise ValueError("%s: max_vertices must be an integer, got %r" % (what, max_vertices))
+    max_vertices, max_share = int(max_vertices), float(max_share)
+    if max_vertices < 0 or max_vertices >= 1 << 31:
+        raise ValueError("%s: max_vertices must not be negative, got %d" % (what, max_vertices))
+    if not 0.0 <= max_share <= 1.0:                                                 # a NaN fails both
+        raise ValueError("%s: max_share must lie in [0, 1], got %r" % (what, max_share))
+    return max_vertices, max_share

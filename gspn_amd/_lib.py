@@ -163,6 +163,7 @@ SIGNATURES = {
     "gspn_mask_nms": [_I, _I, _I, _P, _P, _P, _D, _P, _P, _P, _P, _P],
     "gspn_mask_components": [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
     "gspn_mask_component_filter": [_I, _I, _I, _P, _P, _I, _D, _P, _P, _P, _P, _P, _P],
+    "gspn_mask_hole_fill": [_I, _I, _I, _P, _P, _P, _I, _D, _P, _P, _P, _P, _P, _P, _P],
 }
 
 # entry points that do not return an int status: symbol -> (argtypes, restype)
@@ -200,6 +201,7 @@ SPECIAL = {
     "gspn_mask_nms_ws_bytes": ([_I, _I, _I], _L),
     "gspn_mask_components_ws_bytes": ([_I, _I, _I], _L),
     "gspn_mask_component_filter_ws_bytes": ([_I, _I, _I], _L),
+    "gspn_mask_hole_fill_ws_bytes": ([_I, _I, _I], _L),
     "gspn_grid_blocks": ([_L, _I], _L),
 }
 

@@ -38,6 +38,8 @@
 // is read from ws that the call did not write.
 #include "common.h"
 #include "components_args.h"
+#include "float_keys.h"
+#include "holes_args.h"
 #include "mask_rows.h"
 
 #define MC_T 256
@@ -308,5 +310,279 @@ extern "C" int gspn_mask_component_filter(int r, int v, int f, const unsigned ch
     mc_label(st, r, v, f, l, masks, faces, base, comp, ncomp, largest, nkept, mask_points);
     hipLaunchKernelGGL(mc_apply_kernel, dim3((unsigned)((mask_row_chunks(v) + MC_T - 1) / MC_T), (unsigned)r), dim3(MC_T), 0, st, v, min_vertices, min_share,
                        comp, reinterpret_cast<int*>(base + l.size), largest, reinterpret_cast<int*>(base + l.bad), out, mask_points, ncomp, nkept);
+    return gspn_launch_status();
+}
+
+// ---------------- mask holes (additive at ABI 21): the gaps a mask row encloses on the mesh are filled ----------------------
+//
+// The mirror of the filter.  The graph of row k is its CANDIDATES, the unset vertices inside the closed box of its set vertices with finite
+// coordinates, under the edges whose two ends are both candidates; a candidate component is a HOLE iff no edge joins it to an unset vertex
+// outside the box (it is not OPEN), some edge joins it to a set vertex (it TOUCHES), and its size is within max_vertices and
+// max_share * points_in.  The union-find above runs unchanged on a parent array that holds -2 at a set vertex, -1 at an unset vertex that
+// is no candidate, and x at a candidate: every mc_* kernel treats a negative parent as "not in the graph".
+//
+//   prime    grid (r / 256): the box keys to (INT_MAX, INT_MIN), which decode to NaN; the row's counters and marks zeroed
+//   box      grid over the ADDRESS of the row (mask_rows.h): the set vertices counted (points_in), lo and hi of those whose three coordinates
+//            are finite reduced per wave and landed with integer atomicMin / atomicMax on the keys of float_keys.h
+//   init     grid over the address of the row: parent = set ? -2 : (inside ? x : -1), size = 0; inside is lo <= c && c <= hi on the three
+//            axes as float compares, so a NaN coordinate, and every vertex of a row without a box, is outside
+//   tables   grid (v / 256, words): both vertex-major tables in one read of parent, cand (parent >= 0) and set (parent == -2)
+//   hook, compress, flatten   the kernels above on the cand table: parent[k][x] = the root, size[k][root] = the component's vertices
+//   mark     one face per lane, grid ceil(f / 256): per edge and word, cand[u] & set[w] are the rows in which u's component touches,
+//            cand[u] & ~cand[w] & ~set[w] those in which it is open, and the same with the ends swapped; per bit one integer atomicOr of
+//            the flag into size[k][parent[k][u]], skipped where a read past the L1 shows it set already
+//   apply    grid over the ADDRESS of out's row: out = set or in a hole; nholes, nfilled and mask_points summed over the hole roots, one
+//            atomic of each per wave.  It reads parent, size and points_in and never masks, so out may be masks
+//
+// STALE READS: mark runs in a later kernel than every union and than flatten, whose only stores are roots; a kernel boundary makes them
+// visible, so parent[k][u] is the final root and no walk is needed.  The flags are ORed by integer atomics into words nobody else writes
+// in that kernel; the early-out read may miss a flag another lane has just set, which costs one more atomicOr of the same bit.  No loop
+// but the table words and their bits; every index read from memory (a face's vertex, a root) is range-checked; a root outside [0, v) marks
+// the row, whose nholes comes back -1.
+#define HF_TOUCH (1 << 30)
+#define HF_OPEN (1 << 29)
+#define HF_COUNT (HF_OPEN - 1)           // sizes are at most 2^24
+
+namespace {
+
+// grid (ceil(r / MC_T))
+__global__ __launch_bounds__(MC_T) void hf_prime_kernel(int r, int* __restrict__ box, int* __restrict__ points_in, int* __restrict__ bad,
+                                                        int* __restrict__ mask_points, int* __restrict__ nholes, int* __restrict__ nfilled) {
+    const int row = blockIdx.x * MC_T + threadIdx.x;
+    if (row >= r) return;
+    for (int a = 0; a < 3; ++a) {
+        box[6 * row + a] = 0x7FFFFFFF;
+        box[6 * row + 3 + a] = -0x7FFFFFFF - 1;
+    }
+    points_in[row] = 0;
+    bad[row] = 0;
+    mask_points[row] = 0;
+    nholes[row] = 0;
+    nfilled[row] = 0;
+}
+
+// grid (ceil(chunks / MC_T), r) over the address of the row
+__global__ __launch_bounds__(MC_T) void hf_box_kernel(int v, const unsigned char* masks, const float* __restrict__ xyz, int* __restrict__ box,
+                                                      int* __restrict__ points_in) {
+    const int row = blockIdx.y;
+    const unsigned char* p = masks + (long)row * v;
+    const int i0 = (blockIdx.x * MC_T + threadIdx.x) * MASK_ROW_VEC - mask_row_a0(p);    // >= -15; < 2^24 + 16 * MC_T
+    const unsigned bits = mask_row_load(p, i0, v);                   // (nobody returns: the lanes trade their bits below)
+    if (__ballot(bits != 0u) == 0ull) return;                        // uniform over the wave: nothing set in its 1024 vertices
+    // as in mc_init_kernel, in pass t the wave takes the 64 consecutive vertices 64 t .. 64 t + 63 of its chunks: xyz is read coalesced
+    const int lane = lane_id();
+    const int first = i0 - lane * MASK_ROW_VEC;
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    int count = 0;
+#pragma unroll
+    for (int t = 0; t < MASK_ROW_VEC; ++t) {
+        const unsigned theirs = (unsigned)__shfl((int)bits, 4 * t + (lane >> 4), GSPN_WAVE);
+        const int i = first + GSPN_WAVE * t + lane;
+        if (i >= 0 && i < v && ((theirs >> (lane & 15)) & 1u)) {
+            ++count;
+            const float c[3] = {xyz[3l * i], xyz[3l * i + 1], xyz[3l * i + 2]};
+            if (fabsf(c[0]) < INFINITY && fabsf(c[1]) < INFINITY && fabsf(c[2]) < INFINITY) {         // a NaN fails the compare
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    lo[a] = fminf(lo[a], c[a]);
+                    hi[a] = fmaxf(hi[a], c[a]);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        lo[a] = wave_min_f32(lo[a]);
+        hi[a] = wave_max_f32(hi[a]);
+    }
+    count = wave_sum_lane0(count);
+    if (lane == 0) {
+        atomicAdd(&points_in[row], count);
+        if (lo[0] <= hi[0]) {                                        // the wave saw a finite vertex: all three axes have one
+            // (Reading the six keys first, past the L1, and landing only what would change them was measured and is slower: the wave then
+            // waits for the reads, while an atomic whose value nobody uses does not hold it.)
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                atomicMin(&box[6 * row + a], np_key(lo[a]));
+                atomicMax(&box[6 * row + 3 + a], np_key(hi[a]));
+            }
+        }
+    }
+}
+
+// grid (ceil(chunks / MC_T), r) over the address of the row
+__global__ __launch_bounds__(MC_T) void hf_init_kernel(int v, const unsigned char* masks, const float* __restrict__ xyz, const int* __restrict__ box,
+                                                       int* __restrict__ parent, int* __restrict__ size) {
+    const int row = blockIdx.y;
+    const unsigned char* p = masks + (long)row * v;
+    const int i0 = (blockIdx.x * MC_T + threadIdx.x) * MASK_ROW_VEC - mask_row_a0(p);    // >= -15; < 2^24 + 16 * MC_T
+    const unsigned bits = mask_row_load(p, i0, v);                   // (nobody returns: the lanes trade their bits below)
+    float lo[3], hi[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        lo[a] = np_unkey(box[6 * row + a]);                          // NaN for a row without a box: nothing is inside
+        hi[a] = np_unkey(box[6 * row + 3 + a]);
+    }
+    const bool boxed = lo[0] <= hi[0];
+    const int lane = lane_id();
+    const int first = i0 - lane * MASK_ROW_VEC;                      // the first vertex of the wave's chunks, >= -15
+    int* par = parent + (long)row * v;
+    int* sz = size + (long)row * v;
+#pragma unroll
+    for (int t = 0; t < MASK_ROW_VEC; ++t) {
+        const unsigned theirs = (unsigned)__shfl((int)bits, 4 * t + (lane >> 4), GSPN_WAVE);
+        const int i = first + GSPN_WAVE * t + lane;
+        if (i >= 0 && i < v) {
+            int value = -2;
+            if (((theirs >> (lane & 15)) & 1u) == 0u) {
+                value = -1;
+                if (boxed) {
+                    const float x = xyz[3l * i], y = xyz[3l * i + 1], z = xyz[3l * i + 2];
+                    if (lo[0] <= x && x <= hi[0] && lo[1] <= y && y <= hi[1] && lo[2] <= z && z <= hi[2]) value = i;
+                }
+            }
+            par[i] = value;
+            sz[i] = 0;
+        }
+    }
+}
+
+// grid (ceil(v / MC_T), words)
+__global__ __launch_bounds__(MC_T) void hf_tables_kernel(int r, int v, int words, const int* __restrict__ parent, u64* __restrict__ cand,
+                                                         u64* __restrict__ set) {
+    const int x = blockIdx.x * MC_T + threadIdx.x;
+    if (x >= v) return;
+    const int k0 = blockIdx.y * 64, k1 = min(r, k0 + 64);
+    u64 c = 0ull, s = 0ull;
+    for (int k = k0; k < k1; ++k) {
+        const int p = parent[(long)k * v + x];
+        if (p >= 0) c |= 1ull << (k - k0);
+        if (p == -2) s |= 1ull << (k - k0);
+    }
+    cand[(long)x * words + blockIdx.y] = c;
+    set[(long)x * words + blockIdx.y] = s;
+}
+
+// the flag ORed into the size word of u's root in every row of m
+__device__ __forceinline__ void hf_flag(u64 m, int j, int u, int v, int flag, const int* __restrict__ parent, int* size, int* __restrict__ bad) {
+    while (m != 0ull) {
+        const int k = j * 64 + __ffsll((long long)m) - 1;                                             // < r: the tables have no bit beyond
+        m &= m - 1ull;
+        const int root = parent[(long)k * v + u];                    // final: flatten is over
+        if ((unsigned)root >= (unsigned)v) {
+            bad[k] = 1;
+            continue;
+        }
+        int* word = size + (long)k * v + root;
+        if ((mc_load(word) & flag) == 0) atomicOr(word, flag);
+    }
+}
+
+// grid (ceil(f / MC_T)): one face per lane
+__global__ __launch_bounds__(MC_T) void hf_mark_kernel(int v, int f, int words, const int* __restrict__ faces, const u64* __restrict__ cand,
+                                                       const u64* __restrict__ set, const int* __restrict__ parent, int* size, int* __restrict__ bad) {
+    const long t = blockIdx.x * (long)MC_T + threadIdx.x;
+    if (t >= f) return;
+    const int a = faces[3 * t], b = faces[3 * t + 1], c = faces[3 * t + 2];
+    const int eu[3] = {a, b, a}, ew[3] = {b, c, c};
+#pragma unroll
+    for (int e = 0; e < 3; ++e) {
+        const int u = eu[e], w = ew[e];
+        if ((unsigned)u >= (unsigned)v || (unsigned)w >= (unsigned)v || u == w) continue;            // an end outside [0, v): no edge
+        for (int j = 0; j < words; ++j) {
+            const u64 cu = cand[(long)u * words + j], cw = cand[(long)w * words + j];
+            if ((cu | cw) == 0ull) continue;
+            const u64 su = set[(long)u * words + j], sw = set[(long)w * words + j];
+            hf_flag(cu & sw, j, u, v, HF_TOUCH, parent, size, bad);
+            hf_flag(cu & ~cw & ~sw, j, u, v, HF_OPEN, parent, size, bad);
+            hf_flag(cw & su, j, w, v, HF_TOUCH, parent, size, bad);
+            hf_flag(cw & ~cu & ~su, j, w, v, HF_OPEN, parent, size, bad);
+        }
+    }
+}
+
+// grid (ceil(chunks / MC_T), r) over the ADDRESS of out's row
+__global__ __launch_bounds__(MC_T) void hf_apply_kernel(int v, int max_vertices, double max_share, const int* __restrict__ parent,
+                                                        const int* __restrict__ size, const int* __restrict__ points_in, const int* __restrict__ bad,
+                                                        unsigned char* out, int* __restrict__ mask_points, int* __restrict__ nholes,
+                                                        int* __restrict__ nfilled) {
+    const int row = blockIdx.y;
+    const bool marked = bad[row] != 0;                               // mark is over: nobody writes it any more
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if (marked) nholes[row] = -1;                                // (nobody adds to it in a marked row)
+        atomicAdd(&mask_points[row], points_in[row]);                // once a row: the waves below add what they fill
+    }
+    unsigned char* p = out + (long)row * v;
+    const int i0 = (blockIdx.x * MC_T + threadIdx.x) * MASK_ROW_VEC - mask_row_a0(p);    // >= -15; < 2^24 + 16 * MC_T
+    const int* par = parent + (long)row * v;
+    const int* sz = size + (long)row * v;
+    const double ceiling_share = max_share * (double)points_in[row];
+    // as in mc_apply_kernel: in pass t lane l decides vertex 64 t + l of the wave's 1024, and the ballot of the pass holds four chunks
+    const int lane = lane_id();
+    const int first = i0 - lane * MASK_ROW_VEC;                      // the first vertex of the wave's chunks, >= -15
+    unsigned bits = 0u;
+    int holes = 0, filled = 0;
+#pragma unroll
+    for (int t = 0; t < MASK_ROW_VEC; ++t) {
+        const int i = first + GSPN_WAVE * t + lane;
+        bool on = false;
+        if (i >= 0 && i < v) {
+            const int root = par[i];
+            if (root == -2) on = true;
+            else if ((unsigned)root < (unsigned)v) {                 // -1: unset and no candidate
+                const int word = sz[root], s = word & HF_COUNT;
+                on = (word & (HF_TOUCH | HF_OPEN)) == HF_TOUCH && s <= max_vertices && (double)s <= ceiling_share;
+                if (on && root == i) {                               // summed over the roots, never per vertex
+                    ++holes;
+                    filled += s;
+                }
+            }
+        }
+        const u64 word = __ballot(on);
+        if ((lane >> 2) == t) bits = (unsigned)(word >> (16 * (lane & 3))) & 0xFFFFu;
+    }
+    mask_row_store(p, i0, v, bits);
+    holes = wave_sum_lane0(holes);
+    filled = wave_sum_lane0(filled);                                 // <= v <= 2^24
+    if (lane_id() == 0 && holes != 0 && !marked) {
+        atomicAdd(&nholes[row], holes);
+        atomicAdd(&nfilled[row], filled);
+        atomicAdd(&mask_points[row], filled);
+    }
+}
+
+}  // namespace
+
+extern "C" long gspn_mask_hole_fill_ws_bytes(int r, int v, int f) { return hf_ws_bytes(r, v, f); }
+
+extern "C" int gspn_mask_hole_fill(int r, int v, int f, const unsigned char* masks, const int* faces, const float* xyz, int max_vertices,
+                                   double max_share, void* ws, unsigned char* out, int* mask_points, int* nholes, int* nfilled, int* label,
+                                   void* stream) {
+    const int rc = hf_check(r, v, f, masks, faces, xyz, max_vertices, max_share, ws, out, mask_points, nholes, nfilled);
+    if (rc != 0) return rc;
+    if (r == 0 || v == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    const HfLayout l = hf_layout(r, v);
+    char* base = static_cast<char*>(ws);
+    u64* cand = reinterpret_cast<u64*>(base + l.cand);
+    u64* set = reinterpret_cast<u64*>(base + l.set);
+    int* size = reinterpret_cast<int*>(base + l.size);
+    int* bad = reinterpret_cast<int*>(base + l.bad);
+    int* box = reinterpret_cast<int*>(base + l.box);
+    int* points_in = reinterpret_cast<int*>(base + l.points);
+    int* parent = label ? label : reinterpret_cast<int*>(base + l.parent);
+    const dim3 by_vector((unsigned)((mask_row_chunks(v) + MC_T - 1) / MC_T), (unsigned)r), by_vertex((unsigned)((v + MC_T - 1) / MC_T), (unsigned)r);
+    hipLaunchKernelGGL(hf_prime_kernel, dim3((unsigned)((r + MC_T - 1) / MC_T)), dim3(MC_T), 0, st, r, box, points_in, bad, mask_points, nholes, nfilled);
+    hipLaunchKernelGGL(hf_box_kernel, by_vector, dim3(MC_T), 0, st, v, masks, xyz, box, points_in);
+    hipLaunchKernelGGL(hf_init_kernel, by_vector, dim3(MC_T), 0, st, v, masks, xyz, box, parent, size);
+    if (f > 0) {                                                     // without faces nothing touches: no holes
+        hipLaunchKernelGGL(hf_tables_kernel, dim3(by_vertex.x, (unsigned)l.words), dim3(MC_T), 0, st, r, v, l.words, parent, cand, set);
+        hipLaunchKernelGGL(mc_hook_kernel, dim3(grid_for(f, MC_T)), dim3(MC_T), 0, st, v, f, l.words, faces, cand, parent, bad);
+        hipLaunchKernelGGL(mc_compress_kernel, by_vertex, dim3(MC_T), 0, st, v, parent, bad);
+        hipLaunchKernelGGL(mc_flatten_kernel, by_vertex, dim3(MC_T), 0, st, v, parent, size, bad);
+        hipLaunchKernelGGL(hf_mark_kernel, dim3((unsigned)((f + MC_T - 1) / MC_T)), dim3(MC_T), 0, st, v, f, l.words, faces, cand, set, parent, size, bad);
+    }
+    hipLaunchKernelGGL(hf_apply_kernel, by_vector, dim3(MC_T), 0, st, v, max_vertices, max_share, parent, size, points_in, bad, out, mask_points, nholes,
+                       nfilled);
     return gspn_launch_status();
 }

@@ -1,5 +1,5 @@
 // mask_rows.h -- rows of v mask bytes read and written 16 bytes at a time, shared by the per-vertex mask stages: segments.hip (sv_count_kernel
-// reads), mask_nms.hip (mn_pack_kernel reads, mn_apply_kernel writes) and components.hip (mc_init_kernel reads, mc_apply_kernel writes).
+// reads), mask_nms.hip (mn_pack_kernel reads, mn_apply_kernel writes) and components.hip (mc_init_kernel, hf_box_kernel and hf_init_kernel read, mc_apply_kernel and hf_apply_kernel write).
 //
 // THE ADDRESS WALK.  v is arbitrary, so a row p = base + row * v starts at an arbitrary address and a vector grid laid over the row's
 // VERTICES would be misaligned in most rows.  The grid is laid over the row's ADDRESS instead: with a0 = address of p modulo 16

@@ -28,6 +28,7 @@
 #include <stdint.h>
 
 #include "common.h"
+#include "float_keys.h"                  // np_key, np_unkey
 
 #define NP_T 256
 #define NP_SCAN_T 1024
@@ -67,9 +68,6 @@ static inline int np_build_wps(int m) {
     return w < 1 ? 1 : (w > NP_BUILD_MAX_WPS ? NP_BUILD_MAX_WPS : w);
 }
 
-// floats to integers that order like them (-0 below +0, which is harmless here); the reset values decode to NaN
-__device__ __forceinline__ int np_key(float x) { const int v = __float_as_int(x); return v >= 0 ? v : v ^ 0x7FFFFFFF; }
-__device__ __forceinline__ float np_unkey(int k) { return __int_as_float(k >= 0 ? k : k ^ 0x7FFFFFFF); }
 
 __global__ __launch_bounds__(NP_T) void nearest_init_kernel(int b, long ncnt, NpPlan* __restrict__ hdr, int* __restrict__ cnt) {
     for (long i = blockIdx.x * (long)NP_T + threadIdx.x; i < ncnt; i += (long)gridDim.x * NP_T) {

@@ -15,8 +15,9 @@ V differs from scan to scan, so nothing here is meant for a captured step.  No C
 import torch
 
 from . import _lib as L
-from ._args import _on_device, _parameters, _typed
+from ._args import _hole_parameters, _on_device, _parameters, _typed
 from .components import COMPONENTS_MAX_F, component_filter
+from .holes import hole_fill
 from .mask_nms import mask_nms
 from .nearest import nearest_point
 from .predict import SCANNET_LABEL_MAP, SCENE_RANK_MAX_R, scene_rank
@@ -124,7 +125,8 @@ _KEYS = ("detections", "rpointnet_mask_selected", "pc_coord_cropped_final_unnorm
 
 
 def scan_predictions(end_points, scene, verts, *, pc=None, sem_conf_th=0.01, fb_conf_th=0.01, mask_th=0.4, label_map=SCANNET_LABEL_MAP,
-                     segments=None, num_segments=None, vote_th=0.5, mask_nms_th=None, faces=None, min_component=None, min_component_share=0.0):
+                     segments=None, num_segments=None, vote_th=0.5, mask_nms_th=None, faces=None, min_component=None, min_component_share=0.0,
+                     max_hole=None, max_hole_share=1.0):
     """test.py:155-205 on the vertices of one scan.  end_points: rpointnet_inference's of a batch, as they are (read: detections (B, R, 8),
     rpointnet_mask_selected (B, R, P), pc_coord_cropped_final_unnormalized (B, R, P, 3), pc_seed, fb_prob, sem_class_logits (B, N, C));
     scene: the scan's slot in that batch; verts (V, 3) float32: the scan's vertices, in the coordinates of the scene's points; pc (B, N, 3):
@@ -147,8 +149,13 @@ def scan_predictions(end_points, scene, verts, *, pc=None, sem_conf_th=0.01, fb_
     segment vote, BEFORE the rows are put in output order and before mask NMS, which must see the cleaned rows: a component of a row
     smaller than min_component vertices, or than min_component_share of the row's largest, is dropped.  masks and mask_points change and
     the dict gains 'components' and 'components_kept' (1, R) int32 in output order; the confidences, the order, the score and the count
-    come from the soft values as before.  One of the two without the other raises ValueError; with neither the keys and bits are what
-    they were.
+    come from the soft values as before.  With neither faces nor a stage that needs them the keys and bits are what they were.
+    faces with max_hole: an int >= 0.  Then holes.hole_fill(max_vertices=max_hole, max_share=max_hole_share) runs in place
+    on the hard rows on the scan's own vertices `verts`, BEHIND the component filter where there is one, before the rows are put in
+    output order and before mask NMS: a gap of at most max_hole vertices, and at most max_hole_share of the row's set vertices, that the
+    row encloses on the mesh is filled.  masks and mask_points change and the dict gains 'holes' and 'holes_filled' (1, R) int32 in
+    output order; the confidences, the order, the score and the count come from the soft values as before.  faces goes with at least one
+    of min_component and max_hole, and each of the two needs faces: anything else raises ValueError.
     Raises ValueError on a missing key or a shape or dtype that does not fit, NotImplementedError for R > 1024, P > 4096 or V > 2^24,
     before anything runs."""
     for k in _KEYS:
@@ -205,14 +212,19 @@ def scan_predictions(end_points, scene, verts, *, pc=None, sem_conf_th=0.01, fb_
         mask_nms_th = float(mask_nms_th)
         if not 0.0 <= mask_nms_th < 1.0:
             raise ValueError("scan_predictions: mask_nms_th must lie in [0, 1), got %r" % mask_nms_th)
-    if (faces is None) != (min_component is None):
+    if (faces is None and min_component is not None) or (faces is not None and min_component is None and max_hole is None):
         raise ValueError("scan_predictions: faces and min_component go together (got faces %s, min_component %r)"
                          % ("None" if faces is None else "given", min_component))
+    if faces is None and max_hole is not None:
+        raise ValueError("scan_predictions: faces and max_hole go together (got faces None, max_hole %r)" % (max_hole,))
     if faces is not None:
         faces = _typed(faces, torch.int32, 2, "faces")
         if faces.shape[1] != 3:
             raise ValueError("scan_predictions: faces must be (F, 3) (components.mesh_faces), got %s" % (tuple(faces.shape),))
-        min_component, min_component_share = _parameters(min_component, min_component_share, "scan_predictions")
+        if min_component is not None:
+            min_component, min_component_share = _parameters(min_component, min_component_share, "scan_predictions")
+        if max_hole is not None:
+            max_hole, max_hole_share = _hole_parameters(max_hole, max_hole_share, "scan_predictions")
     if r > SCENE_RANK_MAX_R or p > LIFT_MAX_P or v > LIFT_MAX_V:
         raise NotImplementedError("scan_predictions: R <= %d, P <= %d and V <= %d (got %d, %d and %d)"
                                   % (SCENE_RANK_MAX_R, LIFT_MAX_P, LIFT_MAX_V, r, p, v))
@@ -240,8 +252,11 @@ def scan_predictions(end_points, scene, verts, *, pc=None, sem_conf_th=0.01, fb_
             own = logits[s].max(-1).indices.int().index_select(0, src.long())                           # the first maximal column, as gspn_sem_iou_counts takes it
             sem_label = segment_label_vote(own, segments, num_segments, c)
         components = None
-        if faces is not None:                                                                           # 4.25: in place, behind the vote, before the order
+        if min_component is not None:                                                                   # 4.25: in place, behind the vote, before the order
             mask, mask_points, components, kept = component_filter(mask, faces, min_vertices=min_component, min_share=min_component_share, out=mask)
+        holes = None
+        if max_hole is not None:                                                                        # 4.26: in place, behind the filter, before the order
+            mask, mask_points, holes, holes_filled = hole_fill(mask, faces, verts, max_vertices=max_hole, max_share=max_hole_share, out=mask)
         order, count, label_ids, confidence, score = scene_rank(det[None, :, 7], class_ids[None], sem_conf[None], fb_conf[None], thresholds[0],
                                                                 thresholds[1], label_map)
         at = order[0].long()
@@ -254,6 +269,8 @@ def scan_predictions(end_points, scene, verts, *, pc=None, sem_conf_th=0.01, fb_
             pred["sem_label"] = sem_label
         if components is not None:
             pred["components"], pred["components_kept"] = components[at][None], kept[at][None]
+        if holes is not None:
+            pred["holes"], pred["holes_filled"] = holes[at][None], holes_filled[at][None]
         if mask_nms_th is not None:                                                                     # 4.24: in place, on the rows in output order
             pred["masks"], pred["keep"], pred["mask_points"] = mask_nms(pred["masks"], count, label_ids, iou_th=mask_nms_th, out=pred["masks"])
         return pred

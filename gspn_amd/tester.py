@@ -42,6 +42,8 @@ class Tester:
     per-vertex mask that copies an earlier one of its label; run() and the captured predict step never read it.
     min_component (an int >= 1, or None) and min_component_share (in [0, 1]): run_vertices drops the components of a mask that are smaller
     than that many vertices or than that share of the mask's largest, for a scan that brings 'faces' (DESIGN.md 4.25); nothing else reads them.
+    max_hole (an int >= 0, or None) and max_hole_share (in [0, 1]): run_vertices fills the gaps of at most that many vertices, and at most
+    that share of the mask's set vertices, that a mask encloses on the mesh, for a scan that brings 'faces' (DESIGN.md 4.26); nothing else reads them.
 
     The variables are created by one rpointnet_inference pass over the first batch, in the reference's order.
     captured=True: rpointnet_inference, scene_predictions, the AP counts and the semantic IoU counts replay from one graph.CapturedStep.
@@ -51,7 +53,7 @@ class Tester:
 
     def __init__(self, config, data, scans=None, batch_size=1, seed=0, captured=True, fused_crop=False, sem_conf_th=0.01, fb_conf_th=0.01,
                  mask_th=0.4, label_map=SCANNET_LABEL_MAP, max_captures=8, vote_th=0.5, mask_nms_th=None, min_component=None,
-                 min_component_share=0.0):
+                 min_component_share=0.0, max_hole=None, max_hole_share=1.0):
         if not isinstance(data, DeviceDataset):
             raise TypeError("Tester: data must be a train.DeviceDataset")
         if data.is_augment or data.permute_points:
@@ -80,6 +82,10 @@ class Tester:
         if min_component is not None:
             from ._args import _parameters
             self.min_component, self.min_component_share = _parameters(min_component, min_component_share, "Tester")
+        self.max_hole, self.max_hole_share = None, 1.0                             # run_vertices alone: a scan that brings 'faces' 
+        if max_hole is not None:
+            from ._args import _hole_parameters
+            self.max_hole, self.max_hole_share = _hole_parameters(max_hole, max_hole_share, "Tester")
         self.dev = data.pc.device
         self.store = tf_util.set_variable_store(tf_util.VariableStore(device=self.dev, seed=self.seed))
 
@@ -241,6 +247,7 @@ class Tester:
         mask_nms_th every scan's masks then pass mask NMS: a suppressed mask is empty, so it is not written and not counted.
         With the tester's min_component a scan that brings 'faces' ((F, 3) integers: its mesh's triangles, io_util.read_ply_faces) has the
         small components of its masks dropped behind the vote and before mask NMS; a scan without goes as it went.
+        With the tester's max_hole such a scan has the gaps its masks enclose on the mesh filled behind that and before mask NMS.
         The scenes run batched through the same step as run(); behind it lift.scan_predictions runs eagerly once per scan, V differing from scan to scan.  out_dir:
         <out_dir>/pred_vertices/<scan>.txt with pred_mask/, one line per vertex in every mask, and, where vertices(k) has labels,
         <out_dir>/gt_vertices/<scan>.txt.  evaluate: AP per scan through InstanceAP at B = 1 and the semantic IoU counts of
@@ -272,9 +279,12 @@ class Tester:
                     compact, nseg = compact_segments(raw)
                     voted = dict(segments=compact, num_segments=nseg, vote_th=self.vote_th)
                 cleaned = {}
-                if self.min_component is not None and "faces" in scan:          # 4.25: behind the vote, before the order and mask NMS
-                    cleaned = dict(faces=mesh_faces(scan["faces"], xyz.shape[0]), min_component=self.min_component,
-                                   min_component_share=self.min_component_share)
+                if (self.min_component is not None or self.max_hole is not None) and "faces" in scan:
+                    cleaned = dict(faces=mesh_faces(scan["faces"], xyz.shape[0]))
+                    if self.min_component is not None:                              # 4.25: behind the vote, before the order and mask NMS
+                        cleaned.update(min_component=self.min_component, min_component_share=self.min_component_share)
+                    if self.max_hole is not None:                                   # 4.26: behind the filter, before the order and mask NMS
+                        cleaned.update(max_hole=self.max_hole, max_hole_share=self.max_hole_share)
                 pred = scan_predictions(out["lift"], s, xyz, pc=self.buf["pc"], label_map=self.label_map, **self.thresholds, **voted,
                                         mask_nms_th=self.mask_nms_th, **cleaned)        # 4.24: behind the vote, on the rows in output order
                 labelled = "seg_label" in scan and "group_label" in scan

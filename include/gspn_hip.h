@@ -59,7 +59,8 @@ extern "C" {
  * Additive at 21: gspn_nearest_point (+ gspn_nearest_point_ws_bytes): exact one-nearest search over a cell grid in global memory.
  * Additive at 21: gspn_segment_vote, gspn_segment_label_vote (+ their _ws_bytes): masks and labels snapped to a scan's segments.
  * Additive at 21: gspn_mask_overlaps, gspn_mask_nms (+ their _ws_bytes): duplicate instance masks suppressed by pairwise IoU.
- * Additive at 21: gspn_mask_components, gspn_mask_component_filter (+ their _ws_bytes): fragments cut off on the mesh dropped from masks. */
+ * Additive at 21: gspn_mask_components, gspn_mask_component_filter (+ their _ws_bytes): fragments cut off on the mesh dropped from masks.
+ * Additive at 21: gspn_mask_hole_fill (+ gspn_mask_hole_fill_ws_bytes): the gaps a mask encloses on the mesh are filled. */
 #define GSPN_ABI_VERSION 21
 int gspn_dist_policy(void);
 int gspn_abi_version(void);
@@ -967,6 +968,42 @@ int gspn_mask_components(int r, int v, int f, const unsigned char* masks, const 
 long gspn_mask_component_filter_ws_bytes(int r, int v, int f);
 int gspn_mask_component_filter(int r, int v, int f, const unsigned char* masks, const int* faces, int min_vertices, double min_share, void* ws,
                                unsigned char* out, int* mask_points, int* ncomp, int* nkept, void* stream);
+
+/* ---------------- mask holes (gspn_amd/csrc/components.hip, additive at ABI 21) ---------------------------------------------- */
+
+/* One scan as above, with the vertices xyz (v,3) f32.  Rows are independent.  For row k, points_in[k] is the number of set vertices; the BOX
+ * is the closed axis-aligned box over the set vertices whose three coordinates are all finite (none: no box, no candidate); a vertex is
+ * INSIDE iff lo <= c && c <= hi on all three axes as IEEE float compares, so -0.0 and +0.0 are one place and a vertex with a NaN coordinate
+ * is never inside.  A CANDIDATE is an unset vertex inside the box; the candidate components are those of the candidates under the edges
+ * whose two ends are both candidates of row k.  A candidate component is OPEN iff an edge joins it to an unset vertex that is no candidate
+ * (an unset vertex outside the box), and TOUCHES iff an edge joins it to a set vertex.  A candidate component of s vertices is a HOLE iff
+ * it is not open, it touches, s <= max_vertices and (double)s <= max_share * (double)points_in[k], one IEEE double multiply and a
+ * non-strict compare.  max_vertices >= 0, max_share a double in [0, 1]; max_vertices = 0 is the identity up to the normalisation of a
+ * nonzero byte to 1.
+ *   out[k][x] (r,v) u8     = 1 iff x is set or lies in a hole, else 0; every byte written
+ *   mask_points[k] (r) i32 = points_in[k] + nfilled[k], the set bytes of out[k]
+ *   nholes[k], nfilled[k] (r) i32 = the holes filled in row k, and their vertices
+ *   label[k][x] (r,v) i32, or null = -2 where x is set, -1 where it is unset and no candidate, else the smallest vertex of its candidate
+ *                            component
+ * out may be masks itself.
+ *
+ * The union-find of the components on the candidates, then one pass over the faces that marks what each component borders; every loop
+ * carries the bound v, and nholes[k] = -1 marks a row in which one reached it, which a correct build never does.  Integer atomics only:
+ * the same bits on every call.  Row offsets are 64-bit.  ws: gspn_mask_hole_fill_ws_bytes(r, v, f) bytes -- two tables of
+ * v * ceil(r / 64) 64-bit words (candidates, set), then, each 16-byte aligned, r * v, r, 6 * r, r and r * v i32 (sizes with the flags of a
+ * root, marks, box keys, points_in, and the parents, which live in label instead when there is one) -- (0 for sizes the call declines, and
+ * for r or v == 0), 16-byte aligned; it need not be initialised and nothing is read from it that the call did not write.
+ * GSPN_ERR_ARG for a negative size, a null pointer (ws included; faces may be null when f == 0, label may always be null),
+ * max_vertices < 0, max_share NaN or outside [0, 1]; GSPN_ERR_UNSUPPORTED for r > GSPN_MASK_HOLE_FILL_MAX_R, v > GSPN_MASK_HOLE_FILL_MAX_V,
+ * f > GSPN_MASK_HOLE_FILL_MAX_F or a ws that is not 16-byte aligned, all before anything is launched, an argument error first; r or
+ * v == 0 then returns 0 and writes nothing, and with f == 0 there are no holes.  No host synchronisation, nothing allocated, static
+ * shapes: a call with a caller-held ws captures in a graph. */
+#define GSPN_MASK_HOLE_FILL_MAX_R 1024
+#define GSPN_MASK_HOLE_FILL_MAX_V (1 << 24)
+#define GSPN_MASK_HOLE_FILL_MAX_F (1 << 26)
+long gspn_mask_hole_fill_ws_bytes(int r, int v, int f);
+int gspn_mask_hole_fill(int r, int v, int f, const unsigned char* masks, const int* faces, const float* xyz, int max_vertices,
+                        double max_share, void* ws, unsigned char* out, int* mask_points, int* nholes, int* nfilled, int* label, void* stream);
 
 /* ---------------- train.py: the per-step batch, the reference's optimisers, the running loss sums (gspn_amd/csrc/train.hip, ABI 20) -------
  *

@@ -52,6 +52,9 @@
   components  mask components (gspn_amd/components.py) on the same rows, synth.scan_faces over `segments`' instances as the mesh (a bridge
             per 1000 vertices): mask_components and component_filter (their own workspace, and one the caller holds) against iterated
             scatter_reduce(amin) over the set edges in torch on the device, and scan_predictions with segments with and without the stage
+  holes     mask holes (gspn_amd/holes.py) on `components`' rows and mesh with gaps punched into the rows: hole_fill (its own workspace, and
+            one the caller holds with out) beside component_filter on the same rows, and scan_predictions with segments with and without
+            the stage
   evaluate the instance AP counts of one batch (gspn_amd/evaluate.py) on synthetic masks at Config(istrain=False)'s widths -- 100 rows, 100
             groups, 19 categories, the benchmark's 10 thresholds: instance_overlaps against the same counts written in torch on the device
             (masks.float() against a one-hot of seg * G + group), each alone and in front of instance_match, alternating in one process,
@@ -75,6 +78,7 @@ Prints one JSON line per (shape, measurement): median / min milliseconds over --
     python tools/spn_step.py --shapes 1x18000 --measures segments --warmup 5 --iters 30
     python tools/spn_step.py --shapes 1x18000 --measures mask_nms --warmup 5 --iters 30
     python tools/spn_step.py --shapes 1x18000 --measures components --warmup 5 --iters 30
+    python tools/spn_step.py --shapes 1x18000 --measures holes --warmup 5 --iters 30
     python tools/spn_step.py --shapes 2x18000,8x32768 --measures train --iters 20
     python tools/spn_step.py --shapes 2x18000 --measures evaluate --iters 30
     python tools/spn_step.py --shapes 1x150000 --measures data_prep --iters 9
@@ -956,6 +960,55 @@ def measure_components(a, shape, b, n, dev):
     print(json.dumps({"shape": shape, "kind": a.kind, "measure": "components", "rows": m, "iters": a.iters, **res}), flush=True)
 
 
+def measure_holes(a, shape, b, n, dev):
+    """--measures holes: `components`' rows and mesh -- 100 rows in output order behind the segment vote, synth.scan_faces
+    over `segments`' instances -- on the scene's own points and on synthetic scans of --lift-vertices vertices, with gaps punched into the
+    rows (every set vertex whose cube of 0.1 m falls on one residue in eleven is unset): hole_fill with a workspace it allocates and with
+    one the caller holds, beside component_filter on the same rows, and scan_predictions with segments with and without the stage,
+    alternating in one process.  Call times by device events."""
+    from gspn_amd import _lib, lift
+    from gspn_amd import components as MC
+    from gspn_amd import holes as MH
+    from gspn_amd import segments as SG
+    RP, pc, masks, ep, det_rois, (m, p, c, ns) = predict_inputs(a, b, n, dev)
+    own = pc[0].contiguous()
+    res = {}
+    for v in [n] + [int(t) for t in a.lift_vertices.split(",") if t]:
+        xyz = synth.scan_vertices(own.cpu().numpy(), np.zeros(n, np.int32), np.zeros(n, np.int32), v, 3)[0]
+        cube = np.floor(xyz.astype(np.float64)).astype(np.int64)
+        group = ((cube[:, 0] * 7 + cube[:, 1]) * 5 + cube[:, 2]).astype(np.int32)                    # instances: the 1 m cubes of the room
+        seg, s = SG.compact_segments(torch.from_numpy(synth.scan_segments(xyz, group % c, group, 0.25, 5)).to(dev))
+        faces = MC.mesh_faces(synth.scan_faces(xyz, group % c, group, 0.25, 5, bridges=v // 1000), v)
+        verts = torch.from_numpy(xyz).to(dev)
+        pred = lift.scan_predictions(ep, 0, verts, pc=pc, segments=seg, num_segments=s)
+        small = np.floor(xyz.astype(np.float64) / 0.1).astype(np.int64)
+        punched = torch.from_numpy(((small[:, 0] * 7 + small[:, 1] * 5 + small[:, 2] * 3) % 11) == 0).to(dev)
+        whole = pred["masks"][0].contiguous()
+        rows = (whole * ~punched).contiguous()
+        nf = int(faces.shape[0])
+        ws = torch.empty((int(_lib.lib().gspn_mask_hole_fill_ws_bytes(m, v, nf)),), dtype=torch.uint8, device=dev)
+        ws_f = torch.empty((int(_lib.lib().gspn_mask_component_filter_ws_bytes(m, v, nf)),), dtype=torch.uint8, device=dev)
+        held = torch.empty_like(rows)
+        limit = 200
+        out, points, nholes, nfilled, label = MH.hole_fill(rows, faces, verts, max_vertices=limit, label=True)
+        entry = res.setdefault("at_%d" % v, {})
+        entry.update({"mask_bytes": m * v, "faces": nf, "set_share": round(float((rows != 0).float().mean()), 5),
+                      "vertices_punched": int((whole != 0).sum()) - int((rows != 0).sum()), "candidates": int((label >= 0).sum()),
+                      "candidate_components": int((label == torch.arange(v, device=dev, dtype=torch.int32)).sum()), "holes": int(nholes.sum()),
+                      "vertices_filled": int(nfilled.sum()), "filled_were_set": int(((out != 0) & (rows == 0) & (whole != 0)).sum()),
+                      "bound_never_reached": bool((nholes >= 0).all()), "workspace_bytes": int(ws.numel())})
+        stage = dict(faces=faces, max_hole=limit)
+        entry.update(timed_alternating({
+            "hole_fill": lambda: MH.hole_fill(rows, faces, verts, max_vertices=limit),
+            "hole_fill_held_ws_and_out": lambda: MH.hole_fill(rows, faces, verts, max_vertices=limit, out=held, ws=ws),
+            "component_filter": lambda: MC.component_filter(rows, faces, min_vertices=100, min_share=0.1),
+            "component_filter_held_ws_and_out": lambda: MC.component_filter(rows, faces, min_vertices=100, min_share=0.1, out=held, ws=ws_f),
+            "scan_predictions_segments": lambda: lift.scan_predictions(ep, 0, verts, pc=pc, segments=seg, num_segments=s),
+            "scan_predictions_segments_holes": lambda: lift.scan_predictions(ep, 0, verts, pc=pc, segments=seg, num_segments=s, **stage)},
+            a.warmup, a.iters))
+    print(json.dumps({"shape": shape, "kind": a.kind, "measure": "holes", "rows": m, "iters": a.iters, **res}), flush=True)
+
+
 def instance_counts_torch(masks, pred_class, seg, group, c, g):
     """instance_overlaps' four outputs in torch on the device: masks.float() against a one-hot of seg * G + group, a (B, N, C * G) float tensor"""
     live = (seg > 0) & (seg < c) & (group >= 0) & (group < g)
@@ -1189,6 +1242,8 @@ def main():
             measure_mask_nms(a, shape, b, n, dev)
         if "components" in measures:
             measure_components(a, shape, b, n, dev)
+        if "holes" in measures:
+            measure_holes(a, shape, b, n, dev)
         if "train" in measures:
             measure_train(a, shape, b, n, dev)
         if "evaluate" in measures:

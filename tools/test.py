@@ -30,6 +30,10 @@ and mask components (the fragments of a per-vertex mask that the
   --components N     with --mesh_path (the faces of each scan's <scan>_vh_clean_2.ply) or --synthetic_vertices (synth.scan_faces): drop a
                      component of fewer than N >= 1 vertices; behind the segment vote, before mask NMS [default: off]
   --component_share S   with --components: also drop a component smaller than S of its mask's largest; in [0, 1] [default: 0]
+and mask holes (the gaps a per-vertex mask encloses on the mesh are filled):
+  --holes N          with --mesh_path or --synthetic_vertices, the faces as for --components: fill an enclosed gap of at most N >= 0
+                     vertices; behind --components, before mask NMS [default: off]
+  --hole_share S     with --holes: and of at most S of the mask's set vertices; in [0, 1] [default: 1]
 
     python tools/test.py --synthetic 5 --num_point 4096 --num_sample 64 --num_category 9 --batch_size 2 --model_path log/model.ckpt
     python tools/test.py --cache val.pt --list scannet_val.txt --model_path log_heads/model.ckpt --batch_size 8
@@ -41,6 +45,8 @@ and mask components (the fragments of a per-vertex mask that the
         --mesh_path scannet/mesh/scans --label_path scannet/label/scans --segments --mask_nms 0.5
     python tools/test.py --cache val.pt --list scannet_val.txt --model_path log_heads/model.ckpt --batch_size 8 \\
         --mesh_path scannet/mesh/scans --label_path scannet/label/scans --segments --components 100 --component_share 0.1 --mask_nms 0.5
+    python tools/test.py --cache val.pt --list scannet_val.txt --model_path log_heads/model.ckpt --batch_size 8 \\
+        --mesh_path scannet/mesh/scans --label_path scannet/label/scans --segments --components 100 --holes 200 --hole_share 0.25 --mask_nms 0.5
 """
 import argparse
 import os
@@ -87,6 +93,8 @@ def parser():
     ap.add_argument('--mask_nms', type=float, default=None, help='suppress per-vertex masks above this IoU with an earlier one of their label [default: off]')
     ap.add_argument('--components', type=int, default=None, help='drop the components of a per-vertex mask with fewer vertices than this [default: off]')
     ap.add_argument('--component_share', type=float, default=0.0, help="and those smaller than this share of the mask's largest [default: 0]")
+    ap.add_argument('--holes', type=int, default=None, help='fill the gaps a per-vertex mask encloses on the mesh of at most this many vertices [default: off]')
+    ap.add_argument('--hole_share', type=float, default=1.0, help="and of at most this share of the mask's set vertices [default: 1]")
     return ap
 
 
@@ -190,6 +198,12 @@ def main(argv=None):
         raise SystemExit("--components goes with the vertex modes: --mesh_path DIR or --synthetic_vertices V")
     if a.components is not None and (a.components < 1 or not 0.0 <= a.component_share <= 1.0):
         raise SystemExit("--components must be at least 1 and --component_share must lie in [0, 1]")
+    if a.holes is None and a.hole_share != 1.0:
+        raise SystemExit("--hole_share goes with --holes N")
+    if a.holes is not None and not (a.synthetic_vertices or a.mesh_path):
+        raise SystemExit("--holes goes with the vertex modes: --mesh_path DIR or --synthetic_vertices V")
+    if a.holes is not None and (a.holes < 0 or not 0.0 <= a.hole_share <= 1.0):
+        raise SystemExit("--holes must not be negative and --hole_share must lie in [0, 1]")
     if not 2 <= a.num_category <= len(SCANNET_LABEL_MAP):
         raise SystemExit("--num_category must lie in [2, %d], the classes of the ScanNet label map" % len(SCANNET_LABEL_MAP))
     dev = torch.device("cuda", a.gpu)
@@ -204,12 +218,13 @@ def main(argv=None):
         raise SystemExit("%s names %d scans, the cache holds %d scenes" % (a.list, len(scans), len(data)))
     tester = Tester(config_of(a), data, scans=scans, batch_size=a.batch_size, seed=a.seed, captured=not a.eager,
                     label_map=SCANNET_LABEL_MAP[:a.num_category], vote_th=a.vote_th, mask_nms_th=a.mask_nms,
-                    min_component=a.components, min_component_share=a.component_share)
+                    min_component=a.components, min_component_share=a.component_share, max_hole=a.holes, max_hole_share=a.hole_share)
     tester.restore(a.model_path, scope=a.restore_scope)
     if a.mesh_path or a.synthetic_vertices:
-        vertices = (mesh_vertices(a.mesh_path, a.label_path, scans, dev, a.segments, a.components is not None) if a.mesh_path
+        meshed = a.components is not None or a.holes is not None      # the faces are read or drawn for either stage
+        vertices = (mesh_vertices(a.mesh_path, a.label_path, scans, dev, a.segments, meshed) if a.mesh_path
                     else synthetic_vertices(cache, a.synthetic_vertices, a.seed, a.segment_cell if a.segments else None,
-                                            a.segment_cell if a.components is not None else None))
+                                            a.segment_cell if meshed else None))
         result = tester.run_vertices(None if a.no_files else a.out, vertices, evaluate=bool(a.synthetic_vertices or a.label_path))
         if result is None:
             print("per-vertex masks written to %s (no --label_path: nothing to evaluate against)" % os.path.join(a.out, "pred_vertices"))

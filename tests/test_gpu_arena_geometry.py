@@ -692,7 +692,7 @@ def grouppoint_grad_ws():
     def run():
         g, ws = torch.empty((b, n, c), device="cuda"), _exact_ws(lib.gspn_grouppoint_grad_ws_bytes(b, n, c, m, ns))
         assert lib.gspn_grouppoint_grad_ws(b, n, c, m, ns, _p(t_go), _p(t_idx), _p(g), _p(ws), _st()) == 0
-        torch.cuda.synchronize()
+        torch.cuda.current_stream().synchronize()
         np.testing.assert_array_equal(g.cpu().numpy(), ref)
         return g
     return Case("gspn_grouppoint_grad_ws c=6", run, note="called through ctypes: the Python ops take the inverse-list gathers instead")
@@ -711,7 +711,7 @@ def scatteraddpoint_ws():
     def run():
         g, ws = torch.empty((b, n, 3), device="cuda"), _exact_ws(lib.gspn_scatteraddpoint_ws_bytes(b, n, m))
         assert lib.gspn_scatteraddpoint_ws(b, n, m, _p(t_go), _p(t_idx), _p(g), _p(ws), _st()) == 0
-        torch.cuda.synchronize()
+        torch.cuda.current_stream().synchronize()
         np.testing.assert_array_equal(g.cpu().numpy(), ref)
         return g
     return Case("gspn_scatteraddpoint_ws", run, note="called through ctypes")
@@ -730,7 +730,7 @@ def threeinterpolate_grad_ws():
     def run():
         g, ws = torch.empty((b, m, c), device="cuda"), _exact_ws(lib.gspn_threeinterpolate_grad_ws_bytes(b, n, c, m))
         assert lib.gspn_threeinterpolate_grad_ws(b, n, c, m, _p(t_go), _p(t_idx), _p(t_w), _p(g), _p(ws), _st()) == 0
-        torch.cuda.synchronize()
+        torch.cuda.current_stream().synchronize()
         np.testing.assert_array_equal(g.cpu().numpy(), ref)
         return g
     return Case("gspn_threeinterpolate_grad_ws c=37", run, note="called through ctypes")

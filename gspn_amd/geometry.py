@@ -60,6 +60,9 @@ def sa_front(xyz, new_xyz, idx, shift=None):
     """pointnet_util.py:41-42 reduced to what depends on coordinates only: rel[r] = (xyz[idx[r]] - centre, 0) and the source row
     gidx[r] of every grouped row r -- the inputs of the fused front end (gspn_mlp_fwd_gather), 20 bytes per grouped row.
     shift (b, npoint, 3), optional: multi_encoding_net's per-seed shift (model_rpointnet.py:56-57), subtracted after the centre."""
+    # the kernel reads all three through bare pointers: a strided xyz would be read as if it were contiguous (this runs on the host's side of
+    # every step, beside the captured layers: .contiguous() hands a contiguous tensor back as it is)
+    xyz, new_xyz, idx = xyz.contiguous(), new_xyz.contiguous(), idx.contiguous()
     b, n, _ = xyz.shape
     _, m, ns = idx.shape
     rel = torch.empty((b * m * ns, 4), dtype=torch.float32, device=xyz.device)

@@ -20,7 +20,7 @@ import torch
 
 from . import _lib as L
 from . import tf_util
-from .mlp import LayerParams, mlp_linear, mlp_stack
+from .mlp import LayerParams, layer_typed, mlp_linear, mlp_stack
 from .pointnet_util import _mlp_layers
 from .roi import _crop_gather_grad, _Lists, points_cropping
 
@@ -78,8 +78,8 @@ def crop_linear(pc, pc_fea, pc_center, rois, masks_selection_idx, lp, normalize_
     rois (B, R, 6) zero padded, masks_selection_idx (B, R, P) int32, lp: the layer's LayerParams with weights (C + 6, cout) in the order
     [features, centre xyz, coordinate xyz] -> (B, R, P, cout), before batch norm and activation.  Gradients flow to pc_fea, pc_center,
     the weights and the biases; rois is detached, as in points_cropping.
-    Raises NotImplementedError, before anything has run, for C > 1024, cout not a multiple of 4 or > 256, or operands that are not
-    16-byte aligned."""
+    Raises NotImplementedError, before anything has run, for C > 1024, cout not a multiple of 4 or > 256, weights that are not contiguous,
+    or weights / biases / pc_fea that are not 16-byte aligned (the side kernels read them through bare pointers; a strided bias is copied)."""
     idx = L.need(masks_selection_idx, torch.int32, 3, "masks_selection_idx")
     pc = L.need(pc.detach(), torch.float32, 3, "pc")
     pc_fea = L.need(pc_fea, torch.float32, 3, "pc_fea")
@@ -92,17 +92,16 @@ def crop_linear(pc, pc_fea, pc_center, rois, masks_selection_idx, lp, normalize_
             or tuple(rois.shape) != (b, r, 6):
         raise ValueError("crop_linear: expected pc, pc_center (B, N, 3), pc_fea (B, N, C), rois (B, R, 6), masks_selection_idx (B, R, P), got "
                          "%s, %s, %s, %s, %s" % (tuple(pc.shape), tuple(pc_center.shape), tuple(pc_fea.shape), tuple(rois.shape), tuple(idx.shape)))
-    if lp.weights.dim() != 2 or lp.weights.shape[0] != c + 6:
-        raise ValueError("crop_linear: the layer's weights must be (C + 6, cout) = (%d, cout), got %s" % (c + 6, tuple(lp.weights.shape)))
-    cout = lp.weights.shape[1]
+    cout = layer_typed(lp, c + 6, "crop_linear")            # weights (C + 6, cout), biases (cout): dtype, rank, size
+    biases = lp.biases.contiguous()                         # (a strided bias is copied, under autograd; the weights are sliced below and must be in place)
     if c > tf_util._MLP_MAX_CHANNELS or cout % 4 or cout > CROP_LINEAR_MAX_COUT:
         raise NotImplementedError("crop_linear: C <= %d and cout a multiple of 4, <= %d (got C %d, cout %d)"
                                   % (tf_util._MLP_MAX_CHANNELS, CROP_LINEAR_MAX_COUT, c, cout))
     w_fea, w_side = lp.weights[:c], lp.weights[c:]
-    if not (lp.weights.is_contiguous() and _aligned16(w_fea) and _aligned16(w_side) and _aligned16(lp.biases) and _aligned16(pc_fea)):
-        raise NotImplementedError("crop_linear: the weights (and their rows C..C+5), the biases and pc_fea must be 16-byte aligned")
-    T = mlp_linear(pc_fea.reshape(b * n, c), c, LayerParams(w_fea, torch.zeros_like(lp.biases), False))
-    return _CropLinearSide.apply(T, pc_center, w_side, lp.biases, pc, rois, idx, bool(normalize_crop_region), _Lists(idx, n))
+    if not (lp.weights.is_contiguous() and _aligned16(w_fea) and _aligned16(w_side) and _aligned16(biases) and _aligned16(pc_fea)):
+        raise NotImplementedError("crop_linear: the weights (contiguous, and their rows C..C+5), the biases and pc_fea must be 16-byte aligned")
+    T = mlp_linear(pc_fea.reshape(b * n, c), c, LayerParams(w_fea, torch.zeros_like(biases), False))
+    return _CropLinearSide.apply(T, pc_center, w_side, biases, pc, rois, idx, bool(normalize_crop_region), _Lists(idx, n))
 
 
 # --------------------------------------------------------------------------- the layer behind concat(tile(global), local), split
@@ -151,17 +150,16 @@ def tile_linear(local_rows, global_rows, lp, p):
     if p <= 0 or groups <= 0 or rows != groups * p:
         raise ValueError("tile_linear: local_rows (G*P, cl) and global_rows (G, cg) with P = %d, got %s and %s"
                          % (p, tuple(local_rows.shape), tuple(global_rows.shape)))
-    if lp.weights.dim() != 2 or lp.weights.shape[0] != cg + cl:
-        raise ValueError("tile_linear: the layer's weights must be (cg + cl, cout) = (%d, cout), got %s" % (cg + cl, tuple(lp.weights.shape)))
-    cout = lp.weights.shape[1]
+    cout = layer_typed(lp, cg + cl, "tile_linear")          # weights (cg + cl, cout), biases (cout): dtype, rank, size
+    biases = lp.biases.contiguous()                         # (a strided bias is copied, under autograd)
     most = tf_util._MLP_MAX_CHANNELS
     if cout % 4 or cout > most or cg > most or cl > most or rows >= 2 ** 31:
         raise NotImplementedError("tile_linear: cout a multiple of 4, cg, cl, cout <= %d, G*P < 2^31 (got cg %d, cl %d, cout %d, G*P %d)"
                                   % (most, cg, cl, cout, rows))
-    if not (lp.weights.is_contiguous() and _aligned16(lp.weights) and _aligned16(lp.biases)):
+    if not (lp.weights.is_contiguous() and _aligned16(lp.weights) and _aligned16(biases)):
         raise NotImplementedError("tile_linear: the weights and the biases must be contiguous and 16-byte aligned")
-    y_local = mlp_linear(local_rows, cl, LayerParams(lp.weights[cg:], torch.zeros_like(lp.biases), False))
-    y_global = mlp_linear(global_rows, cg, LayerParams(lp.weights[:cg], lp.biases, False))
+    y_local = mlp_linear(local_rows, cl, LayerParams(lp.weights[cg:], torch.zeros_like(biases), False))
+    y_global = mlp_linear(global_rows, cg, LayerParams(lp.weights[:cg], biases, False))
     return _TileAdd.apply(y_local, y_global, p)
 
 

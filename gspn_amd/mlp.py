@@ -15,6 +15,7 @@ import types
 import torch
 
 from . import _lib as L
+from ._args import _typed
 
 BN_EPS = 1e-3      # tf.contrib.layers.batch_norm default epsilon (tf_util.py:529-534 passes none)
 
@@ -121,14 +122,95 @@ class LayerParams:
         return t
 
 
+def _label(what, i):
+    return what if i is None else "%s: layer %d" % (what, i)
+
+
+def _vector_typed(t, cout, updated, what, i, name):
+    """one per-channel tensor of a layer: float32, 1-D, cout long; a moving statistic (`updated`) contiguous besides.  (The label is put
+    together only when a rule fails: this runs for every layer tensor on every call.)"""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 1:
+        _typed(t, torch.float32, 1, "%s: %s" % (_label(what, i), name))
+    if t.shape[0] != cout:
+        raise ValueError("%s: %s must have cout = %d elements, got %d" % (_label(what, i), name, cout, t.shape[0]))
+    if updated and not t.is_contiguous():
+        # updated in place through its data pointer: a copy would take the update, a strided write would land somewhere else
+        raise ValueError("%s: %s is updated in place and must be contiguous, got strides %s" % (_label(what, i), name, tuple(t.stride())))
+
+
+def _on_device(t, dev, what, i, name):
+    if t.device != dev:
+        raise L.GspnHipError("%s: %s is on %s, the input on %s" % (_label(what, i), name, t.device, dev))
+
+
+def layer_typed(lp, cin, what, i=None):
+    """dtype, rank and shape rules of one LayerParams (ValueError wherever the tensors live, like _args._typed) -> cout"""
+    w = lp.weights
+    if not isinstance(w, torch.Tensor) or w.dtype != torch.float32 or w.dim() != 2:
+        _typed(w, torch.float32, 2, "%s: weights" % _label(what, i))
+    if cin is not None and w.shape[0] != cin:
+        raise ValueError("%s: weights must be (cin, cout) = (%d, cout), got %s" % (_label(what, i), cin, tuple(w.shape)))
+    cout = w.shape[1]
+    _vector_typed(lp.biases, cout, False, what, i, "biases")
+    if lp.bn:
+        _vector_typed(lp.beta, cout, False, what, i, "beta")
+        _vector_typed(lp.gamma, cout, False, what, i, "gamma")
+        _vector_typed(lp.moving_mean, cout, True, what, i, "moving_mean")
+        _vector_typed(lp.moving_variance, cout, True, what, i, "moving_variance")
+    return cout
+
+
+def layer_on_device(lp, dev, what, i=None):
+    """the device rule, after the shape rules: every tensor of the layer on `dev` (GspnHipError, like L.need) -> a LayerParams whose tensors the
+    kernels can read through a bare pointer.  A non-contiguous weight / bias / beta / gamma (a .t() view, a slice of a wider buffer) is
+    copied here, under autograd: the gradient the stack computes for the copy reaches the caller's tensor with that tensor's shape and
+    strides.  The copy is a new allocation, so it never matches a gradient sink: such a gradient goes through autograd."""
+    _on_device(lp.weights, dev, what, i, "weights")
+    _on_device(lp.biases, dev, what, i, "biases")
+    contiguous = lp.weights.is_contiguous() and lp.biases.is_contiguous()
+    if lp.bn:
+        for name in ("beta", "gamma", "moving_mean", "moving_variance"):
+            _on_device(getattr(lp, name), dev, what, i, name)
+        contiguous = contiguous and lp.beta.is_contiguous() and lp.gamma.is_contiguous()
+    if contiguous:
+        return lp
+    return LayerParams(lp.weights.contiguous(), lp.biases.contiguous(), lp.bn, lp.beta.contiguous() if lp.bn else None,
+                       lp.gamma.contiguous() if lp.bn else None, lp.moving_mean, lp.moving_variance)
+
+
+def checked_layers(x, ndim, layers, cin, what):
+    """The argument rules of everything that hands LayerParams to the library (mlp_stack, mlp_linear, tf_util's wide-input layer): dtype,
+    rank and shape of x and of every layer tensor first (ValueError), then the device rule (GspnHipError) -> (x contiguous, layers with
+    contiguous tensors).  cin: the first layer's input width (None: not checked); each later layer takes the width the one before it gives."""
+    _typed(x, torch.float32, ndim, "x")
+    for i, lp in enumerate(layers):
+        cin = layer_typed(lp, cin, what, i)
+    x = L.need(x, torch.float32, ndim, "x")
+    return x, [layer_on_device(lp, x.device, what, i) for i, lp in enumerate(layers)]
+
+
+def checked_bn(x, gamma, beta, moving_mean, moving_variance, what):
+    """the same rules for a stand-alone batch norm over the rows of x (rows, c) -> (x, gamma, beta) contiguous; the moving statistics, which
+    the kernels update in place, must be contiguous as they are"""
+    _typed(x, torch.float32, 2, "x")
+    named = (("gamma", gamma, False), ("beta", beta, False), ("moving_mean", moving_mean, True), ("moving_variance", moving_variance, True))
+    for name, t, updated in named:
+        _vector_typed(t, x.shape[1], updated, what, None, name)
+    x = L.need(x, torch.float32, 2, "x")
+    for name, t, _ in named:
+        _on_device(t, x.device, what, None, name)
+    return x, gamma.contiguous(), beta.contiguous()
+
+
 # ---- gradient sinks (r06) ---------------------------------------------------------------------------------------------------------
 # A caller that keeps all parameter gradients in ONE flat buffer (parallel.FlatGradBucket: the operand of the gradient all-reduce and of the
 # one-launch Adam) can register, per parameter, the slice of that buffer its gradient belongs in (FlatGradBucket.attach_sinks()).  The backward
 # pass of a stack then lets its reduction kernels write dW / dbias / dbeta / dgamma STRAIGHT into those slices and returns None to autograd for
 # them: no per-step `cat` of ~60 gradient tensors into the bucket (the last library kernel inside the captured step but autograd's two gradient
 # accumulations).  Keyed by the parameter's data pointer (LayerParams.weights is a fresh VIEW of the stored kernel on every forward); an entry
-# holds a weak reference to the stored parameter and dies with it.  A parameter used by two stacks in one backward pass is written once, the
-# second gradient goes through autograd and FlatGradBucket.flatten() adds it.
+# holds a weak reference to the stored parameter and dies with it.  A parameter used by two stacks in one backward pass is written once; its
+# .grad is the slice from then on, so the second gradient, which goes through autograd, is added to the slice by autograd's own accumulation.
+# The rules of a claim -- frozen parameters, abandoned steps, torch.autograd.grad -- are FlatGradBucket's docstring and DESIGN.md 4.5.
 GRAD_SINKS = {}
 
 
@@ -139,29 +221,73 @@ class _Sink:
         self.bucket, self.index, self.view, self.ref = bucket, index, view, ref
 
 
+def _delivers_grad(base):
+    """does the backward pass that is running accumulate into base.grad?  torch.autograd.grad() and backward(inputs=...) without `base`
+    do not: a gradient written into the bucket would be lost to the caller, so such a pass gets its gradients through autograd.
+    Asks the engine (torch._C._will_engine_execute_node on the parameter's AccumulateGrad node: a private call, probed once by
+    FlatGradBucket.attach_sinks()).  Under torch.autograd.grad the engine refuses the question for a leaf with a RuntimeError that names
+    autograd.grad: only that error means "no"; any other is raised."""
+    with torch.enable_grad():
+        acc = base.view_as(base).grad_fn.next_functions[0][0]
+    try:
+        return bool(torch._C._will_engine_execute_node(acc))
+    except RuntimeError as e:
+        if "autograd.grad" in str(e):
+            return False
+        raise
+
+
+def probe_engine_query():
+    """attach_sinks() calls this once: a plain backward() must answer True for a leaf, or sinks would switch themselves off silently (or
+    claim under torch.autograd.grad) after a torch update.  CPU tensors, no launch."""
+    seen = []
+    w = torch.ones(1, requires_grad=True)
+
+    def product():
+        y = w * 2.0
+        y.register_hook(lambda g: seen.append(_delivers_grad(w)))       # (runs inside the backward pass, like a node's backward)
+        return y.sum()
+
+    product().backward()
+    torch.autograd.grad(product(), [w])
+    if seen != [True, False]:
+        raise L.GspnHipError("gradient sinks: torch's engine no longer tells backward() from autograd.grad() (got %s): sinks cannot be attached" % seen)
+
+
 def _grad_buffer(param, sunk):
-    """where the gradient of `param` is to be written: its registered bucket slice (first gradient of this backward pass) or a fresh tensor"""
+    """where the gradient of `param` is to be written: its registered bucket slice (first gradient since the parameter's .grad was last
+    reset) or a fresh tensor.  A claim shows on the parameter: its .grad becomes the slice.  Whatever autograd delivers afterwards -- a second
+    use of the layer, a second backward pass -- is then added to the slice by autograd itself; a .grad that was reset since (None, or another
+    tensor) marks the claim as one of an abandoned step, and the slice is claimed again and overwritten.  A parameter that does not require a
+    gradient gets a scratch tensor and no claim: its slice stays zero."""
     e = GRAD_SINKS.get(param.data_ptr())
     if e is not None:
         base = e.ref()
         if base is None or base.data_ptr() != param.data_ptr() or base.numel() != param.numel():
             GRAD_SINKS.pop(param.data_ptr(), None)                 # the parameter is gone (or moved): never write through a stale entry
-        elif e.index not in e.bucket._written and param.dtype == torch.float32 and param.is_contiguous():
-            e.bucket._written.add(e.index)
-            v = e.view.view(param.shape)
-            sunk.add(v.data_ptr())
-            return v
+        elif param.requires_grad and base.requires_grad and param.dtype == torch.float32 and param.is_contiguous():
+            g = base.grad
+            mine = g is not None and g.data_ptr() == e.view.data_ptr() and g.numel() == e.view.numel()
+            if (g is None or mine) and not (mine and e.index in e.bucket._written) and _delivers_grad(base):
+                e.bucket._written.add(e.index)
+                base.grad = e.view.view(base.shape)
+                v = e.view.view(param.shape)
+                sunk.add(v.data_ptr())
+                return v
     return torch.empty_like(param)
 
 
 def _grad_release(param, buf, sunk):
     """undo _grad_buffer(param, sunk) for a launch that declined before it wrote `buf`: the slice is claimable again, so whichever launch does
-    produce the gradient writes it there (a slot left claimed but unwritten would get that gradient ADDED by flatten(), onto whatever the
+    produce the gradient writes it there (a slot left claimed but unwritten would get that gradient ADDED by autograd, onto whatever the
     slice held -- the previous step's gradient)"""
     if buf.data_ptr() in sunk:
         e = GRAD_SINKS.get(param.data_ptr())
         if e is not None:
             e.bucket._written.discard(e.index)
+            base = e.ref()
+            if base is not None and base.grad is not None and base.grad.data_ptr() == e.view.data_ptr():
+                base.grad = None
         sunk.discard(buf.data_ptr())
 
 
@@ -304,9 +430,21 @@ class _MlpStack(torch.autograd.Function):
         ctx.gather = gather
         ctx.pre = pre
         ctx.saved = saved
-        # backward re-reads the weights and gamma: an in-place update between forward and backward would silently change the result
-        # (autograd's own check only covers save_for_backward tensors; these are kept as attributes so the layer list stays one object)
-        ctx.versions = [(lp.weights._version, lp.gamma._version if lp.bn else 0) for lp in layers]
+        # backward re-reads the weights and gamma, the top layer's biases of a pooled stack, the input x -- the feature matrix of the gathered and the
+        # pre-aggregated form -- and those forms' index / weight / side tensors: an in-place update between forward and backward would
+        # silently change the result (autograd's own check only covers save_for_backward tensors; these are kept as attributes so the
+        # layer list stays one object)
+        reread = [("x", x)]
+        for li, lp in enumerate(layers):
+            reread += [("layer %d weights" % li, lp.weights)] + ([("layer %d gamma" % li, lp.gamma)] if lp.bn else [])
+        if pool_ns:
+            reread.append(("layer %d biases" % (len(layers) - 1), layers[-1].biases))          # (gspn_mlp_bwd_data_pooltop rebuilds y from them)
+        if gather is not None:
+            reread += [("gather[%r]" % k, gather.get(k)) for k in ("gidx", "rel", "idx", "order", "offsets")]
+        if pre is not None:
+            reread += [("preagg[%r]" % k, pre.get(k)) for k in ("idx", "w", "side")]
+            reread += [("preagg['scatter_reads'][%d]" % k, t) for k, t in enumerate(pre.get("scatter_reads", ()))]
+        ctx.versions = [(name, t, t._version) for name, t in reread if t is not None]
         ctx.arg = arg
         ctx.pool_yarg = pool[0] if pool is not None else None
         if pool_ns:
@@ -321,9 +459,10 @@ class _MlpStack(torch.autograd.Function):
     def backward(ctx, d_out):
         spec = ctx.spec
         layers = spec["layers"]
-        for lp, (vw, vg) in zip(layers, ctx.versions):
-            if lp.weights._version != vw or (lp.bn and lp.gamma._version != vg):
-                raise RuntimeError("mlp_stack: a weight or gamma tensor was modified in place between forward and backward")
+        for name, t, version in ctx.versions:
+            if t._version != version:
+                raise RuntimeError("mlp_stack: %s, which backward reads again, was modified in place between forward and backward "
+                                   "(it is at version %d, the forward pass saw version %d)" % (name, t._version, version))
         d_out = d_out.contiguous()
         dev = d_out.device
         is_training = bool(spec["is_training"])
@@ -711,7 +850,7 @@ def mlp_linear(x, cin, lp):
     """x (rows, ld >= cin) -> x[:, :cin].W + b for a LayerParams without batch-norm."""
     if lp.bn:
         raise ValueError("mlp_linear is the no-BN, no-activation layer")
-    x = L.need(x, torch.float32, 2, "x")
+    x, (lp,) = checked_layers(x, 2, [lp], cin, "mlp_linear")
     return _Linear.apply(x, cin, lp.weights, lp.biases)
 
 
@@ -729,7 +868,9 @@ def _mlp_stack_sync_bn(x, cin, layers, decay, pool_ns):
 
 
 def _aligned16(t):
-    return t is None or not t.is_contiguous() or t.data_ptr() % 16 == 0          # (a non-contiguous tensor is copied -- to a fresh allocation -- before use)
+    # (a non-contiguous tensor never reaches a kernel: L.need copies the input x, layer_on_device a layer tensor, each to a fresh -- aligned --
+    #  allocation, before use)
+    return t is None or not t.is_contiguous() or t.data_ptr() % 16 == 0
 
 
 def preagg_ok(layers, is_training, c, x=None):
@@ -750,11 +891,14 @@ def mlp_stack(x, cin, layers, is_training, bn_decay, pool_ns=None, grad_cols=Non
     dict(rows, c, xyz_first, gidx, rel, dims=(b, n, m, ns), idx, order, offsets), see pointnet_util.pointnet_sa_module; cin = 3 + c.
     preagg (pre-aggregated first layer): x is the (source rows, ldf) feature matrix; dict(rows, c, T, idx, w, per_scene_rows,
     per_scene_src, side, side_ld, side_n, wf0, ws0 [first rows of W_feat / W_side inside the layer's weights], scatter [callable:
-    (dY (rows, cout), cout) -> (source rows, cout), the transpose of the aggregation]) -- see pointnet_util.
+    (dY (rows, cout), cout) -> (source rows, cout), the transpose of the aggregation], scatter_reads [optional: the tensors that callable
+    reads, so that an in-place change of one between forward and backward is refused like one of x]) -- see pointnet_util.
+    Every layer tensor is validated (checked_layers); a non-contiguous weight / bias / beta / gamma is copied, a non-contiguous moving
+    statistic is refused.  Backward raises RuntimeError when a tensor it reads again was modified in place since the forward pass.
     Raises NotImplementedError (before anything has run) when the first layer's shape is outside what the gathering kernels take."""
     if not layers:
         raise ValueError("mlp_stack needs at least one layer")
-    x = L.need(x, torch.float32, 2, "x")
+    x, layers = checked_layers(x, 2, layers, cin, "mlp_stack")
     if gather is not None:
         if x.shape[1] % 4 or x.data_ptr() % 16 or gather["c"] > x.shape[1] or cin != 3 + gather["c"] or len(layers) < 2 or layers[0].weights.shape[1] % 4:
             raise NotImplementedError("mlp_stack(gather=): needs 16-byte aligned feature rows, >= 2 layers and a first layer of 4k output channels")

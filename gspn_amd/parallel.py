@@ -106,7 +106,15 @@ class FlatGradBucket:
     """Flat fp32 bucket over a fixed parameter list.  flatten(): one `cat` gathers the fresh gradients into the persistent bucket and
     every p.grad is re-pointed at its slice (views, no copies back); all_reduce(): ONE all_reduce(SUM) + scale averages the bucket
     over ranks.  Use with optimizer.zero_grad(set_to_none=True) so backward assigns gradients instead of accumulating into the views.
-    The bucket's storage never changes, so a captured step (graph.py) can end in flatten() and be replayed."""
+    The bucket's storage never changes, so a captured step (graph.py) can end in flatten() and be replayed.
+
+    With gradient sinks (attach_sinks()) a backward pass writes a gradient straight into its slice and CLAIMS the slice: the index joins
+    `_written` and the parameter's .grad becomes the slice, so that whatever autograd delivers afterwards (a second use of the layer, a
+    second backward pass) is accumulated into it.  A claim lives no longer than the step it was made in: flatten(), discard() and the flat
+    optimisers' zero_grad() clear `_written`, and a claimed parameter whose .grad has been reset since (None, or another tensor) counts as
+    abandoned -- the next backward pass claims and overwrites its slice, flatten() copies or zeroes it, as it would without sinks.
+    A parameter with requires_grad=False is never claimed: its slice stays zero.  A pass that does not accumulate into .grad
+    (torch.autograd.grad, backward(inputs=...) without the parameter) claims nothing and gets its gradients through autograd."""
 
     def __init__(self, params):
         self.params = [p for p in params]
@@ -128,6 +136,7 @@ class FlatGradBucket:
         use of the same layer in one backward pass) are still folded in by flatten()."""
         import weakref
         from . import mlp
+        mlp.probe_engine_query()                    # a claim asks torch's engine whether the running pass delivers .grad: refuse to attach if it cannot tell
         for k in [k for k, e in mlp.GRAD_SINKS.items() if e.bucket is self]:
             del mlp.GRAD_SINKS[k]
         for i, (p, v) in enumerate(zip(self.params, self._views)):
@@ -136,19 +145,30 @@ class FlatGradBucket:
         self.sinks = True
         return self
 
+    def detach_sinks(self):
+        """remove this bucket's entries from gspn_amd.mlp.GRAD_SINKS (they hold the bucket, and its flat buffer, alive) and forget its claims"""
+        from . import mlp
+        for k in [k for k, e in mlp.GRAD_SINKS.items() if e.bucket is self]:
+            del mlp.GRAD_SINKS[k]
+        self.sinks = False
+        self._written.clear()
+        return self
+
+    def discard(self):
+        """forget the claims of a step that ends without flatten() (a backward pass that raised, a step skipped after its backward)"""
+        self._written.clear()
+
     def _flatten_sunk(self):
-        """flatten() when (some) gradients already sit in their slices: only what autograd delivered separately is copied / added"""
+        """flatten() when (some) gradients already sit in their slices: only what autograd delivered separately is copied.  A claimed slice
+        IS its parameter's .grad (mlp._grad_buffer), and autograd adds later gradients to it in place; a .grad that is anything else belongs
+        to this step alone, whatever an abandoned claim left in the slice"""
         with torch.no_grad():
-            for i, (p, v) in enumerate(zip(self.params, self._views)):
+            for p, v in zip(self.params, self._views):
                 g = p.grad
-                fresh = g is not None and g.data_ptr() != v.data_ptr()
-                if i in self._written:
-                    if fresh:
-                        v.add_(g)                   # a second gradient of a parameter whose first one was written in place
-                elif fresh:
+                if g is None:
+                    v.zero_()                       # no gradient this step (or one claimed by a step abandoned since)
+                elif g.data_ptr() != v.data_ptr():
                     v.copy_(g)
-                elif g is None:
-                    v.zero_()                       # no gradient this step
                 p.grad = v
         self._written.clear()
         return self.flat
@@ -234,6 +254,7 @@ class FlatAdam:
             self._dev_state.copy_(torch.tensor([int(value), 0], dtype=torch.int64))
 
     def zero_grad(self, set_to_none=True):
+        self.bucket.discard()
         for p in self.bucket.params:
             if set_to_none:
                 p.grad = None

@@ -139,6 +139,7 @@ class _PadCols(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, ld):
+        x = L.need(x, torch.float32, 2, "x")                 # (the kernel reads rows of pitch c through a bare pointer)
         rows, c = x.shape
         out = torch.empty((rows, ld), dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
@@ -177,7 +178,8 @@ def _sa_stack_gathered(points, geometry, xyz_first, cin, layers, is_training, bn
             return gp.view(b * n, cout)
 
         pre = {"rows": b * m * ns, "c": c, "T": 1, "idx": geometry.gidx, "w": None, "per_scene_rows": 0, "per_scene_src": b * n,      # (global idx: per_scene_src = ALL source rows, the library's offset guard)
-               "side": geometry.rel, "side_ld": 4, "side_n": 3, "wf0": 3 if xyz_first else 0, "ws0": 0 if xyz_first else c, "scatter": scatter}
+               "side": geometry.rel, "side_ld": 4, "side_n": 3, "wf0": 3 if xyz_first else 0, "ws0": 0 if xyz_first else c, "scatter": scatter,
+               "scatter_reads": (order, offsets) if order is not None else (idx,)}
         return mlp_stack(feat, cin, layers, bool(is_training), bn_decay, pool_ns=nsample, preagg=pre)
     g = {"rows": b * m * ns, "c": c, "xyz_first": xyz_first, "gidx": geometry.gidx, "rel": geometry.rel, "dims": (b, n, m, ns),
          "idx": geometry.idx, "order": geometry.order, "offsets": geometry.offsets}
@@ -314,7 +316,8 @@ def _fp_stack_preagg(points2, points1, geometry, cin, layers, is_training, bn_de
         return g2.view(b * m, cout)
 
     pre = {"rows": b * n1, "c": c2, "T": 3, "idx": idx, "w": weight, "per_scene_rows": n1, "per_scene_src": m,
-           "side": side, "side_ld": max(c1, 1), "side_n": c1, "wf0": 0, "ws0": c2, "scatter": scatter}
+           "side": side, "side_ld": max(c1, 1), "side_n": c1, "wf0": 0, "ws0": c2, "scatter": scatter,
+           "scatter_reads": (order, offsets) if order is not None else ()}
     return mlp_stack(points2.reshape(b * m, c2), cin, layers, bool(is_training), bn_decay, pool_ns=None, preagg=pre)
 
 

@@ -277,10 +277,12 @@ class _CropGather(torch.autograd.Function):
     @staticmethod
     def forward(ctx, points, idx, lists):
         ctx.lists = lists
+        ctx.save_for_backward(idx)           # backward reads it again through `lists` (and builds the inverse lists from it on first use)
         return group_point(points, idx)
 
     @staticmethod
     def backward(ctx, grad_out):
+        ctx.saved_tensors                    # raises if idx was modified in place since the forward pass
         return _crop_gather_grad(ctx.lists, grad_out), None, None
 
 

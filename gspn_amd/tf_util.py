@@ -12,7 +12,7 @@ import math
 import torch
 
 from . import _lib as L
-from .mlp import mlp_linear, LayerParams, mlp_stack
+from .mlp import _Linear, checked_layers, mlp_linear, LayerParams, mlp_stack
 
 
 # --------------------------------------------------------------------------- variables / scopes
@@ -213,13 +213,14 @@ def _apply_wide_input_layer(x2d, cin, lp, relu, is_training, bn_decay):
     """A layer with more input channels than one MLP launch takes (shape_proposal_net's mu_sigma_x/conv0, model_rpointnet.py:385:
     128 + 768 + 256 = 1152 inputs): row blocks of the same weights on column blocks of the input, added in order, then the stand-alone
     batch norm and ReLU.  Same variables, same arithmetic up to the order of the sum over input channels."""
+    x2d, (lp,) = checked_layers(x2d, 2, [lp], cin, "wide-input layer")
     if lp.weights.shape[1] > _MLP_MAX_CHANNELS:
         raise NotImplementedError("a layer with more than %d input AND output channels" % _MLP_MAX_CHANNELS)
     y = None
     for a in range(0, cin, _MLP_MAX_CHANNELS):
         w = lp.weights[a:a + _MLP_MAX_CHANNELS]
         bias = lp.biases if a == 0 else torch.zeros_like(lp.biases)
-        part = mlp_linear(x2d[:, a:a + w.shape[0]].contiguous(), w.shape[0], LayerParams(w, bias, False))
+        part = _Linear.apply(x2d[:, a:a + w.shape[0]].contiguous(), w.shape[0], w, bias)       # (row blocks of the checked, contiguous weights)
         y = part if y is None else y + part
     if lp.bn:
         y = _BatchNormRows.apply(y, lp.gamma, lp.beta, lp.moving_mean, lp.moving_variance, bool(is_training),
@@ -254,7 +255,9 @@ class _BatchNormRows(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, mm, mv, is_training, decay):
         import ctypes
-        from .mlp import BN_EPS
+        from .mlp import BN_EPS, checked_bn
+        # (copies made here sit inside the node: the gradients backward returns for them reach the caller's own gamma / beta / x)
+        x, gamma, beta = checked_bn(x, gamma, beta, mm, mv, "batch_norm")
         lib = L.lib()
         rows, c = x.shape
         dev = x.device

@@ -224,6 +224,7 @@ class _FlatOptimizer:
         self.t = 0
 
     def zero_grad(self, set_to_none=True):
+        self.bucket.discard()
         for p in self.bucket.params:
             if set_to_none:
                 p.grad = None

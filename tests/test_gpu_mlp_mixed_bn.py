@@ -144,8 +144,9 @@ def _two_steps(sinks):
             x = place_x(x0.cuda(), None)
             out = M.mlp_stack(x, cin, layers, True, 0.7, pool_ns=ns)
             out.backward(place_grad(gos[step], None))
-            if sinks:                                              # every gradient went straight into its slice: autograd got none of them
-                assert all(p.grad is None for p in params)
+            if sinks:                                              # every gradient went straight into its slice: autograd got none of them, .grad IS the slice
+                assert len(bucket._written) == len(params)
+                assert all(p.grad is not None and p.grad.data_ptr() == v.data_ptr() for p, v in zip(params, bucket._views))
             bucket.flatten()
             torch.cuda.synchronize()
             assert all(p.grad.data_ptr() == v.data_ptr() for p, v in zip(params, bucket._views))

@@ -611,7 +611,8 @@ def test_gradient_sinks_leave_the_bucket_bit_identical_and_capture_without_a_cat
                 if sinks:
                     st["bucket"].attach_sinks()
             elif sinks:
-                assert all(p.grad is None for p in store.parameters())      # nothing went through autograd: every gradient was written in place
+                # nothing went through autograd: every gradient was written in place, and each claim shows as the parameter's .grad BEING its slice
+                assert all(p.grad is not None and p.grad.data_ptr() == v.data_ptr() for p, v in zip(store.parameters(), st["bucket"]._views))
                 assert len(st["bucket"]._written) == len(store.parameters())
             st["bucket"].flatten()
             return out.detach()

@@ -10,9 +10,8 @@
 // walk over stale values still descends inside x's component and ends on a vertex that WAS a root; the compare-and-swap, which executes
 // at the memory side, is what decides, and it fails on a vertex that no longer is one.
 //
-//   init     grid (chunks of 16 bytes / 256, r) over the ADDRESS of the row (the walk of mask_rows.h), one chunk per lane;
-//            parent[k][x] = set ? x : -1, size[k][x] = 0, written 64 consecutive vertices per wave and pass (the lanes trade their 16 bits
-//            by shuffles), and the row's counters zeroed
+//   init     grid (chunks of 16 bytes / 256, r) over the ADDRESS of the row, one chunk per lane (the address walk and the wave walk of
+//            mask_rows.h): parent[k][x] = set ? x : -1, size[k][x] = 0, and the row's counters zeroed
 //   table    grid (v / 256, words): the VERTEX-MAJOR bit table, words = ceil(r / 64) 64-bit words per vertex, bit k = set in row k, read
 //            from parent (coalesced dwords) so that rows need no alignment
 //   hook     one lane per face, grid-stride: the face is read ONCE, not r times; each of its three edges ANDs its ends' words and does one
@@ -25,10 +24,9 @@
 //            one integer atomicAdd
 //   stats    one lane per (row, vertex), roots alone (comp == x): ncomp += 1, largest = max(size), one atomic of each per wave
 //   finish   (components) / apply (filter): ncomp[k] = -1 for a row in which a loop reached its bound
-//   apply    grid over the ADDRESS of out's row (mask_rows.h), one chunk written per lane, comp read 64 consecutive vertices per wave and pass
-//            and the decisions traded by ballots: out = the component of the vertex is kept,
-//            size >= min_vertices and (double)size >= min_share * (double)largest; nkept and mask_points summed over the kept roots.  It
-//            reads comp and size and never masks, so out may be masks
+//   apply    grid over the ADDRESS of out's row, one chunk written per lane (both walks of mask_rows.h): out = the component of the vertex
+//            is kept, size >= min_vertices and (double)size >= min_share * (double)largest; nkept and mask_points summed over the kept
+//            roots.  It reads comp and size and never masks, so out may be masks
 //
 // TERMINATION: a walk from x visits x > x1 > x2 > ... >= 0, at most v vertices; a failed compare-and-swap on hi returns a parent below hi,
 // the next attempt's larger root lies below that, so the attempts of one union have strictly descending targets, at most v.  Both loops
@@ -100,46 +98,53 @@ __global__ __launch_bounds__(MC_T) void mc_init_kernel(int v, const unsigned cha
     }
     const unsigned char* p = masks + (long)row * v;
     const int i0 = (blockIdx.x * MC_T + threadIdx.x) * MASK_ROW_VEC - mask_row_a0(p);    // >= -15; < 2^24 + 16 * MC_T
-    const unsigned bits = mask_row_load(p, i0, v);                   // (nobody returns: the lanes trade their bits below)
-    // The wave's 64 chunks are 1024 consecutive vertices.  A lane that wrote its own 16 would put 64 bytes between one lane's dword and
-    // the next (454 us at 100 x 500 000, measured); in pass t the wave writes the 64 consecutive vertices 64 t .. 64 t + 63 instead, lane l
-    // taking bit l % 16 of the chunk of lane 4 t + l / 16.
-    const int lane = lane_id();
-    const int first = i0 - lane * MASK_ROW_VEC;                      // the first vertex of the wave's chunks, >= -15
+    const unsigned bits = mask_row_load(p, i0, v);                   // (nobody returns: the wave walk needs every lane)
     int* par = parent + (long)row * v;
     int* sz = size + (long)row * v;
-#pragma unroll
-    for (int t = 0; t < MASK_ROW_VEC; ++t) {
-        const unsigned theirs = (unsigned)__shfl((int)bits, 4 * t + (lane >> 4), GSPN_WAVE);
-        const int i = first + GSPN_WAVE * t + lane;
-        if (i >= 0 && i < v) {
-            par[i] = (theirs >> (lane & 15)) & 1u ? i : -1;
-            sz[i] = 0;
-        }
-    }
+    mask_wave_read(bits, i0, v, [&](int i, bool set) {
+        par[i] = set ? i : -1;
+        sz[i] = 0;
+    });
 }
 
-// grid (ceil(v / MC_T), words)
-__global__ __launch_bounds__(MC_T) void mc_table_kernel(int r, int v, int words, const int* __restrict__ parent, u64* __restrict__ table) {
+// grid (ceil(v / MC_T), words): table bit k = parent[k][x] >= 0 and, with SETS (the holes), set bit k = parent[k][x] == -2, in one read
+template <bool SETS>
+__global__ __launch_bounds__(MC_T) void mc_table_kernel(int r, int v, int words, const int* __restrict__ parent, u64* __restrict__ table,
+                                                        u64* __restrict__ set) {
     const int x = blockIdx.x * MC_T + threadIdx.x;
     if (x >= v) return;
     const int k0 = blockIdx.y * 64, k1 = min(r, k0 + 64);
-    u64 word = 0ull;
-    for (int k = k0; k < k1; ++k)
-        if (parent[(long)k * v + x] >= 0) word |= 1ull << (k - k0);
-    table[(long)x * words + blockIdx.y] = word;
+    u64 c = 0ull, s = 0ull;
+    for (int k = k0; k < k1; ++k) {
+        const int p = parent[(long)k * v + x];
+        if (p >= 0) c |= 1ull << (k - k0);
+        if (SETS && p == -2) s |= 1ull << (k - k0);
+    }
+    table[(long)x * words + blockIdx.y] = c;
+    if (SETS) set[(long)x * words + blockIdx.y] = s;
 }
+
+// Face t, read once.  edge(e, v, u, w) -> the ends of edge e of {a,b}, {b,c}, {a,c}; false where one lies outside [0, v) or u == w: no edge
+struct McFace {
+    int a, b, c;
+    __device__ __forceinline__ McFace(const int* __restrict__ faces, long t) : a(faces[3 * t]), b(faces[3 * t + 1]), c(faces[3 * t + 2]) {}
+    __device__ __forceinline__ bool edge(int e, int v, int& u, int& w) const {
+        const int eu[3] = {a, b, a}, ew[3] = {b, c, c};
+        u = eu[e];
+        w = ew[e];
+        return (unsigned)u < (unsigned)v && (unsigned)w < (unsigned)v && u != w;
+    }
+};
 
 // grid-stride over the faces.  parent is read and written by every lane: no __restrict__
 __global__ __launch_bounds__(MC_T) void mc_hook_kernel(int v, int f, int words, const int* __restrict__ faces, const u64* __restrict__ table,
                                                        int* parent, int* __restrict__ bad) {
     for (long t = blockIdx.x * (long)MC_T + threadIdx.x; t < f; t += (long)gridDim.x * MC_T) {
-        const int a = faces[3 * t], b = faces[3 * t + 1], c = faces[3 * t + 2];
-        const int eu[3] = {a, b, a}, ew[3] = {b, c, c};
+        const McFace face(faces, t);
 #pragma unroll
         for (int e = 0; e < 3; ++e) {
-            const int u = eu[e], w = ew[e];
-            if ((unsigned)u >= (unsigned)v || (unsigned)w >= (unsigned)v || u == w) continue;        // an end outside [0, v): no edge
+            int u, w;
+            if (!face.edge(e, v, u, w)) continue;
             for (int j = 0; j < words; ++j) {
                 u64 m = table[(long)u * words + j] & table[(long)w * words + j];
                 while (m != 0ull) {
@@ -227,16 +232,11 @@ __global__ __launch_bounds__(MC_T) void mc_apply_kernel(int v, int min_vertices,
     const int* c = comp + (long)row * v;
     const int* sz = size + (long)row * v;
     const double floor_share = min_share * (double)largest[row];
-    // As in init, the wave's 64 chunks are 1024 consecutive vertices: in pass t lane l decides vertex 64 t + l of them (one coalesced read of
-    // comp; a lane that read its own 16 took 135 us at 100 x 500 000, measured), the ballot of the pass holds the bits of four chunks, and
-    // the lane whose chunk is among them keeps its 16.
-    const int lane = lane_id();
-    const int first = i0 - lane * MASK_ROW_VEC;                      // the first vertex of the wave's chunks, >= -15
     unsigned bits = 0u;
     int kept_roots = 0, kept_points = 0;
 #pragma unroll
     for (int t = 0; t < MASK_ROW_VEC; ++t) {
-        const int i = first + GSPN_WAVE * t + lane;
+        const int i = mask_wave_vertex(i0, t);
         bool on = false;
         if (i >= 0 && i < v) {
             const int root = c[i];
@@ -249,8 +249,7 @@ __global__ __launch_bounds__(MC_T) void mc_apply_kernel(int v, int min_vertices,
                 }
             }
         }
-        const u64 word = __ballot(on);
-        if ((lane >> 2) == t) bits = (unsigned)(word >> (16 * (lane & 3))) & 0xFFFFu;
+        mask_wave_write(on, t, bits);
     }
     mask_row_store(p, i0, v, bits);
     kept_roots = wave_sum_lane0(kept_roots);
@@ -261,21 +260,28 @@ __global__ __launch_bounds__(MC_T) void mc_apply_kernel(int v, int min_vertices,
     }
 }
 
+// the two grid shapes of the per-row kernels: one chunk of the address walk per lane, and one vertex per lane
+dim3 mc_by_vector(int r, int v) { return dim3((unsigned)((mask_row_chunks(v) + MC_T - 1) / MC_T), (unsigned)r); }
+dim3 mc_by_vertex(int r, int v) { return dim3((unsigned)((v + MC_T - 1) / MC_T), (unsigned)r); }
+
+// table, hook, compress over f > 0 faces: the trees of parent joined along the edges; set is the holes' second table, or null
+void mc_join(hipStream_t st, int r, int v, int f, int words, const int* faces, int* parent, u64* table, u64* set, int* bad) {
+    const dim3 by_word(mc_by_vertex(r, v).x, (unsigned)words);
+    if (set) hipLaunchKernelGGL(mc_table_kernel<true>, by_word, dim3(MC_T), 0, st, r, v, words, parent, table, set);
+    else hipLaunchKernelGGL(mc_table_kernel<false>, by_word, dim3(MC_T), 0, st, r, v, words, parent, table, set);
+    hipLaunchKernelGGL(mc_hook_kernel, dim3(grid_for(f, MC_T)), dim3(MC_T), 0, st, v, f, words, faces, table, parent, bad);
+    hipLaunchKernelGGL(mc_compress_kernel, mc_by_vertex(r, v), dim3(MC_T), 0, st, v, parent, bad);
+}
+
 // init .. stats: comp (= parent), ncomp and largest of every row
 void mc_label(hipStream_t st, int r, int v, int f, const McLayout& l, const unsigned char* masks, const int* faces, char* base, int* comp,
               int* ncomp, int* largest, int* nkept, int* mask_points) {
-    u64* table = reinterpret_cast<u64*>(base + l.table);
     int* size = reinterpret_cast<int*>(base + l.size);
     int* bad = reinterpret_cast<int*>(base + l.bad);
-    const dim3 by_vector((unsigned)((mask_row_chunks(v) + MC_T - 1) / MC_T), (unsigned)r), by_vertex((unsigned)((v + MC_T - 1) / MC_T), (unsigned)r);
-    hipLaunchKernelGGL(mc_init_kernel, by_vector, dim3(MC_T), 0, st, v, masks, comp, size, bad, ncomp, largest, nkept, mask_points);
-    if (f > 0) {
-        hipLaunchKernelGGL(mc_table_kernel, dim3(by_vertex.x, (unsigned)l.words), dim3(MC_T), 0, st, r, v, l.words, comp, table);
-        hipLaunchKernelGGL(mc_hook_kernel, dim3(grid_for(f, MC_T)), dim3(MC_T), 0, st, v, f, l.words, faces, table, comp, bad);
-    }
-    if (f > 0) hipLaunchKernelGGL(mc_compress_kernel, by_vertex, dim3(MC_T), 0, st, v, comp, bad);       // without faces every vertex is a root
-    hipLaunchKernelGGL(mc_flatten_kernel, by_vertex, dim3(MC_T), 0, st, v, comp, size, bad);
-    hipLaunchKernelGGL(mc_stats_kernel, by_vertex, dim3(MC_T), 0, st, v, comp, size, ncomp, largest);
+    hipLaunchKernelGGL(mc_init_kernel, mc_by_vector(r, v), dim3(MC_T), 0, st, v, masks, comp, size, bad, ncomp, largest, nkept, mask_points);
+    if (f > 0) mc_join(st, r, v, f, l.words, faces, comp, reinterpret_cast<u64*>(base + l.table), nullptr, bad);      // without faces every vertex is a root
+    hipLaunchKernelGGL(mc_flatten_kernel, mc_by_vertex(r, v), dim3(MC_T), 0, st, v, comp, size, bad);
+    hipLaunchKernelGGL(mc_stats_kernel, mc_by_vertex(r, v), dim3(MC_T), 0, st, v, comp, size, ncomp, largest);
 }
 
 }  // namespace
@@ -308,8 +314,8 @@ extern "C" int gspn_mask_component_filter(int r, int v, int f, const unsigned ch
     int* comp = reinterpret_cast<int*>(base + l.parent);
     int* largest = reinterpret_cast<int*>(base + l.largest);
     mc_label(st, r, v, f, l, masks, faces, base, comp, ncomp, largest, nkept, mask_points);
-    hipLaunchKernelGGL(mc_apply_kernel, dim3((unsigned)((mask_row_chunks(v) + MC_T - 1) / MC_T), (unsigned)r), dim3(MC_T), 0, st, v, min_vertices, min_share,
-                       comp, reinterpret_cast<int*>(base + l.size), largest, reinterpret_cast<int*>(base + l.bad), out, mask_points, ncomp, nkept);
+    hipLaunchKernelGGL(mc_apply_kernel, mc_by_vector(r, v), dim3(MC_T), 0, st, v, min_vertices, min_share, comp, reinterpret_cast<int*>(base + l.size),
+                       largest, reinterpret_cast<int*>(base + l.bad), out, mask_points, ncomp, nkept);
     return gspn_launch_status();
 }
 
@@ -326,7 +332,7 @@ extern "C" int gspn_mask_component_filter(int r, int v, int f, const unsigned ch
 //            are finite reduced per wave and landed with integer atomicMin / atomicMax on the keys of float_keys.h
 //   init     grid over the address of the row: parent = set ? -2 : (inside ? x : -1), size = 0; inside is lo <= c && c <= hi on the three
 //            axes as float compares, so a NaN coordinate, and every vertex of a row without a box, is outside
-//   tables   grid (v / 256, words): both vertex-major tables in one read of parent, cand (parent >= 0) and set (parent == -2)
+//   table    grid (v / 256, words): mc_table_kernel<true>, both vertex-major tables in one read of parent, cand (parent >= 0) and set (parent == -2)
 //   hook, compress, flatten   the kernels above on the cand table: parent[k][x] = the root, size[k][root] = the component's vertices
 //   mark     one face per lane, grid ceil(f / 256): per edge and word, cand[u] & set[w] are the rows in which u's component touches,
 //            cand[u] & ~cand[w] & ~set[w] those in which it is open, and the same with the ends swapped; per bit one integer atomicOr of
@@ -367,36 +373,29 @@ __global__ __launch_bounds__(MC_T) void hf_box_kernel(int v, const unsigned char
     const int row = blockIdx.y;
     const unsigned char* p = masks + (long)row * v;
     const int i0 = (blockIdx.x * MC_T + threadIdx.x) * MASK_ROW_VEC - mask_row_a0(p);    // >= -15; < 2^24 + 16 * MC_T
-    const unsigned bits = mask_row_load(p, i0, v);                   // (nobody returns: the lanes trade their bits below)
+    const unsigned bits = mask_row_load(p, i0, v);                   // (nobody returns: the wave walk needs every lane)
     if (__ballot(bits != 0u) == 0ull) return;                        // uniform over the wave: nothing set in its 1024 vertices
-    // as in mc_init_kernel, in pass t the wave takes the 64 consecutive vertices 64 t .. 64 t + 63 of its chunks: xyz is read coalesced
-    const int lane = lane_id();
-    const int first = i0 - lane * MASK_ROW_VEC;
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
     int count = 0;
+    mask_wave_read(bits, i0, v, [&](int i, bool set) {
+        if (!set) return;
+        ++count;
+        const float c[3] = {xyz[3l * i], xyz[3l * i + 1], xyz[3l * i + 2]};
+        if (fabsf(c[0]) < INFINITY && fabsf(c[1]) < INFINITY && fabsf(c[2]) < INFINITY) {             // a NaN fails the compare
 #pragma unroll
-    for (int t = 0; t < MASK_ROW_VEC; ++t) {
-        const unsigned theirs = (unsigned)__shfl((int)bits, 4 * t + (lane >> 4), GSPN_WAVE);
-        const int i = first + GSPN_WAVE * t + lane;
-        if (i >= 0 && i < v && ((theirs >> (lane & 15)) & 1u)) {
-            ++count;
-            const float c[3] = {xyz[3l * i], xyz[3l * i + 1], xyz[3l * i + 2]};
-            if (fabsf(c[0]) < INFINITY && fabsf(c[1]) < INFINITY && fabsf(c[2]) < INFINITY) {         // a NaN fails the compare
-#pragma unroll
-                for (int a = 0; a < 3; ++a) {
-                    lo[a] = fminf(lo[a], c[a]);
-                    hi[a] = fmaxf(hi[a], c[a]);
-                }
+            for (int a = 0; a < 3; ++a) {
+                lo[a] = fminf(lo[a], c[a]);
+                hi[a] = fmaxf(hi[a], c[a]);
             }
         }
-    }
+    });
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         lo[a] = wave_min_f32(lo[a]);
         hi[a] = wave_max_f32(hi[a]);
     }
     count = wave_sum_lane0(count);
-    if (lane == 0) {
+    if (lane_id() == 0) {
         atomicAdd(&points_in[row], count);
         if (lo[0] <= hi[0]) {                                        // the wave saw a finite vertex: all three axes have one
             // (Reading the six keys first, past the L1, and landing only what would change them was measured and is slower: the wave then
@@ -416,7 +415,7 @@ __global__ __launch_bounds__(MC_T) void hf_init_kernel(int v, const unsigned cha
     const int row = blockIdx.y;
     const unsigned char* p = masks + (long)row * v;
     const int i0 = (blockIdx.x * MC_T + threadIdx.x) * MASK_ROW_VEC - mask_row_a0(p);    // >= -15; < 2^24 + 16 * MC_T
-    const unsigned bits = mask_row_load(p, i0, v);                   // (nobody returns: the lanes trade their bits below)
+    const unsigned bits = mask_row_load(p, i0, v);                   // (nobody returns: the wave walk needs every lane)
     float lo[3], hi[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
@@ -424,43 +423,20 @@ __global__ __launch_bounds__(MC_T) void hf_init_kernel(int v, const unsigned cha
         hi[a] = np_unkey(box[6 * row + 3 + a]);
     }
     const bool boxed = lo[0] <= hi[0];
-    const int lane = lane_id();
-    const int first = i0 - lane * MASK_ROW_VEC;                      // the first vertex of the wave's chunks, >= -15
     int* par = parent + (long)row * v;
     int* sz = size + (long)row * v;
-#pragma unroll
-    for (int t = 0; t < MASK_ROW_VEC; ++t) {
-        const unsigned theirs = (unsigned)__shfl((int)bits, 4 * t + (lane >> 4), GSPN_WAVE);
-        const int i = first + GSPN_WAVE * t + lane;
-        if (i >= 0 && i < v) {
-            int value = -2;
-            if (((theirs >> (lane & 15)) & 1u) == 0u) {
-                value = -1;
-                if (boxed) {
-                    const float x = xyz[3l * i], y = xyz[3l * i + 1], z = xyz[3l * i + 2];
-                    if (lo[0] <= x && x <= hi[0] && lo[1] <= y && y <= hi[1] && lo[2] <= z && z <= hi[2]) value = i;
-                }
+    mask_wave_read(bits, i0, v, [&](int i, bool set) {
+        int value = -2;
+        if (!set) {
+            value = -1;
+            if (boxed) {
+                const float x = xyz[3l * i], y = xyz[3l * i + 1], z = xyz[3l * i + 2];
+                if (lo[0] <= x && x <= hi[0] && lo[1] <= y && y <= hi[1] && lo[2] <= z && z <= hi[2]) value = i;
             }
-            par[i] = value;
-            sz[i] = 0;
         }
-    }
-}
-
-// grid (ceil(v / MC_T), words)
-__global__ __launch_bounds__(MC_T) void hf_tables_kernel(int r, int v, int words, const int* __restrict__ parent, u64* __restrict__ cand,
-                                                         u64* __restrict__ set) {
-    const int x = blockIdx.x * MC_T + threadIdx.x;
-    if (x >= v) return;
-    const int k0 = blockIdx.y * 64, k1 = min(r, k0 + 64);
-    u64 c = 0ull, s = 0ull;
-    for (int k = k0; k < k1; ++k) {
-        const int p = parent[(long)k * v + x];
-        if (p >= 0) c |= 1ull << (k - k0);
-        if (p == -2) s |= 1ull << (k - k0);
-    }
-    cand[(long)x * words + blockIdx.y] = c;
-    set[(long)x * words + blockIdx.y] = s;
+        par[i] = value;
+        sz[i] = 0;
+    });
 }
 
 // the flag ORed into the size word of u's root in every row of m
@@ -483,12 +459,11 @@ __global__ __launch_bounds__(MC_T) void hf_mark_kernel(int v, int f, int words, 
                                                        const u64* __restrict__ set, const int* __restrict__ parent, int* size, int* __restrict__ bad) {
     const long t = blockIdx.x * (long)MC_T + threadIdx.x;
     if (t >= f) return;
-    const int a = faces[3 * t], b = faces[3 * t + 1], c = faces[3 * t + 2];
-    const int eu[3] = {a, b, a}, ew[3] = {b, c, c};
+    const McFace face(faces, t);
 #pragma unroll
     for (int e = 0; e < 3; ++e) {
-        const int u = eu[e], w = ew[e];
-        if ((unsigned)u >= (unsigned)v || (unsigned)w >= (unsigned)v || u == w) continue;            // an end outside [0, v): no edge
+        int u, w;
+        if (!face.edge(e, v, u, w)) continue;
         for (int j = 0; j < words; ++j) {
             const u64 cu = cand[(long)u * words + j], cw = cand[(long)w * words + j];
             if ((cu | cw) == 0ull) continue;
@@ -517,14 +492,11 @@ __global__ __launch_bounds__(MC_T) void hf_apply_kernel(int v, int max_vertices,
     const int* par = parent + (long)row * v;
     const int* sz = size + (long)row * v;
     const double ceiling_share = max_share * (double)points_in[row];
-    // as in mc_apply_kernel: in pass t lane l decides vertex 64 t + l of the wave's 1024, and the ballot of the pass holds four chunks
-    const int lane = lane_id();
-    const int first = i0 - lane * MASK_ROW_VEC;                      // the first vertex of the wave's chunks, >= -15
     unsigned bits = 0u;
     int holes = 0, filled = 0;
 #pragma unroll
     for (int t = 0; t < MASK_ROW_VEC; ++t) {
-        const int i = first + GSPN_WAVE * t + lane;
+        const int i = mask_wave_vertex(i0, t);
         bool on = false;
         if (i >= 0 && i < v) {
             const int root = par[i];
@@ -538,8 +510,7 @@ __global__ __launch_bounds__(MC_T) void hf_apply_kernel(int v, int max_vertices,
                 }
             }
         }
-        const u64 word = __ballot(on);
-        if ((lane >> 2) == t) bits = (unsigned)(word >> (16 * (lane & 3))) & 0xFFFFu;
+        mask_wave_write(on, t, bits);
     }
     mask_row_store(p, i0, v, bits);
     holes = wave_sum_lane0(holes);
@@ -571,18 +542,15 @@ extern "C" int gspn_mask_hole_fill(int r, int v, int f, const unsigned char* mas
     int* box = reinterpret_cast<int*>(base + l.box);
     int* points_in = reinterpret_cast<int*>(base + l.points);
     int* parent = label ? label : reinterpret_cast<int*>(base + l.parent);
-    const dim3 by_vector((unsigned)((mask_row_chunks(v) + MC_T - 1) / MC_T), (unsigned)r), by_vertex((unsigned)((v + MC_T - 1) / MC_T), (unsigned)r);
     hipLaunchKernelGGL(hf_prime_kernel, dim3((unsigned)((r + MC_T - 1) / MC_T)), dim3(MC_T), 0, st, r, box, points_in, bad, mask_points, nholes, nfilled);
-    hipLaunchKernelGGL(hf_box_kernel, by_vector, dim3(MC_T), 0, st, v, masks, xyz, box, points_in);
-    hipLaunchKernelGGL(hf_init_kernel, by_vector, dim3(MC_T), 0, st, v, masks, xyz, box, parent, size);
+    hipLaunchKernelGGL(hf_box_kernel, mc_by_vector(r, v), dim3(MC_T), 0, st, v, masks, xyz, box, points_in);
+    hipLaunchKernelGGL(hf_init_kernel, mc_by_vector(r, v), dim3(MC_T), 0, st, v, masks, xyz, box, parent, size);
     if (f > 0) {                                                     // without faces nothing touches: no holes
-        hipLaunchKernelGGL(hf_tables_kernel, dim3(by_vertex.x, (unsigned)l.words), dim3(MC_T), 0, st, r, v, l.words, parent, cand, set);
-        hipLaunchKernelGGL(mc_hook_kernel, dim3(grid_for(f, MC_T)), dim3(MC_T), 0, st, v, f, l.words, faces, cand, parent, bad);
-        hipLaunchKernelGGL(mc_compress_kernel, by_vertex, dim3(MC_T), 0, st, v, parent, bad);
-        hipLaunchKernelGGL(mc_flatten_kernel, by_vertex, dim3(MC_T), 0, st, v, parent, size, bad);
+        mc_join(st, r, v, f, l.words, faces, parent, cand, set, bad);
+        hipLaunchKernelGGL(mc_flatten_kernel, mc_by_vertex(r, v), dim3(MC_T), 0, st, v, parent, size, bad);
         hipLaunchKernelGGL(hf_mark_kernel, dim3((unsigned)((f + MC_T - 1) / MC_T)), dim3(MC_T), 0, st, v, f, l.words, faces, cand, set, parent, size, bad);
     }
-    hipLaunchKernelGGL(hf_apply_kernel, by_vector, dim3(MC_T), 0, st, v, max_vertices, max_share, parent, size, points_in, bad, out, mask_points, nholes,
-                       nfilled);
+    hipLaunchKernelGGL(hf_apply_kernel, mc_by_vector(r, v), dim3(MC_T), 0, st, v, max_vertices, max_share, parent, size, points_in, bad, out, mask_points,
+                       nholes, nfilled);
     return gspn_launch_status();
 }

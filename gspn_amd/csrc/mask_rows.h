@@ -1,5 +1,6 @@
 // mask_rows.h -- rows of v mask bytes read and written 16 bytes at a time, shared by the per-vertex mask stages: segments.hip (sv_count_kernel
-// reads), mask_nms.hip (mn_pack_kernel reads, mn_apply_kernel writes) and components.hip (mc_init_kernel, hf_box_kernel and hf_init_kernel read, mc_apply_kernel and hf_apply_kernel write).
+// reads), mask_nms.hip (mn_pack_kernel reads, mn_apply_kernel writes) and components.hip, whose kernels also take the wave walk below
+// (mc_init_kernel, hf_box_kernel and hf_init_kernel read, mc_apply_kernel and hf_apply_kernel write).
 //
 // THE ADDRESS WALK.  v is arbitrary, so a row p = base + row * v starts at an arbitrary address and a vector grid laid over the row's
 // VERTICES would be misaligned in most rows.  The grid is laid over the row's ADDRESS instead: with a0 = address of p modulo 16
@@ -11,8 +12,14 @@
 //
 // A chunk travels as 16 bits, bit k = "byte i0 + k is set" (any nonzero byte is set; a written byte is 0 or 1); the bits of vertices
 // outside [0, v) are zero when read and ignored when written.  No LDS, no barrier; every function is inlined.
+//
+// THE WAVE WALK.  The 64 chunks of a wave are 1024 consecutive vertices.  A lane that went through its own 16 would touch every per-vertex
+// array (parent, size, xyz) with 64 bytes between one lane's dword and the next: 454 us for mc_init_kernel's stores and 135 us for
+// mc_apply_kernel's loads at 100 x 500 000, measured.  So in pass t of 16 the wave takes the 64 consecutive vertices 64 t .. 64 t + 63 of
+// its chunks, lane l vertex 64 t + l, which is bit l % 16 of the chunk of lane 4 t + l / 16.  Shuffles and ballots carry the bits, so
+// EVERY lane of the wave must reach every pass: between mask_row_load and the walk only a return that is uniform over the wave.
 #pragma once
-#include <stdint.h>
+#include "common.h"
 
 #define MASK_ROW_VEC 16                  // bytes per aligned vector
 
@@ -60,4 +67,28 @@ __device__ __forceinline__ void mask_row_store(unsigned char* p, int i0, int v, 
             if (i >= 0 && i < v) p[i] = (unsigned char)((bits >> k) & 1u);
         }
     }
+}
+
+// the vertex of this lane in pass t of the wave walk, i0 being the first vertex of the lane's own chunk; it may lie outside [0, v)
+__device__ __forceinline__ int mask_wave_vertex(int i0, int t) { return i0 - lane_id() * MASK_ROW_VEC + GSPN_WAVE * t + lane_id(); }
+
+// The wave walk, reading: body(i, set) for every vertex i in [0, v) of the wave's chunks, set being its bit; bits is what mask_row_load
+// gave this lane for its chunk at i0.
+template <class Body>
+__device__ __forceinline__ void mask_wave_read(unsigned bits, int i0, int v, Body body) {
+    const int lane = lane_id();
+#pragma unroll
+    for (int t = 0; t < MASK_ROW_VEC; ++t) {
+        const unsigned theirs = (unsigned)__shfl((int)bits, 4 * t + (lane >> 4), GSPN_WAVE);
+        const int i = mask_wave_vertex(i0, t);
+        if (i >= 0 && i < v) body(i, ((theirs >> (lane & 15)) & 1u) != 0u);
+    }
+}
+
+// The wave walk, writing, pass t: on is the bit of mask_wave_vertex(i0, t), false outside [0, v).  The ballot holds the bits of four chunks
+// and the lane whose chunk is among them keeps its 16: after the 16 passes bits is the lane's chunk, for mask_row_store.  (The pass loop
+// is the kernel's: with a lambda for a body that also counts, the apply kernels compile to other code, profiles/components_fold.txt.)
+__device__ __forceinline__ void mask_wave_write(bool on, int t, unsigned& bits) {
+    const unsigned long long word = __ballot(on);
+    if ((lane_id() >> 2) == t) bits = (unsigned)(word >> (16 * (lane_id() & 3))) & 0xFFFFu;
 }

@@ -1,18 +1,19 @@
-"""GPU tests of the address walk the per-vertex mask stages share (csrc/mask_rows.h): segment voting, mask NMS and mask components read,
-and the last two write, rows of V mask bytes in 16-byte chunks laid over the row's ADDRESS.  Rows set in exactly one byte, the byte put
-at each of the 16 positions of a chunk, in the head chunk, in full chunks and in the tail chunk of rows at every misalignment; and out= at
-a misaligned base inside a poisoned buffer.  Every comparison is for equal bits, against the numpy restatements of the three stages."""
+"""GPU tests of the address walk the per-vertex mask stages share (csrc/mask_rows.h): segment voting, mask NMS, mask components and mask
+holes read, and the last three write, rows of V mask bytes in 16-byte chunks laid over the row's ADDRESS.  Rows set in exactly one byte
+(for the holes: unset in exactly one), the byte put at each of the 16 positions of a chunk, in the head chunk, in full chunks and in the
+tail chunk of rows at every misalignment; and out= at a misaligned base inside a poisoned buffer.  Every comparison is for equal bits,
+against the numpy restatements of the four stages."""
 import numpy as np
 import pytest
 import torch
 
-from tests import components_ref, mask_nms_ref, segments_ref
+from tests import components_ref, holes_ref, mask_nms_ref, segments_ref
 
 pytestmark = pytest.mark.gpu
 
 R = 16                                                                # rows k * V apart: V = 67 puts them at all 16 misalignments
 BYTES = np.array([0, 1, 2, 255], np.uint8)
-STAGES = ("segments", "mask_nms", "components")
+STAGES = ("segments", "mask_nms", "components", "holes")
 PLACES = ("head", "inner", "late", "tail", "stairs")
 POISON = 0xAB
 NO_FACES = np.zeros((0, 3), np.int32)
@@ -39,6 +40,14 @@ def one_byte_rows(v, place):
     host[k, at] = BYTES[1 + k % 3]
     masks.copy_(torch.from_numpy(host))
     return masks, host, at, (a0 + at) % 16
+
+
+def path_mesh(v):
+    """-> the path 0 - 1 - ... - V-1 as degenerate faces (a, b, b), and the vertices on a line, xyz[i] = (i, 0, 0)"""
+    i = np.arange(v - 1)
+    xyz = np.zeros((v, 3), np.float32)
+    xyz[:, 0] = np.arange(v)
+    return np.stack((i, i + 1, i + 1), axis=1).astype(np.int32), xyz
 
 
 def test_the_rows_of_67_vertices_start_at_every_misalignment_and_the_places_cover_every_position():
@@ -87,6 +96,21 @@ def test_a_vector_set_in_exactly_one_byte_at_each_of_its_positions(stage, v, pla
         want = mask_nms_ref.mask_nms_ref(host, iou_th=0.0)
         assert all(np.array_equal(g, w) for g, w in zip(got, want))
         assert got[1].tolist() == [1] + [0] * (R - 1) and got[2].tolist() == [2 if at[0] != v - 1 else 1] + [0] * (R - 1)
+    elif stage == "holes":
+        from gspn_amd.holes import hole_fill
+        faces, xyz = path_mesh(v)
+        mirror = BYTES[1 + (rows[:, None] + np.arange(v)[None, :]) % 3]              # the mirror case: every byte set but the one at the place
+        mirror[rows, at] = 0
+        masks.copy_(torch.from_numpy(mirror))                        # in place: the rows stay at the addresses the places were computed for
+        got = [t.cpu().numpy() for t in hole_fill(masks, dev(faces), dev(xyz), max_vertices=1, label=True)]
+        want = holes_ref.hole_fill_ref(mirror, faces, xyz, 1)
+        assert len(got) == len(want) == 5 and all(np.array_equal(g, w) for g, w in zip(got, want))
+        inner = ((at != 0) & (at != v - 1)).astype(np.int32)          # an unset end of the path lies outside the box of the set vertices: not filled
+        assert np.array_equal(got[0][rows, at], inner) and np.array_equal(got[1], v - 1 + inner)
+        assert np.array_equal(got[2], inner) and np.array_equal(got[3], inner)
+        out, points, nholes, nfilled = hole_fill(masks, dev(faces), dev(xyz), max_vertices=0)           # the normalised input
+        assert np.array_equal(out.cpu().numpy(), (mirror != 0).astype(np.uint8)) and points.tolist() == [v - 1] * R
+        assert nholes.tolist() == nfilled.tolist() == [0] * R
     else:
         from gspn_amd.components import component_filter, mask_components
         comp, ncomp, largest = mask_components(masks, dev(NO_FACES))   # without faces a set vertex is its own component
@@ -121,6 +145,12 @@ def test_out_at_a_misaligned_base_is_written_in_full_and_nothing_around_it(stage
         got = mask_nms(masks, iou_th=0.3, out=out)
         want = mask_nms_ref.mask_nms_ref(host, iou_th=0.3)
         assert 0 < int(want[1].sum()) < R                             # suppressed rows, written as zeros, and kept ones
+    elif stage == "holes":
+        from gspn_amd.holes import hole_fill
+        faces, xyz = path_mesh(v)
+        got = hole_fill(masks, dev(faces), dev(xyz), max_vertices=3, out=out)
+        want = holes_ref.hole_fill_ref(host, faces, xyz, 3)[:4]
+        assert int(want[3].sum()) > 0 and int(want[0].sum()) < R * v  # filled vertices, and unset ones left
     else:
         from gspn_amd.components import component_filter
         faces = np.stack((np.arange(v - 2), np.arange(1, v - 1), np.arange(2, v)), axis=1).astype(np.int32)

@@ -5,9 +5,10 @@ REFERENCE's own nms_3d (:436-466) run once per class, on the seeded cases of tes
 
 As tools/make_golden_roi.py: lines 436-466 are cut out of the reference at generation time, exec'd with numpy, and only inputs and outputs
 are stored -- boxes, scores, class ids, the arguments and the selected rows after the intersection of :893 and the top_k of :900 -- nothing
-of the source.  refine_detections and unmold_segmentation themselves are TensorFlow graph code and TensorFlow is not available where
-this runs, so they cannot be executed: the loop over the classes, the index sets and the top_k around the reference's function are the
-restatement of tests/detect_ref.py.  The generator asserts what the cases are there for: pairwise distinct scores per scene, a scene with more
+of the source.  Here the loop over the classes, the index sets and the top_k around the reference's function are the restatement of
+tests/detect_ref.py; refine_detections and unmold_segmentation themselves, TensorFlow graph code, are executed by
+tools/make_golden_graph.py over the numpy stand-in tools/tf_numpy.py, which pins that loop to the reference's own lines too
+(tests/golden/graph/refine_detections.npz).  The generator asserts what the cases are there for: pairwise distinct scores per scene, a scene with more
 survivors than max_output_size, a class that reaches max_per_class, a zero-volume candidate that is picked again, a scene without any
 candidate."""
 import argparse
